@@ -9,9 +9,11 @@ N = 1 (default), workload "track240" = BASELINE.json configs[1]: offline conv st
 sliCQT), ONE 240 s track (10,584,000 samples = 4 full 59.4 s chunks + a 98,240-sample tail),
 Wiener off (mix-phase), seeded synthetic audio and weights (no dataset / checkpoint offline).
 A "step" = one full pass sliCQT -> CDAE -> phasemix -> isliCQT over that track, input already
-resident in HBM.  The same line carries, outside the timed region: the per-kernel HBM / MFMA
+resident in HBM.  A plain run sets up, warms up, times the K steps and prints the headline.
+With --full the same line also carries, outside the timed region: the per-kernel HBM / MFMA
 roofline fractions, configs[2] (Wiener-EM on) and configs[4] (the B = 16 training step) as
 `variants`, the split-bf16 arithmetic variants, and the CPU oracle on this box's host cores.
+--dump-outputs DIR writes a fixed seeded sample of the last timed step's stems (dump_outputs).
 
 N > 1, workload "testset50" = BASELINE.json configs[3]: 50 seeded track lengths in [150, 420] s
 flattened into (track, chunk) work items, dealt longest-first to the ranks (one process per GPU,
@@ -548,14 +550,20 @@ def main():
     ap.add_argument("--tracks", type=int, default=TESTSET_TRACKS, help="testset50: number of tracks")
     ap.add_argument("--stack", type=int, default=4, help="testset50: work items per round / stacked pass")
     ap.add_argument("--wiener", action="store_true", help="BASELINE configs[2]: Wiener-EM on (default off = configs[1])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="track240: beside the headline also the per-kernel table and rooflines (instrumented warm-up step, the "
+                         "dominant kernel timed inside the timed region), the step's GPU span / host enqueue split, the variants and "
+                         "the CPU baseline.  Default: only set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="track240: after the timed steps write a fixed seeded sample of the last step's stems to DIR/*.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--cpu-baseline-clip", action="store_true",
                     help="time the CPU oracle on a 30 s clip (~3 s of host time) instead of the whole 240 s track (the workload of "
                          "`value`: ~40 s of host time on 16 threads)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x6", "bf16x3"],
                     help="arithmetic of the convolution contractions for the headline value (default: exact fp32)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra measurements outside the timed region")
+    ap.add_argument("--no-variants", action="store_true", help="skip the extra measurements outside the timed region (track240: with --full)")
     ap.add_argument("--graph", action="store_true",
                     help="track240: replay the step from a captured HIP graph (Separator.forward_graphed)")
     ap.add_argument("--gather-at-1", action="store_true",
@@ -570,6 +578,10 @@ def main():
     ap.add_argument("--no-gather", action="store_true",
                     help="testset50: headline without the all-gather (default: with it; the other one is a variant)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.workload or ("track240" if args.gpus == 1 else "testset50")) != "track240":
+        ap.error("--dump-outputs is implemented for the track240 workload")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -699,6 +711,14 @@ def bench_track(args, sep, dev, world, rank, dist):
     def step():
         return run(track)
 
+    if not args.full:                     # the headline alone: no instrumentation, no side measurements
+        for _ in range(args.warmup):
+            step()
+        dt, out = timed_steps(step, args.steps, world, dist, dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)
+        return track_headline(args, world, dt) if rank == 0 else None
+
     # Warm-up steps: every kernel is timed with HIP events on its launch stream (the per-kernel table and the
     # choice of the dominant kernel).  Timed region: only the dominant kernel keeps its two events per launch --
     # event records around all launches of a step cost ~0.1 ms of it (tools/prof_overhead.py).
@@ -714,6 +734,8 @@ def bench_track(args, sep, dev, world, rank, dist):
     prof = _lib.profile_read()          # the dominant kernel only, over the timed region
     _lib.profile_enable(False)
     _lib.profile_filter(None)
+    if args.dump_outputs and rank == 0:   # before the variants: they run the same separator again
+        dump_outputs(args.dump_outputs, out)
     nwarm = 1
     if prof_all is None:                # no warm-up step to take the table from
         prof_all, nwarm = prof, args.steps
@@ -744,7 +766,6 @@ def bench_track(args, sep, dev, world, rank, dist):
                     variants[name] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
     if rank != 0:
         return None
-    audio_s = world * args.steps * TRACK_SAMPLES / FS
     work = algorithmic_work(plan, 1, my_items, args.wiener)
     roofline = dominant_roofline(dom, prof, work, args.steps, dt, args.precision, args.wiener) if dom else None
     hbm, mfma = roofline_tables(work, prof_all, nwarm, args.wiener)
@@ -764,15 +785,8 @@ def bench_track(args, sep, dev, world, rank, dist):
             roofline["frac_by_executed_flops"] = round(executed * args.steps / roofline["launches"] / (roofline["avg_launch_ms"] * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)
     kernels = {k: {"ms_per_step": round(v[0] / nwarm, 4), "launches_per_step": v[1] / nwarm}
                for k, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0])}
-    result = {
-        "metric": METRIC,
-        "value": round(audio_s / dt, 2), "unit": "x real-time", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": DTYPES[args.precision], "data": "synthetic",
-        "config": {"workload": "BASELINE configs[%d]: offline model (Bark-262 sliCQT), one 240 s stereo track "
-                               "(10,584,000 samples, 5 chunks) per GPU, %s, seeded synthetic weights"
-                               % (2 if args.wiener else 1, "norbert Wiener-EM niter=1" if args.wiener else "Wiener off (mix-phase)"),
-                   "parallelism": "one track per rank, %d rank(s), no data-path collective" % world},
+    result = track_headline(args, world, dt)
+    result.update({
         "gpu_span_ms": split.get("gpu_span_ms"), "host_enqueue_ms": split.get("host_enqueue_ms"),
         "gpu_total_ms": split.get("gpu_total_ms"),
         "timing_note": "ms_per_step: wall clock over the K steps incl. the final synchronize; gpu_span_ms: HIP events around each step on "
@@ -787,12 +801,45 @@ def bench_track(args, sep, dev, world, rank, dist):
                                "(profiles/isa_budget.json, tools/isa_budget.py); frac_of_issue_bound = t_issue_bound / measured",
         "kernels_source": "last warm-up step: all kernels instrumented and the tail pass serialised behind the stacked pass (clean per-kernel times; their sum exceeds ms_per_step, whose timed region overlaps the two passes and instruments the roofline kernel only)",
         "kernels": kernels,
-    }
+    })
     if variants:
         result["variants"] = variants
     if world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(min(16, os.cpu_count() or 1), full=not args.cpu_baseline_clip)
     return result
+
+
+def track_headline(args, world, dt):
+    """The fields of a track240 line that a plain run prints (dt: seconds of the `args.steps` timed steps)."""
+    audio_s = world * args.steps * TRACK_SAMPLES / FS
+    return {
+        "metric": METRIC,
+        "value": round(audio_s / dt, 2), "unit": "x real-time", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": DTYPES[args.precision], "data": "synthetic",
+        "config": {"workload": "BASELINE configs[%d]: offline model (Bark-262 sliCQT), one 240 s stereo track "
+                               "(10,584,000 samples, 5 chunks) per GPU, %s, seeded synthetic weights"
+                               % (2 if args.wiener else 1, "norbert Wiener-EM niter=1" if args.wiener else "Wiener off (mix-phase)"),
+                   "parallelism": "one track per rank, %d rank(s), no data-path collective" % world},
+    }
+
+
+DUMP_SAMPLES, DUMP_SEED = 1 << 22, 20261016
+
+
+def dump_outputs(path, stems):
+    """--dump-outputs: what a caller of the timed path receives, the (4, 1, 2, N) fp32 stems of the last timed step, as a fixed
+    seeded sample (the whole tensor is 339 MB): one position drawn from each of 2^22 equal strata of the flattened tensor, the
+    same positions in every run.  Written as DIR/stems_sample.npy (float32, 16 MiB)."""
+    import numpy as np
+    import torch
+    flat = stems.reshape(-1)
+    k = min(DUMP_SAMPLES, flat.numel())
+    stride = flat.numel() // k
+    idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, k)
+    sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stems_sample.npy"), sample)
 
 
 def _timed_loop(fn, steps):

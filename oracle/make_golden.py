@@ -22,6 +22,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from oracle import golden
 from xumx_slicq_amd.synth import synth_audio
 from xumx_slicq_amd.weights import seeded_state_dict
 
@@ -124,7 +125,7 @@ def main():
                 d[f"mask_{'causal' if name == 'realtime' else 'offline'}_{i}"] = masks[i].numpy()
             d[f"mask_sums_{'causal' if name == 'realtime' else 'offline'}"] = np.stack(
                 [checksums(m) for m in masks])
-    np.savez_compressed(os.path.join(OUT, "cdae_masks_70000.npz"), **d)
+    golden.save(os.path.join(OUT, "cdae_masks_70000.npz"), **d)
 
     # ---- (5) blockwise_wiener ----------------------------------------------
     rng = np.random.default_rng(5)
@@ -157,7 +158,7 @@ def main():
             d[f"{name}_sums"] = np.stack([checksums(est[t]) for t in range(4)])
             d[f"{name}"] = est.numpy() if n == 9031 else est[..., ::7].contiguous().numpy()
         d["chunk_size"] = 2621440 if n < 50000 else 60000
-        np.savez_compressed(os.path.join(OUT, f"stems_{n}.npz"), **d)
+        golden.save(os.path.join(OUT, f"stems_{n}.npz"), **d)
 
     # ---- (7) validation half of one training.loop step (training.py:66-103, train=False, SDR term off):
     #      B = 2 clips of 2 s, mix = sum of four seeded sources, offline model in eval mode
@@ -210,7 +211,7 @@ def main():
         d[f"{tag}_running_mean::sliced_umx.1.cdaes.0.4"] = rm["sliced_umx.1.cdaes.0.4.running_mean"].numpy()
         d[f"{tag}_running_var::sliced_umx.1.cdaes.0.4"] = rm["sliced_umx.1.cdaes.0.4.running_var"].numpy()
         print("training step", tag, "mse", float(mse), "mask", float(msk))
-    np.savez_compressed(os.path.join(OUT, "training_step.npz"), **d)
+    golden.save(os.path.join(OUT, "training_step.npz"), **d)
 
     # ---- (9) dataset statistics: the reference's training.get_statistics on three seeded "tracks"
     # training.py pulls in packages that are absent offline; none of them is touched by get_statistics
@@ -277,7 +278,7 @@ def main():
              inv=y.numpy())
     for i, cb in enumerate(C):
         d[f"fwd_{i}"] = cb.numpy()
-    np.savez_compressed(os.path.join(OUT, "mel32_32768.npz"), **d)
+    golden.save(os.path.join(OUT, "mel32_32768.npz"), **d)
 
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

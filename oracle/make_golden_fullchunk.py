@@ -24,6 +24,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from oracle import golden
 from oracle.make_golden import WEIGHT_SEED, checksums
 from xumx_slicq_amd.synth import synth_audio
 from xumx_slicq_amd.weights import seeded_state_dict
@@ -70,8 +71,8 @@ def main():
         print(name, d[f"{name}_sums"])
         del est, sep, m
     path = os.path.join(OUT, "stems_fullchunk.npz")
-    np.savez_compressed(path, **d)
-    print(path, os.path.getsize(path))
+    for p in golden.save(path, **d):
+        print(p, os.path.getsize(p))
 
 
 if __name__ == "__main__":

@@ -25,6 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from oracle import golden
 from oracle.make_golden import WEIGHT_SEED, checksums
 from xumx_slicq_amd.weights import seeded_state_dict
 
@@ -86,8 +87,8 @@ def main():
             d[tag] = est[..., ::13].contiguous().numpy()
             print(tag, d[f"{tag}_sums"][:, 2])
     path = os.path.join(OUT, "stems_gspi.npz")
-    np.savez_compressed(path, **d)
-    print(path, os.path.getsize(path))
+    for p in golden.save(path, **d):
+        print(p, os.path.getsize(p))
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+from oracle import golden
 from xumx_slicq_amd.synth import synth_audio
 from xumx_slicq_amd.weights import seeded_state_dict
 
@@ -117,8 +118,8 @@ def main():
         d[f"{tag}_bn_min_abs"] = np.array([minima[k] for k in sorted(minima)])
         d[f"{tag}_risk_groups"] = np.array(risk_groups(minima) or [""])
         print("training step B", tag, "mse", mse, "mask", msk, "risk groups", risk_groups(minima))
-    np.savez_compressed(os.path.join(OUT, "training_step_b.npz"), **d)
-    print("training_step_b.npz", os.path.getsize(os.path.join(OUT, "training_step_b.npz")))
+    for p in golden.save(os.path.join(OUT, "training_step_b.npz"), **d):
+        print(p, os.path.getsize(p))
 
 
 if __name__ == "__main__":

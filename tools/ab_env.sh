@@ -4,7 +4,7 @@ O=$1; shift
 mkdir -p $O
 for spec in "$@"; do
   name=${spec%%=*}; envs=${spec#*=}
-  env $envs python bench.py --steps 20 --warmup 3 --no-variants --no-cpu-baseline > $O/$name.json 2> $O/$name.err
+  env $envs python bench.py --full --steps 20 --warmup 3 --no-variants --no-cpu-baseline > $O/$name.json 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ O=$1; P=$2; shift; shift
 for spec in "$@"; do
   name=${spec%%=*}; flags=${spec#*=}
   make -s -C $R/xumx_slicq_amd/csrc -j16 OBJDIR=/tmp/ab_$name OUT=/tmp/libab_$name.so "EXTRA=$flags" 2>/dev/null >/dev/null
-  XSQ_LIB=/tmp/libab_$name.so python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-variants 2>/tmp/ab_err.txt > /tmp/ab_out.json || tail -3 /tmp/ab_err.txt
+  XSQ_LIB=/tmp/libab_$name.so python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-variants 2>/tmp/ab_err.txt > /tmp/ab_out.json || tail -3 /tmp/ab_err.txt
   python3 -c "
 import json, re
 d=json.loads(open('/tmp/ab_out.json').read().strip().splitlines()[-1]); k=d['kernels']

@@ -7,7 +7,7 @@ for v in ${VARIANTS:-0 1 2 4 6 8 14 15}; do
   # same flags as the product library (csrc/Makefile), plus the ablation switch; objects outside the tree
   make -s -j4 OBJDIR=/tmp/ab_$v OUT=/tmp/libab_$v.so EXTRA=-D${FLAG:-XSQ_ABLATE}=$v 2>/dev/null
   echo "== ablate=$v"
-  XSQ_LIB=/tmp/libab_$v.so python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/tmp/ab_err.txt > /tmp/ab_out.json || tail -5 /tmp/ab_err.txt
+  XSQ_LIB=/tmp/libab_$v.so python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline 2>/tmp/ab_err.txt > /tmp/ab_out.json || tail -5 /tmp/ab_err.txt
   python3 -c "
 import json
 d=json.loads(open('/tmp/ab_out.json').read().strip().splitlines()[-1]); k=d['kernels']

@@ -16,6 +16,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "xumx_slicq_amd", "csrc")
@@ -45,7 +46,7 @@ def mfma_cycles(op):
 
 
 def compile_asm(src, out):
-    flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-Xclang", "-target-feature", "-Xclang",
+    flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-Xclang", "-target-feature", "-Xclang",
              "-packed-fp32-ops", "-S", "--cuda-device-only"]
     subprocess.run([HIPCC] + flags + [os.path.join(CSRC, src), "-o", out], check=True, capture_output=True, timeout=1800)
 
@@ -114,15 +115,12 @@ template __global__ void l4f_body_probe<4>(CdaeArgs, const L4fTileDev*, int);
 """
 
 
-def l4f_bodies():
-    """{"cdae_l4f<NCB>": budget} from a probe translation unit (see L4F_PROBE)."""
-    src = os.path.join(CSRC, "_isa_budget_l4f_probe.hip")
+def l4f_bodies(tmp):
+    """{"cdae_l4f<NCB>": budget} from a probe translation unit (see L4F_PROBE), compiled in the directory `tmp`."""
+    src = os.path.join(tmp, "isa_budget_l4f_probe.hip")
     open(src, "w").write(L4F_PROBE)
-    try:
-        compile_asm("_isa_budget_l4f_probe.hip", "/tmp/isa_budget_l4f.s")
-    finally:
-        os.remove(src)
-    funcs = parse("/tmp/isa_budget_l4f.s")
+    compile_asm(src, os.path.join(tmp, "isa_budget_l4f.s"))
+    funcs = parse(os.path.join(tmp, "isa_budget_l4f.s"))
     names = subprocess.run(["c++filt"], input="\n".join(funcs), capture_output=True, text=True).stdout.split("\n")
     out = {}
     for mangled, dem in zip(funcs, names):
@@ -139,10 +137,15 @@ def l4f_bodies():
 
 
 def main():
+    with tempfile.TemporaryDirectory(prefix="isa_budget_") as tmp:
+        budget(tmp)
+
+
+def budget(tmp):
     out = {"what": "MFMA cycles and other vector instructions (4 issue cycles each) per loop trip and outside the MFMA loops, per wave; "
                    "tools/isa_budget.py from the gfx950 assembly of csrc/cdae.hip and csrc/slicqt.hip", "kernels": {}}
     for src in ("cdae.hip", "slicqt.hip"):
-        asm = "/tmp/isa_budget_%s.s" % src.split(".")[0]
+        asm = os.path.join(tmp, "isa_budget_%s.s" % src.split(".")[0])
         compile_asm(src, asm)
         funcs = parse(asm)
         names = subprocess.run(["c++filt"], input="\n".join(funcs), capture_output=True, text=True).stdout.split("\n")
@@ -155,7 +158,7 @@ def main():
                     extra = sum(v["valu"] for v in d["loops"].values() if not v["nmfma"])
                     outside = dict(d["outside"], valu=d["outside"]["valu"] + extra)
                     out["kernels"][key] = {"symbol": dem.split("(")[0], "outside": outside, "loops": sorted(loops, key=lambda v: v["mfma_cycles"])}
-    out["kernels"].update(l4f_bodies())
+    out["kernels"].update(l4f_bodies(tmp))
     missing = [k for k in list(WANT) + ["cdae_l4f<%d>" % i for i in (1, 2, 3, 4)] if k not in out["kernels"]]
     if missing:
         sys.exit("isa_budget: kernels not found in the assembly: %s" % missing)

@@ -6,7 +6,7 @@ O=$1; shift
 for spec in "$@"; do
   name=${spec%%=*}; flags=${spec#*=}
   make -s -C $R/xumx_slicq_amd/csrc -j16 OBJDIR=/tmp/wn_$name OUT=/tmp/libwn_$name.so "EXTRA=$flags" 2>/dev/null >/dev/null
-  XSQ_LIB=/tmp/libwn_$name.so python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-variants 2>/tmp/wn_err.txt > /tmp/wn_out.json || tail -3 /tmp/wn_err.txt
+  XSQ_LIB=/tmp/libwn_$name.so python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-variants 2>/tmp/wn_err.txt > /tmp/wn_out.json || tail -3 /tmp/wn_err.txt
   python3 -c "
 import json
 d=json.loads(open('/tmp/wn_out.json').read().strip().splitlines()[-1]); k=d['kernels']
