@@ -247,6 +247,20 @@ int xsq_wiener_em(int nblocks, const int32_t* F, const int32_t* T, const float* 
  * max_len = the largest row length (sizes the grid).  Rows must not overlap in dst.                     */
 int xsq_place_rows(const float* src, float* dst, const int64_t* table, int nrows, int64_t max_len, void* stream);
 
+/* ---- sample-rate conversion of the front end ---------------------------------------------------------------------
+ * Replaces torchaudio.transforms.Resample(orig, new, "sinc_interpolation") of data.py:148-156 (preprocess_audio): Hann
+ * window, the polyphase filter torchaudio applies as conv1d(x_pad, K, stride o) with o = orig / g, n = new / g,
+ * g = gcd(orig, new).  The host (xumx_slicq_amd/resample.py) builds K and keeps only each phase's non-zero taps:
+ *   table      DEVICE fp32 [n][span]: K[p][first_tap[p] + i], i < span (zeros past a phase's last non-zero tap)
+ *   first_tap  DEVICE int32 [n]: index k of table[p][0] in K's 2*width + o taps
+ * and row r of y (rows rows, y + r * y_stride) becomes
+ *   y[j*n + p] = sum_{i < span} table[p][i] * x[j*o + first_tap[p] - width + i],   j*n + p < len_out
+ * summed in that order, where x (x + r * x_stride, len_in samples) reads as 0 outside [0, len_in) -- torchaudio's
+ * padding, never written out.  len_out: ceil(fp32(n * len_in / o)), as torchaudio.  All offsets must fit 32 bits.
+ * No allocation, no synchronisation: capturable into a graph.                                                     */
+int xsq_resample(const float* x, int64_t x_stride, int rows, int64_t len_in, float* y, int64_t y_stride, int64_t len_out,
+                 const float* table, const int32_t* first_tap, int o, int n, int span, int width, void* stream);
+
 /* ---- in-place exchange of stems between the ranks of the sharded path (RCCL over xGMI) -------------------------------
  * The form of "the final waveform concat" (separator.py:229-231 across ranks) that needs no packing buffer and no
  * placement pass: every rank holds the SAME flat per-track layout, its kernels write the rows it owns in place

@@ -87,6 +87,7 @@ _SIGS = {
     "xsq_train_step_count": (C.c_int64, [_vp, C.c_int64]),
     "xsq_train_set_precision": (C.c_int, [_vp, C.c_int]),
     "xsq_place_rows": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp]),
+    "xsq_resample": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "xsq_wiener_num_windows": (C.c_int64, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "xsq_wiener_window_max": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "xsq_wiener_em_masked_ext": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),

@@ -149,7 +149,9 @@ def preprocess_audio(audio: torch.Tensor, rate: Optional[float] = None,
                      model_rate: Optional[float] = None) -> torch.Tensor:
     """data.py:98-156: any of (T,), (C,T), (T,C), (B,C,T) -> (nb_samples, 2, T).
     Mono is duplicated, more than two channels are cut to the first two (the reference
-    means to warn there but never imports ``warnings``)."""
+    means to warn there but never imports ``warnings``).  Audio on the GPU at another rate is resampled
+    to ``model_rate`` there (xumx_slicq_amd.resample, torchaudio's sinc / Hann filter); on the CPU it is refused, as the
+    resampler has no CPU path."""
     if audio.dim() == 1:
         audio = audio[None, None, ...]
     elif audio.dim() == 2:
@@ -162,6 +164,10 @@ def preprocess_audio(audio: torch.Tensor, rate: Optional[float] = None,
     if audio.shape[1] == 1:
         audio = torch.repeat_interleave(audio, 2, dim=1)
     if rate is not None and model_rate is not None and float(rate) != float(model_rate):
-        raise ValueError(f"input is {rate} Hz, the model {float(model_rate)} Hz: resample first "
-                         "(the reference uses torchaudio's sinc resampler, not available offline)")
+        if audio.device.type != "cuda":
+            raise ValueError(f"input is {rate} Hz, the model {float(model_rate)} Hz: the resampler runs on the GPU only, "
+                             "move the audio to the device first")
+        from .resample import Resample
+        warnings.warn("resample to model sample rate")
+        audio = Resample(rate, model_rate, resampling_method="sinc_interpolation")(audio)
     return audio

@@ -5,11 +5,13 @@ from __future__ import annotations
 
 import argparse
 import time
+import warnings
 from pathlib import Path
 
 import torch
 
 from . import audio as xaudio
+from .resample import Resample
 from .separator import Separator, seeded_separator
 
 
@@ -62,16 +64,19 @@ _POOLS: dict = {}        # process-wide pinned staging pools of demix_directory
 
 def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, writers: int = 4, depth: int = 3, quiet=False):
     """The CLI's loop (inference.py:118-146) as a pipeline over the tracks: decode -> pinned host buffer (reader threads) |
-    H2D on a copy stream | ``separator(audio)`` | channel interleave on the GPU (the wav payload layout, so the host never
+    H2D on a copy stream | resampling to the model's rate on the GPU where the file's rate differs (preprocess_audio,
+    data.py:148-156) | ``separator(audio)`` | channel interleave on the GPU (the wav payload layout, so the host never
     transposes 339 MB per track) | D2H into a pinned buffer on a second copy stream | header + payload written by writer
     threads.  At ~5 ms of GPU time per 240 s track the loop is bound by PCIe and file I/O; the stages of consecutive
-    tracks overlap.  Returns [(name, audio seconds, separator milliseconds by HIP events)] in input order."""
+    tracks overlap.  Stems are written at ``separator.sample_rate`` (inference.py:135-142).  Returns [(name, audio seconds,
+    separator milliseconds by HIP events)] in input order."""
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
 
     dev = torch.device(device)
     out_dir = Path(out_dir)
+    model_rate = int(float(separator.sample_rate))
     # the staging buffers outlive the call (page-locking a 339 MB block costs more than demixing the track it carries)
     pool_in, pool_out = _POOLS.setdefault("in", _PinnedPool()), _POOLS.setdefault("out", _PinnedPool())
     copy_in, copy_out = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
@@ -86,8 +91,6 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
             keep.append(pool_in.take(numel, depth + readers))
             return keep[0]
         view, rate = xaudio.load_audio_into(str(path), take)        # (2, N) float32 in the pinned buffer, decoded in one pass
-        if float(rate) != float(separator.sample_rate):
-            raise ValueError(f"{path}: {rate} Hz, the model runs at {float(separator.sample_rate)} Hz: resample first")
         return path, view, keep[0], rate
 
     lock = threading.Lock()
@@ -104,7 +107,7 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 done.synchronize()
                 target_dir = out_dir / path.stem
                 target_dir.mkdir(parents=True, exist_ok=True)
-                xaudio.save_wav_float_interleaved(str(target_dir / f"{separator.sources[k]}.wav"), host[k], rate)
+                xaudio.save_wav_float_interleaved(str(target_dir / f"{separator.sources[k]}.wav"), host[k], model_rate)
             except Exception as e:                                   # noqa: BLE001 -- reported after the loop
                 errors.append((str(path), e))
             finally:
@@ -129,12 +132,15 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 up = torch.cuda.Event()
                 up.record(copy_in)
             main.wait_event(up)
+            x.record_stream(main)
+            if rate != model_rate:                                   # (1, 2, N'), on the main stream, outside the timed region
+                warnings.warn("resample to model sample rate")
+                x = Resample(rate, model_rate, resampling_method="sinc_interpolation")(x)
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record(main)
-            est = separator(x)                                       # (4, 1, 2, N)
+            est = separator(x)                                       # (4, 1, 2, N')
             t1.record(main)
-            inter = est[:, 0].transpose(1, 2).contiguous()           # (4, N, 2): the wav payload of each target
-            x.record_stream(main)
+            inter = est[:, 0].transpose(1, 2).contiguous()           # (4, N', 2): the wav payload of each target
             ready = torch.cuda.Event()
             ready.record(main)
             buf_out = pool_out.take(inter.numel(), depth + writers)
@@ -198,7 +204,7 @@ def inference_main(argv=None):
         target_dir = out_dir / wav.stem
         target_dir.mkdir(parents=True, exist_ok=True)
         for target, est in estimates.items():
-            xaudio.save_wav_float(str(target_dir / f"{target}.wav"), est[0], rate)
+            xaudio.save_wav_float(str(target_dir / f"{target}.wav"), est[0], int(float(separator.sample_rate)))
         print(f"{wav.name}: {sig.shape[-1] / rate:.1f} s demixed in {dt * 1e3:.1f} ms")
     if n:
         print(f"xumx-sliCQ-V2 inference time: {tot / n:.4f} s/track over {n} track(s)")
