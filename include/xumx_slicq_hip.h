@@ -150,6 +150,23 @@ int xsq_slicqt_inverse_rows(xsq_plan* plan, const float* coef, int BC, int S, in
 int xsq_slicqt_inverse_masked(xsq_plan* plan, const float* masks, const float* mix, int BC, int BCx,
                               int S, int64_t length, float* y, const int64_t* row_offsets,
                               void* workspace, size_t workspace_bytes, void* stream);
+/*   R gain-weighted mixes of the four targets through R inverse transforms instead of four plus a sum: the
+ *   slider mix of demixui.py:94-114 (sum_t level_t * stem_t), remix_signal of cadenza/enhance.py:270-290 and the
+ *   target groups of separator.py:235-259 (to_dict with aggregate_dict).  The inverse is linear, so
+ *     mix-phase:  sum_t g_t iSliCQT(m_t * X) = iSliCQT((sum_t g_t m_t) * X)
+ *     Wiener-EM:  sum_t g_t iSliCQT(Y_t)     = iSliCQT(sum_t g_t Y_t)
+ *   A combine kernel forms the weighted masks (real) or estimates (complex) of the R mixes, t = 0..3 in this order with
+ *   the products rounded before the sum (a one-hot row reproduces its target bit for bit), skipping every target no row
+ *   weights; then xsq_slicqt_inverse_masked / xsq_slicqt_inverse_rows runs on R * 2B channels.
+ *   Mix-phase: masks = REAL arena of 8B channels (target, item, c), mix = complex arena of 2B channels, Y = NULL.
+ *   Wiener-EM: Y = complex arena of 8B channels, masks = mix = NULL.  gains: HOST float[R * 4], row-major, targets in
+ *   Separator.sources order (bass, vocals, other, drums), finite; 1 <= R <= 4.  Output channel (r, item, c) -> y +
+ *   row_offsets[r * 2B + 2 item + c] (row_offsets: DEVICE int64[R * 2B], NULL: contiguous rows of `length`).
+ *   workspace: xsq_slicqt_remix_workspace bytes (wiener = Y != NULL).                                                  */
+size_t xsq_slicqt_remix_workspace(xsq_plan* plan, int R, int B, int S, int wiener);      /* 0 on error */
+int xsq_slicqt_inverse_remix(xsq_plan* plan, const float* masks, const float* mix, const float* Y, const float* gains,
+                             int R, int B, int S, int64_t length, float* y, const int64_t* row_offsets,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- CDAE model ----------------------------------------------------------------
  * Replaces Unmix.forward (model.py:69-82) -> _SlicedUnmixCDAE.forward (model.py:213-271)
@@ -416,6 +433,18 @@ int xsq_separator_forward_indirect(xsq_demixer* d, xsq_model* model, const float
                                    int64_t chunk_size, int max_stack, int wiener, int overlap_tail, float* out,
                                    void* workspace, size_t workspace_bytes, void* tail_workspace,
                                    size_t tail_workspace_bytes, void* stream, void* tail_stream);
+/* xsq_separator_forward whose result is R gain-weighted mixes of the four stems instead of the stems: out (R, nb, 2, N),
+ * out[r] = sum_t gains[4 r + t] * stem_t with the targets in Separator.sources order (bass, vocals, other, drums) --
+ * the slider mix of demixui.py:94-114, remix_signal of cadenza/enhance.py:270-290 and the target groups of
+ * separator.py:235-259 (to_dict with aggregate_dict), through R inverse transforms per chunk instead of four
+ * (xsq_slicqt_inverse_remix).  Same schedule as xsq_separator_forward: stacked full chunks, the tail chunk on
+ * tail_stream, split batches with the shared Wiener window-maximum table, the sllen/2 + 1 padding.  gains: HOST
+ * float[R * 4], finite, 1 <= R <= 4.  The workspaces xsq_separator_workspace returns for the call shape are enough for
+ * every R <= 4; the call reads the demixer's cached row tables and changes none of them.                            */
+int xsq_separator_remix(xsq_demixer* d, xsq_model* model, const float* audio, int nb, int64_t N, int64_t chunk_size,
+                        int max_stack, int wiener, int overlap_tail, float* out, void* workspace, size_t workspace_bytes,
+                        void* tail_workspace, size_t tail_workspace_bytes, void* stream, void* tail_stream,
+                        const float* gains, int R);
 /* The schedule xsq_separator_forward follows for a call shape, as pure host arithmetic (no device needed): pass i ->
  * passes[8 i ..] = (first sample of its first chunk, samples per chunk, chunks stacked, first sample index of the batch,
  * samples of the batch in this pass, 1 = may run on the tail stream, index of the first pass of its set, 1 = the set

@@ -62,6 +62,8 @@ _SIGS = {
     "xsq_slicqt_inverse": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
     "xsq_slicqt_inverse_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xsq_slicqt_inverse_masked": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_slicqt_remix_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xsq_slicqt_inverse_remix": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xsq_model_num_params": (C.c_int64, [C.c_int, _vp, _vp]),
     "xsq_model_create": (C.c_int, [C.POINTER(_vp), C.c_int, _vp, _vp, C.c_int, _vp, C.c_int64]),
     "xsq_model_destroy": (C.c_int, [_vp]),
@@ -100,6 +102,7 @@ _SIGS = {
     "xsq_separator_workspace": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "xsq_separator_forward": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "xsq_separator_forward_indirect": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "xsq_separator_remix": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int]),
     "xsq_comm_load": (C.c_int, [C.c_char_p]),
     "xsq_comm_version": (C.c_int, []),
     "xsq_comm_unique_id": (C.c_int, [_vp]),

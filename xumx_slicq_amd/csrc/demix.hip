@@ -3,6 +3,7 @@
 // side stream beside them -- through row-offset tables cached per call shape.  No kernels of its own: it sequences
 // the entry points of slicqt.hip / cdae.hip / wiener.hip (include/xumx_slicq_hip.h, "the whole call").
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -102,9 +103,25 @@ static int pass_layout(xsq_demixer* d, const xsq_model* Mo, int B, int64_t n_pad
     return XSQ_OK;
 }
 
+// The remix tail of a pass (xsq_separator_remix): the mixes two at a time through xsq_slicqt_inverse_remix, in the space
+// behind the inverse transform's own workspace -- free once the CDAE and the EM iterations are done.  Two mixes need at
+// most the weighted arena of 4B channels plus the inverse workspace of 4B rows, which fits where the forward call's
+// inverse of 8B rows runs: the forward call's workspace serves every R <= 4.  Output channel (r, item, c) is row
+// (target = r, item, c) of the forward call's table.
+static int run_remix(xsq_plan* P, const float* masks, const float* X, const float* Y, const float* gains, int R, int B, int S,
+                     int64_t n, float* out, const int64_t* out_rows, void* ws, size_t ws_bytes, hipStream_t stream) {
+    for (int r0 = 0; r0 < R; r0 += 2) {
+        const int g = std::min(2, R - r0);
+        if (int rc = xsq_slicqt_inverse_remix(P, masks, X, Y, gains + 4 * r0, g, B, S, n, out, out_rows + (size_t)r0 * 2 * B, ws,
+                                              ws_bytes, stream))
+            return rc;
+    }
+    return XSQ_OK;
+}
+
 static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* const* x_slot, const int64_t* x_rows, int B, int64_t n, int64_t n_pad,
                     int group, int wiener, float* out, const int64_t* out_rows, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const float* ext_max = nullptr) {
+                    const float* ext_max = nullptr, const float* gains = nullptr, int R = 0) {
     xsq_plan* P = d->plan;
     PassLayout L;
     int rc = pass_layout(d, Mo, B, n_pad, wiener, &L);
@@ -126,12 +143,14 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
     if ((rc = xsq_slicqt_forward_rows_indirect(P, x, x_slot, x_rows, 2 * B, n, n_pad, X, xin, mean, scale, split, w + L.fwd, L.fwd_bytes, stream)))
         return rc;
     if ((rc = xsq_cdae_forward_xin(Mo, X, B, S, nullptr, masks, w + L.cdae, L.cdae_bytes, stream, 1))) return rc;
-    if (!wiener)
+    if (!wiener && !gains)
         return xsq_slicqt_inverse_masked(P, masks, X, 8 * B, 2 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
-    if ((rc = xsq_wiener_em_masked_ext(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max, w + L.wien,
-                                       L.wien_bytes, stream)))
+    if (wiener && (rc = xsq_wiener_em_masked_ext(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
+                                                 w + L.wien, L.wien_bytes, stream)))
         return rc;
-    return xsq_slicqt_inverse_rows(P, Y, 8 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
+    if (!gains) return xsq_slicqt_inverse_rows(P, Y, 8 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
+    return run_remix(P, wiener ? nullptr : masks, wiener ? nullptr : X, wiener ? Y : nullptr, gains, R, B, S, n, out, out_rows,
+                     w + L.inv, L.total - L.inv, stream);
 }
 
 // One pass of a split batch, first half: its mix transform and the window maxima of its samples folded into the set's table.
@@ -382,7 +401,7 @@ int xsq_separator_workspace(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
 
 static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* audio, const float* const* x_slot, int nb, int64_t N, int64_t cs,
                                   int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_);
+                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_, const float* gains = nullptr, int R = 0);
 
 int xsq_separator_forward(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack,
                           int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
@@ -402,7 +421,7 @@ int xsq_separator_forward_indirect(xsq_demixer* d, xsq_model* Mo, const float* c
 
 static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* audio, const float* const* x_slot, int nb, int64_t N, int64_t cs,
                                   int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_) {
+                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_, const float* gains, int R) {
     XSQ_REQUIRE(d && Mo && (audio || x_slot) && out && ws, "xsq_separator_forward: null argument");
     XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "xsq_separator_forward: nb=%d N=%lld chunk_size=%lld max_stack=%d",
                 nb, (long long)N, (long long)cs, max_stack);
@@ -439,7 +458,8 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
         XSQ_HIP(hipStreamWaitEvent(side, d->ev_fork, 0));
         forked = true;
         for (const PassPlan& p : fp->passes)
-            if (p.tail && (rc = run_pass(d, Mo, audio, x_slot, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, out, p.d_orows, tail_ws, tail_ws_bytes, side)))
+            if (p.tail && (rc = run_pass(d, Mo, audio, x_slot, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, out, p.d_orows, tail_ws, tail_ws_bytes, side,
+                                         nullptr, gains, R)))
                 break;
         if (rc) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return rc; }
     }
@@ -460,10 +480,20 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
                 rc = run_prepass(d, Mo, audio, x_slot, fp->passes[i + j], pws, pws_bytes, ext, main);
         if (rc == XSQ_OK)
             rc = run_pass(d, Mo, audio, x_slot, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, out, p.d_orows, pws, pws_bytes, main,
-                          p.ext_off >= 0 ? ext + p.ext_off : nullptr);
+                          p.ext_off >= 0 ? ext + p.ext_off : nullptr, gains, R);
     }
     if (rc) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return rc; }
     return join();
+}
+
+int xsq_separator_remix(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
+                        int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws, size_t tail_ws_bytes, void* stream_,
+                        void* tail_stream_, const float* gains, int R) {
+    XSQ_REQUIRE(audio && gains, "xsq_separator_remix: null argument");
+    XSQ_REQUIRE(R >= 1 && R <= 4, "xsq_separator_remix: R=%d mixes (1..4)", R);
+    for (int i = 0; i < 4 * R; ++i) XSQ_REQUIRE(std::isfinite(gains[i]), "xsq_separator_remix: gain [%d][%d] is not finite", i / 4, i % 4);
+    return separator_forward_impl(d, Mo, audio, nullptr, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws, tail_ws_bytes,
+                                  stream_, tail_stream_, gains, R);
 }
 
 }  // extern "C"

@@ -241,6 +241,49 @@ struct BandInvOp {
     }
 };
 
+// Gain-weighted sums of the four targets (xsq_slicqt_inverse_remix): dst channel (r, ch) = sum_t g[r][t] * src channel
+// (t, ch), element by element, t = 0..3 in this fixed order.  Arena layout (any channel count C): band block j holds
+// [C][S * F_j * T_j] coefficients from C * S * cum_j on -- so the element e of channel ch in block j sits at the same e
+// in both arenas, only the block bases and channel strides differ.  src has 4 * nch channels, dst R * nch.  Masks are
+// real (cplx = 1), estimates complex (cplx = 2).  A target no row weights (use[t] == 0) is not loaded: a uniform branch
+// on a kernel argument.  Products are rounded before the sum (contraction off): a one-hot row copies its target's bits.
+constexpr int REMIX_MAX_BLOCKS = 256;      // (Bark-262: 70 blocks; the arguments stay near 1.1 KB)
+struct RemixArgs {
+    const float* src;
+    float* dst;
+    int nch, R, S, cplx;
+    float g[4][4];
+    int use[4];
+    int cum[REMIX_MAX_BLOCKS + 1];      // coefficients per channel-slice before block j (cum[nblocks] = sumFT)
+};
+
+__global__ __launch_bounds__(256) void k_remix_combine(RemixArgs a) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.y, ch = blockIdx.z;
+    const int64_t per = (int64_t)a.S * (a.cum[j + 1] - a.cum[j]) * a.cplx;     // floats of one channel in block j (% 4 == 0: T % 4 == 0)
+    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e >= per) return;
+    const int64_t base = (int64_t)a.S * a.cum[j] * a.cplx;                    // floats of one channel before block j
+    const float* s = a.src + base * (4 * a.nch) + (int64_t)ch * per + e;
+    float4 m[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        m[t] = a.use[t] ? *reinterpret_cast<const float4*>(s + (int64_t)t * a.nch * per) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* d = a.dst + base * ((int64_t)a.R * a.nch) + (int64_t)ch * per + e;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (r >= a.R) break;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (!a.use[t]) continue;
+            const float g = a.g[r][t];
+            acc.x = acc.x + g * m[t].x; acc.y = acc.y + g * m[t].y; acc.z = acc.z + g * m[t].z; acc.w = acc.w + g * m[t].w;
+        }
+        *reinterpret_cast<float4*>(d + (int64_t)r * a.nch * per) = acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -1085,6 +1128,56 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
                        row_offsets, S, length, P->L, P->h); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
+}
+
+// ---- remix: R gain-weighted mixes of the four targets through R (not four) inverse transforms ----
+static int remix_gains_ok(const float* gains, int R, const char* who) {
+    XSQ_REQUIRE(gains, "%s: null gains", who);
+    XSQ_REQUIRE(R >= 1 && R <= 4, "%s: R=%d mixes (1..4)", who, R);
+    for (int i = 0; i < 4 * R; ++i) XSQ_REQUIRE(std::isfinite(gains[i]), "%s: gain [%d][%d] is not finite", who, i / 4, i % 4);
+    return XSQ_OK;
+}
+
+size_t xsq_slicqt_remix_workspace(xsq_plan* P, int R, int B, int S, int wiener) {
+    if (!P || R < 1 || R > 4 || B <= 0 || S <= 0) return 0;
+    const size_t inv = xsq_slicqt_inverse_workspace(P, R * 2 * B, S);
+    if (!inv) return 0;
+    return al((size_t)R * 2 * B * S * P->sumFT * (wiener ? 8 : 4)) + inv;
+}
+
+int xsq_slicqt_inverse_remix(xsq_plan* P, const float* masks, const float* mix, const float* Y, const float* gains, int R, int B,
+                             int S, int64_t length, float* y, const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_) {
+    if (int rc = remix_gains_ok(gains, R, "xsq_slicqt_inverse_remix")) return rc;
+    XSQ_REQUIRE(P && y && ws, "xsq_slicqt_inverse_remix: null argument");
+    XSQ_REQUIRE(Y ? (!masks && !mix) : (masks && mix), "xsq_slicqt_inverse_remix: pass masks and mix (mix-phase) or Y (Wiener-EM), not both");
+    XSQ_REQUIRE(B > 0 && S >= 2 && 2 * B <= 65535, "xsq_slicqt_inverse_remix: B=%d S=%d", B, S);
+    XSQ_REQUIRE(P->nblocks <= REMIX_MAX_BLOCKS, "xsq_slicqt_inverse_remix: %d band blocks (at most %d)", P->nblocks, REMIX_MAX_BLOCKS);
+    const int wiener = Y ? 1 : 0, BC = R * 2 * B;
+    const size_t need = xsq_slicqt_remix_workspace(P, R, B, S, wiener);
+    XSQ_REQUIRE(need && need <= ws_bytes, "xsq_slicqt_inverse_remix: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    const size_t comb_bytes = al((size_t)BC * S * P->sumFT * (wiener ? 8 : 4));
+    float* comb = (float*)ws;
+    RemixArgs a;
+    a.src = Y ? Y : masks; a.dst = comb; a.nch = 2 * B; a.R = R; a.S = S; a.cplx = wiener ? 2 : 1;
+    for (int t = 0; t < 4; ++t) a.use[t] = 0;
+    for (int r = 0; r < 4; ++r)
+        for (int t = 0; t < 4; ++t) {
+            a.g[r][t] = r < R ? gains[4 * r + t] : 0.f;
+            if (r < R && gains[4 * r + t] != 0.f) a.use[t] = 1;
+        }
+    int64_t per_max = 0;
+    for (int j = 0; j < P->nblocks; ++j) {
+        a.cum[j] = (int)P->blocks[j].cum;
+        per_max = std::max<int64_t>(per_max, (int64_t)S * P->blocks[j].F * P->blocks[j].T * a.cplx);
+    }
+    a.cum[P->nblocks] = (int)P->sumFT;
+    hipStream_t stream = (hipStream_t)stream_;
+    { XSQ_PROF("remix_combine", stream);
+    hipLaunchKernelGGL(k_remix_combine, dim3((unsigned)((per_max / 4 + 255) / 256), P->nblocks, 2 * B), dim3(256), 0, stream, a); }
+    XSQ_HIP(hipGetLastError());
+    char* inv_ws = (char*)ws + comb_bytes;
+    if (wiener) return inverse_impl(P, comb, nullptr, 0, BC, S, length, y, row_offsets, inv_ws, ws_bytes - comb_bytes, stream_);
+    return inverse_impl(P, mix, comb, 2 * B, BC, S, length, y, row_offsets, inv_ws, ws_bytes - comb_bytes, stream_);
 }
 
 }  // extern "C"

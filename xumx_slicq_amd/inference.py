@@ -12,7 +12,7 @@ import torch
 
 from . import audio as xaudio
 from .resample import Resample
-from .separator import Separator, seeded_separator
+from .separator import Separator, remix_gains, seeded_separator
 
 
 def separate(audio, separator, rate=None, device=None):
@@ -28,6 +28,43 @@ def separate(audio, separator, rate=None, device=None):
     torch.cuda.synchronize(audio.device)
     time_delta = time.time() - start_time
     return separator.to_dict(estimates), time_delta
+
+
+def parse_remix_spec(spec: str):
+    """``--remix NAME:SPEC`` -> (NAME, gain row in Separator.sources order).  SPEC is a comma-separated list of
+    target=gain; targets not named keep gain 1.0 (``karaoke:vocals=0``, ``instrumental:vocals=0,drums=0.5``).
+    ValueError for a missing or unusable NAME, an unknown target, a target named twice or a gain that is not a finite
+    number.  Host only."""
+    name, sep, body = spec.partition(":")
+    name = name.strip()
+    if not sep or not name or name in (".", "..") or any(c in name for c in "/\\\0"):
+        raise ValueError(f"--remix wants NAME:SPEC with a file name NAME, got {spec!r}")
+    gains = {}
+    for item in filter(None, (x.strip() for x in body.split(","))):
+        target, eq, value = item.partition("=")
+        target = target.strip()
+        if not eq:
+            raise ValueError(f"--remix {spec!r}: {item!r} is not target=gain")
+        if target in gains:
+            raise ValueError(f"--remix {spec!r}: target {target!r} named twice")
+        try:
+            gains[target] = float(value)
+        except ValueError:
+            raise ValueError(f"--remix {spec!r}: gain {value!r} of {target!r} is not a number") from None
+    return name, remix_gains(gains)[0].tolist()
+
+
+def parse_remix_specs(specs):
+    """The repeated ``--remix`` options -> (names, (R, 4) gains); None when there are none.  At most four, names unique."""
+    if not specs:
+        return None
+    if len(specs) > 4:
+        raise ValueError(f"at most four --remix mixes per run (got {len(specs)})")
+    parsed = [parse_remix_spec(s) for s in specs]
+    names = [n for n, _ in parsed]
+    if len(set(names)) != len(names):
+        raise ValueError(f"--remix names must be unique: {names}")
+    return names, remix_gains([row for _, row in parsed])
 
 
 class _PinnedPool:
@@ -62,20 +99,23 @@ class _PinnedPool:
 _POOLS: dict = {}        # process-wide pinned staging pools of demix_directory
 
 
-def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, writers: int = 4, depth: int = 3, quiet=False):
+def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, writers: int = 4, depth: int = 3, quiet=False,
+                    remix=None):
     """The CLI's loop (inference.py:118-146) as a pipeline over the tracks: decode -> pinned host buffer (reader threads) |
     H2D on a copy stream | resampling to the model's rate on the GPU where the file's rate differs (preprocess_audio,
     data.py:148-156) | ``separator(audio)`` | channel interleave on the GPU (the wav payload layout, so the host never
     transposes 339 MB per track) | D2H into a pinned buffer on a second copy stream | header + payload written by writer
     threads.  At ~5 ms of GPU time per 240 s track the loop is bound by PCIe and file I/O; the stages of consecutive
-    tracks overlap.  Stems are written at ``separator.sample_rate`` (inference.py:135-142).  Returns [(name, audio seconds,
-    separator milliseconds by HIP events)] in input order."""
+    tracks overlap.  Stems are written at ``separator.sample_rate`` (inference.py:135-142).  ``remix`` = (names, (R, 4)
+    gains) from ``parse_remix_specs``: ``separator.remix`` runs instead and writes <NAME>.wav per mix in place of the four
+    stems.  Returns [(name, audio seconds, separator milliseconds by HIP events)] in input order."""
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
 
     dev = torch.device(device)
     out_dir = Path(out_dir)
+    names = list(separator.sources) if remix is None else list(remix[0])
     model_rate = int(float(separator.sample_rate))
     # the staging buffers outlive the call (page-locking a 339 MB block costs more than demixing the track it carries)
     pool_in, pool_out = _POOLS.setdefault("in", _PinnedPool()), _POOLS.setdefault("out", _PinnedPool())
@@ -107,7 +147,7 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 done.synchronize()
                 target_dir = out_dir / path.stem
                 target_dir.mkdir(parents=True, exist_ok=True)
-                xaudio.save_wav_float_interleaved(str(target_dir / f"{separator.sources[k]}.wav"), host[k], model_rate)
+                xaudio.save_wav_float_interleaved(str(target_dir / f"{names[k]}.wav"), host[k], model_rate)
             except Exception as e:                                   # noqa: BLE001 -- reported after the loop
                 errors.append((str(path), e))
             finally:
@@ -138,7 +178,7 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 x = Resample(rate, model_rate, resampling_method="sinc_interpolation")(x)
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record(main)
-            est = separator(x)                                       # (4, 1, 2, N')
+            est = separator(x) if remix is None else separator.remix(x, remix[1])      # (4 | R, 1, 2, N')
             t1.record(main)
             inter = est[:, 0].transpose(1, 2).contiguous()           # (4, N', 2): the wav payload of each target
             ready = torch.cuda.Event()
@@ -153,8 +193,8 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 done.record(copy_out)
             up.synchronize()                                         # the input buffer may be refilled once its upload is over
             pool_in.give(buf_in)
-            left = [len(separator.sources)]
-            for k in range(len(separator.sources)):
+            left = [len(names)]
+            for k in range(len(names)):
                 wq.put((path, host, buf_out, done, t0, t1, rate, n, k, left))
     for _ in threads:
         wq.put(None)
@@ -169,6 +209,18 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
     return out
 
 
+def _remix_one(audio, separator, rate, device, remix):
+    """``separate`` with ``separator.remix``: ({name: (nb_samples, 2, T)}, seconds)."""
+    if device:
+        audio = audio.to(device)
+    audio = xaudio.preprocess_audio(audio, rate, separator.sample_rate)
+    torch.cuda.synchronize(audio.device)
+    start_time = time.time()
+    mixes = separator.remix(audio, remix[1])
+    torch.cuda.synchronize(audio.device)
+    return dict(zip(remix[0], mixes)), time.time() - start_time
+
+
 def inference_main(argv=None):
     p = argparse.ArgumentParser(description="xumx-sliCQ-V2 inference on MI355X (hip-rocm backend)")
     p.add_argument("--input-dir", type=str, default="/input")
@@ -180,7 +232,14 @@ def inference_main(argv=None):
     p.add_argument("--warmup", type=int, default=0)
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--serial", action="store_true", help="one track at a time, as the reference's loop (inference.py:118-146)")
+    p.add_argument("--remix", action="append", default=None, metavar="NAME:SPEC",
+                   help="write <NAME>.wav = sum of the stems with the gains of SPEC (target=gain,...; unnamed targets keep 1.0) "
+                        "instead of the four stems, e.g. karaoke:vocals=0; up to four times")
     args = p.parse_args(argv)
+    try:
+        remix = parse_remix_specs(args.remix)
+    except ValueError as e:
+        p.error(str(e))
     if args.model_path:
         separator = Separator.load(model_path=args.model_path, runtime_backend="hip-rocm",
                                    warmup=args.warmup, realtime=args.realtime, device=args.device)
@@ -190,7 +249,7 @@ def inference_main(argv=None):
     wavs = sorted(Path(args.input_dir).glob(f"*{args.ext}"))
     if not args.serial:
         t0 = time.time()
-        done = demix_directory(separator, wavs, out_dir, device=args.device)
+        done = demix_directory(separator, wavs, out_dir, device=args.device, remix=remix)
         wall = time.time() - t0
         if done:
             print(f"xumx-sliCQ-V2 inference time: {sum(d[2] for d in done) / len(done) / 1e3:.4f} s/track over {len(done)} track(s); "
@@ -199,7 +258,10 @@ def inference_main(argv=None):
     tot, n = 0.0, 0
     for wav in wavs:
         sig, rate = xaudio.load_audio(str(wav))
-        estimates, dt = separate(sig, separator, rate=rate, device=args.device)
+        if remix is None:
+            estimates, dt = separate(sig, separator, rate=rate, device=args.device)
+        else:
+            estimates, dt = _remix_one(sig, separator, rate, args.device, remix)
         tot, n = tot + dt, n + 1
         target_dir = out_dir / wav.stem
         target_dir.mkdir(parents=True, exist_ok=True)

@@ -310,10 +310,12 @@ class Separator(nn.Module):
             pool.append(torch.cuda.Stream(device=dev))
         return pool[0]
 
-    def _forward_native(self, audio_big: Tensor, wiener: int, slot: Optional[Tensor] = None) -> Tensor:
+    def _forward_native(self, audio_big: Tensor, wiener: int, slot: Optional[Tensor] = None, gains: Optional[Tensor] = None) -> Tensor:
         """``forward`` as ONE C call (xsq_separator_forward, csrc/demix.hip): the stacked full chunks on the caller's
         stream, the tail chunk beside them on a side stream, the input read and the stems written in place through
-        row-offset tables cached per call shape.  Per call the host allocates the result and makes one ctypes call."""
+        row-offset tables cached per call shape.  Per call the host allocates the result and makes one ctypes call.
+        ``gains`` (host fp32 (R, 4)): the R mixes of ``remix`` instead of the stems (xsq_separator_remix, same schedule
+        and workspaces)."""
         from . import _lib
         import ctypes as C
         if audio_big.dtype != torch.float32 or not audio_big.is_contiguous():
@@ -344,6 +346,14 @@ class Separator(nn.Module):
             two = overlap and sizes[1] > 0
             ws = self._native_ws(dev, main.cuda_stream, "main", sizes[0] if two else max(sizes))
             wt = self._native_ws(dev, main.cuda_stream, "tail", sizes[1]) if two else None
+            if gains is not None:
+                out = torch.empty(gains.shape[0], nb, 2, N, dtype=torch.float32, device=dev)
+                _lib.check(_lib.lib.xsq_separator_remix(d, model, audio_big.data_ptr(), nb, N, cs, max_stack, wiener, 1 if two else 0,
+                                                        out.data_ptr(), ws.data_ptr(), ws.numel(), wt.data_ptr() if two else None,
+                                                        wt.numel() if two else 0, main.cuda_stream,
+                                                        side.cuda_stream if two else main.cuda_stream, gains.data_ptr(),
+                                                        int(gains.shape[0])), "xsq_separator_remix")
+                return out
             out = torch.empty(4, nb, 2, N, dtype=torch.float32, device=dev)
             fn, src = ((_lib.lib.xsq_separator_forward, audio_big.data_ptr()) if slot is None
                        else (_lib.lib.xsq_separator_forward_indirect, slot.data_ptr()))
@@ -435,6 +445,33 @@ class Separator(nn.Module):
             rest(tail_first)
         return out
 
+    @torch.no_grad()
+    def remix(self, audio_big: Tensor, gains) -> Tensor:
+        """(nb_samples, 2, N) fp32 on a ROCm device -> (R, nb_samples, 2, N): R <= 4 gain-weighted mixes of the stems,
+        mix r = sum_t gains[r, t] * forward(audio)[t] -- the slider mix of demixui.py:94-114, remix_signal of
+        cadenza/enhance.py:270-290, the target groups of to_dict (separator.py:235-259).  ``gains``: see ``remix_gains``
+        (an (R, 4) or (4,) array in ``sources`` order, a {target: gain} dict -- unnamed targets keep 1.0 -- or a list of
+        such dicts).  The inverse transform is linear, so the native path runs R inverse transforms per chunk instead of
+        four plus a sum (xsq_separator_remix); a target no row weights is never read.  When this call takes the Python
+        chunk loop (``_native_mode`` is None: an A/B switch off its default, a mixed model) the result is computed by
+        definition, ``einsum("rt,tbcn->rbcn", G, forward(audio))``."""
+        G = remix_gains(gains)
+        if not isinstance(audio_big, Tensor) or audio_big.device.type != "cuda":
+            raise ValueError("remix needs the audio on a ROCm device (as forward)")
+        wiener = self._native_mode(audio_big)
+        if wiener is None:
+            est = self.forward(audio_big)
+            return torch.einsum("rt,tbcn->rbcn", G.to(device=est.device, dtype=est.dtype), est)
+        return self._forward_native(audio_big, wiener, gains=G)
+
+    @torch.no_grad()
+    def forward_aggregate(self, audio_big: Tensor, aggregate_dict: dict) -> dict:
+        """``to_dict(forward(audio), aggregate_dict)`` (separator.py:235-259) through ``remix`` with 0/1 gain rows: one
+        inverse transform per group instead of four.  At most four groups."""
+        names, G = aggregate_gains(aggregate_dict)
+        out = self.remix(audio_big, G)
+        return {name: out[r] for r, name in enumerate(names)}
+
     @staticmethod
     def to_dict(estimates: Tensor, aggregate_dict: Optional[dict] = None) -> dict:
         """separator.py:234-259."""
@@ -447,6 +484,55 @@ class Separator(nn.Module):
                     new_estimates[key] = new_estimates[key] + estimates_dict[target]
             estimates_dict = new_estimates
         return estimates_dict
+
+
+def _gain_row(d: dict) -> list:
+    unknown = [k for k in d if k not in Separator.sources]
+    if unknown:
+        raise ValueError(f"unknown target(s) {unknown}; the targets are {Separator.sources}")
+    return [float(d.get(t, 1.0)) for t in Separator.sources]
+
+
+def remix_gains(gains) -> Tensor:
+    """Gain matrix (R, 4) fp32 on the host for ``Separator.remix``, targets in ``Separator.sources`` order, from
+    - an (R, 4) or (4,) tensor / array / nested list of numbers;
+    - a {target: gain} dict: one row, targets not named keep gain 1.0 ({"vocals": 0} is karaoke);
+    - a list of such dicts: one row each.
+    ValueError for unknown targets, a shape other than (R, 4) with 1 <= R <= 4, and non-finite gains."""
+    if isinstance(gains, dict):
+        rows = [_gain_row(gains)]
+    elif isinstance(gains, (list, tuple)) and len(gains) > 0 and all(isinstance(g, dict) for g in gains):
+        rows = [_gain_row(g) for g in gains]
+    elif isinstance(gains, (list, tuple)) and any(isinstance(g, dict) for g in gains):
+        raise ValueError("a list of gains is all dicts or all numbers")
+    else:
+        rows = gains
+    try:
+        G = torch.as_tensor(rows.detach().cpu() if isinstance(rows, Tensor) else rows, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"gains must be an (R, 4) array, a {{target: gain}} dict or a list of dicts ({e})") from None
+    if G.dim() == 1:
+        G = G[None]
+    if G.dim() != 2 or G.shape[1] != 4 or not 1 <= G.shape[0] <= 4:
+        raise ValueError(f"gains must be (R, 4) with 1 <= R <= 4, targets {Separator.sources}; got {tuple(G.shape)}")
+    if not bool(torch.isfinite(G).all()):
+        raise ValueError("gains must be finite")
+    return G.contiguous()
+
+
+def aggregate_gains(aggregate_dict: dict):
+    """(group names, (R, 4) 0/1 gain matrix) of a to_dict aggregate_dict ({group: [targets]}, at most four groups)."""
+    if not isinstance(aggregate_dict, dict) or not 1 <= len(aggregate_dict) <= 4:
+        raise ValueError("aggregate_dict must be a dict of 1 to 4 groups {name: [targets]}")
+    names, rows = list(aggregate_dict), []
+    for name in names:
+        row = [0.0] * 4
+        for t in aggregate_dict[name]:
+            if t not in Separator.sources:
+                raise ValueError(f"unknown target {t!r} in group {name!r}; the targets are {Separator.sources}")
+            row[Separator.sources.index(t)] += 1.0        # a target named twice counts twice, as in to_dict
+        rows.append(row)
+    return names, torch.tensor(rows, dtype=torch.float32)
 
 
 def build_models(fscale: str = "bark", fbins: int = 262, fmin: float = 32.9, sample_rate: float = 44100.0,
