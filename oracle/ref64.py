@@ -1,0 +1,194 @@
+"""Float64 reference of the demix hot path: sliCQT, CDAE masks, post-filters, the whole chain for one chunk.
+
+TEST INFRASTRUCTURE (see oracle/__init__.py).  The fp32 oracle (oracle/slicqt.py, oracle/model.py) is pinned to the
+reference, but it rounds like the kernels do, so a comparison against it cannot hold a kernel tighter than a few
+thousand fp32 roundings.  This module restates the same closed forms (the docstrings of ``oslicqt.forward`` /
+``oslicqt.inverse``, ``omodel.cdae_masks``, ``omodel.norbert_wiener``) in float64 / complex128 on the SAME tables: the
+analysis windows ``g`` and the slice window ``tw`` are the plan's fp32 values promoted to float64, the dual windows
+``gd`` are fp64 already, the weights are the fp32 state dict promoted.  Against it the error of an fp32 implementation
+is its arithmetic alone; ``rel_err`` is the one metric every test of that kind uses.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import model as omodel
+from . import slicqt as oslicqt
+
+F64, C128 = torch.float64, torch.complex128
+
+
+# --------------------------------------------------------------------------
+# metric
+# --------------------------------------------------------------------------
+def rel_err(got: torch.Tensor, ref: torch.Tensor, keep: Sequence[int] = ()) -> Tuple[np.ndarray, np.ndarray]:
+    """(rel_rms, rel_max) of ``got`` against ``ref``, one value per index of the dimensions ``keep`` (all others are
+    pooled; ``keep=()`` gives two scalars): rel_rms = rms(got - ref) / rms(ref), rel_max = max|got - ref| / rms(ref).
+    Everything is promoted to float64 before the first subtraction.  A group whose reference is all zero has no scale:
+    that is an error of the test, not a result."""
+    g = got.detach().to("cpu", F64)
+    r = ref.detach().to("cpu", F64)
+    assert g.shape == r.shape, (tuple(g.shape), tuple(r.shape))
+    keep = tuple(k % r.dim() for k in keep)
+    pool = tuple(d for d in range(r.dim()) if d not in keep)
+    d = g - r
+    if not pool:
+        raise ValueError("rel_err: nothing to pool over")
+    ref_rms = r.pow(2).mean(pool).sqrt()
+    if not bool((ref_rms > 0).all()):
+        raise ValueError("rel_err: a group of the reference is identically zero")
+    return (d.pow(2).mean(pool).sqrt() / ref_rms).numpy(), (d.abs().amax(pool) / ref_rms).numpy()
+
+
+def band_rel_err(got: List[torch.Tensor], ref: List[torch.Tensor], per_row: bool = False):
+    """``rel_err`` per band over a block list of (*lead, F_b, S, T_b, 2) tensors: two arrays of nbands values (pooled
+    over the leading dimensions), or of prod(lead) x nbands values with ``per_row``."""
+    rms, mx = [], []
+    for a, b in zip(got, ref):
+        F = b.shape[-4]
+        a = a.reshape(-1, F, *b.shape[-3:])
+        b = b.reshape(-1, F, *b.shape[-3:])
+        r, m = rel_err(a, b, keep=(0, 1) if per_row else (1,))
+        rms.append(r)
+        mx.append(m)
+    return np.concatenate(rms, axis=-1), np.concatenate(mx, axis=-1)
+
+
+# --------------------------------------------------------------------------
+# sliCQT
+# --------------------------------------------------------------------------
+def forward(plan: oslicqt.Plan, x: torch.Tensor) -> List[torch.Tensor]:
+    """x (..., n) -> list over blocks of (..., F_b, S, T_b, 2) float64: the closed form of ``oslicqt.forward``,
+      coef[s,ch,j,:] = (-1)^(c_j/2) IFFT_Lg( g_j[q] U_s[(c_j+sq(q)) mod L] ),  U_s = FFT_L( tw * xpad[(2s-2)h : (2s+2)h] )."""
+    lead = x.shape[:-1]
+    n = x.shape[-1]
+    xb = x.reshape(-1, n).to(F64)
+    L, h = plan.L, plan.h
+    S = plan.nslices(n)
+    xpad = torch.zeros(xb.shape[0], (2 * S + 2) * h, dtype=F64)
+    xpad[:, 2 * h: 2 * h + n] = xb
+    seg = xpad.unfold(-1, L, 2 * h)[:, :S]                                   # (BC, S, L)
+    U = torch.fft.fft(seg * torch.from_numpy(plan.tw).to(F64))
+    out = []
+    for (j0, F, T) in plan.blocks:
+        sq = oslicqt._sq(T)
+        idx = torch.from_numpy((plan.c[j0:j0 + F, None] + sq[None, :]) % L)
+        gw = torch.from_numpy(np.stack(plan.g[j0:j0 + F])).to(F64)
+        sign = torch.from_numpy(np.where((plan.c[j0:j0 + F] // 2) % 2 == 0, 1.0, -1.0))
+        cb = torch.fft.ifft(U[:, :, idx] * gw) * sign[None, None, :, None]
+        cb = cb.permute(0, 2, 1, 3).contiguous()                             # (BC, F, S, T)
+        out.append(torch.view_as_real(cb).reshape(*lead, F, S, T, 2))
+    return out
+
+
+def inverse(plan: oslicqt.Plan, X_list: List[torch.Tensor], length: int) -> torch.Tensor:
+    """list of (*lead, F_b, S, T_b, 2) -> (*lead, length) float64: the closed form of ``oslicqt.inverse``,
+      fr_s[c_j+sq(q)] += (-1)^(c_j/2) Lg gd_j[q] FFT_Lg(coef_s,j)[q]  (bins 0..L/2);  seg_s = irfft_L(fr_s);
+      y[(2s-2)h + p] += seg_s[p]."""
+    L, h = plan.L, plan.h
+    lead = X_list[0].shape[:-4]
+    S = X_list[0].shape[-3]
+    BC = int(np.prod(lead)) if len(lead) else 1
+    fr = torch.zeros(BC, S, L // 2 + 1, dtype=C128)
+    for (j0, F, T), Xb in zip(plan.blocks, X_list):
+        cb = torch.view_as_complex(Xb.to(F64).reshape(BC, F, S, T, 2).contiguous())
+        fc = torch.fft.fft(cb)
+        sq = oslicqt._sq(T)
+        for f in range(F):
+            j = j0 + f
+            sign = 1.0 if (plan.c[j] // 2) % 2 == 0 else -1.0
+            w = torch.from_numpy(plan.gd[j] * (T * sign)).to(C128)
+            k = plan.c[j] + sq
+            keep = (k >= 0) & (k <= L // 2)
+            fr[:, :, torch.from_numpy(k[keep])] += (fc[:, f] * w)[:, :, torch.from_numpy(keep)]
+    seg = torch.fft.irfft(fr, n=L)
+    y = torch.zeros(BC, (2 * S + 2) * h, dtype=F64)
+    for s in range(S):
+        y[:, 2 * s * h: 2 * s * h + L] += seg[:, s]
+    return y[:, 2 * h: 2 * h + length].reshape(*lead, length)
+
+
+# --------------------------------------------------------------------------
+# CDAE
+# --------------------------------------------------------------------------
+_SD64 = {}
+
+
+def _sd64(sd: Dict[str, torch.Tensor], b: int) -> Dict[str, torch.Tensor]:
+    """The tensors of block ``b`` promoted to float64, cached per (state dict, block)."""
+    key = (id(sd), b)
+    hit = _SD64.get(key)
+    if hit is None or hit[0] is not sd:
+        pre = f"sliced_umx.{b}."
+        hit = _SD64[key] = (sd, {k: v.to(F64) for k, v in sd.items() if k.startswith(pre) and v.is_floating_point()})
+    return hit[1]
+
+
+def cdae_masks(sd: Dict[str, torch.Tensor], b: int, mag: torch.Tensor, causal: bool) -> torch.Tensor:
+    """mag (B, 2, F, S, T) -> sigmoid masks (4, B, 2, F, S, T) float64: ``omodel.cdae_masks`` itself, run on the
+    promoted state dict (every op in it follows the dtype of its operands)."""
+    with torch.no_grad():
+        return omodel.cdae_masks(_sd64(sd, b), b, mag.to(F64), causal)
+
+
+def cdae_logits(masks: torch.Tensor) -> torch.Tensor:
+    """The layer-4 pre-activation of float64-promoted masks, log(m / (1 - m)); for diagnosis of a failed mask comparison
+    only: meaningful where the mask is away from 0 and 1 (the tests look at (0.02, 0.98))."""
+    m = masks.to(F64)
+    return torch.log(m) - torch.log1p(-m)
+
+
+# --------------------------------------------------------------------------
+# post-filters
+# --------------------------------------------------------------------------
+def phasemix_sep(X: torch.Tensor, Ymag: torch.Tensor) -> torch.Tensor:
+    """X (B,2,F,S,T,2), Ymag (4,B,2,F,S,T) -> Ymag * exp(i angle(X)) as (4,B,2,F,S,T,2) float64."""
+    return omodel.phasemix_sep(X.to(F64), Ymag.to(F64))
+
+
+def blockwise_wiener(X: torch.Tensor, Ymag: torch.Tensor, win_len: int = omodel.WIENER_WIN) -> torch.Tensor:
+    """``omodel.blockwise_wiener`` in complex128, quirks kept: the regulariser is eps of FLOAT32 (and its square root),
+    the window maximum is shared over the batch, and the scale is max(1, 0.1 max|x|) per window (``omodel.norbert_wiener``
+    and ``omodel._em_one_iteration`` follow the dtype of their operands and are used as they are)."""
+    B, C, Fb, S, T, _ = X.shape
+    x = torch.view_as_complex(X.to(F64).reshape(B, C, Fb, S * T, 2).contiguous()).permute(0, 3, 2, 1)   # (B,N,F,C)
+    v = Ymag.to(F64).reshape(4, B, C, Fb, S * T).permute(1, 4, 3, 2, 0)                                  # (B,N,F,C,J)
+    N = S * T
+    wl = win_len if win_len else N
+    y = torch.zeros(B, N, Fb, C, 4, dtype=C128)
+    for p in range(0, N, wl):
+        y[:, p:p + wl] = omodel.norbert_wiener(v[:, p:p + wl], x[:, p:p + wl])
+    return torch.view_as_real(y).permute(4, 0, 3, 2, 1, 5).contiguous().reshape(4, B, C, Fb, S, T, 2)
+
+
+def abs_of_real_complex(X: torch.Tensor) -> torch.Tensor:
+    return omodel.abs_of_real_complex(X.to(F64))
+
+
+def unmix(sd: Dict[str, torch.Tensor], X_list: List[torch.Tensor], causal: bool, wiener: bool):
+    """``omodel.unmix`` in float64: (estimates, masks), lists over blocks."""
+    Ys, masks = [], []
+    for b, X in enumerate(X_list):
+        mag = abs_of_real_complex(X)
+        m = cdae_masks(sd, b, mag, causal)
+        Ymag = m * mag
+        Ys.append(blockwise_wiener(X, Ymag) if wiener else phasemix_sep(X, Ymag))
+        masks.append(m)
+    return Ys, masks
+
+
+def separate(plan: oslicqt.Plan, sd: Dict[str, torch.Tensor], audio: torch.Tensor, causal: bool, wiener: bool) -> torch.Tensor:
+    """audio (B, 2, n), ONE chunk -> (4, B, 2, n) float64: zero-pad to L/2 + 1 samples, sliCQT, CDAE masks, post-filter,
+    inverse sliCQT (``oracle.separator.separate`` with chunk_size >= n)."""
+    n = audio.shape[-1]
+    a = audio.to(F64)
+    min_samples = plan.L // 2 + 1
+    if n < min_samples:
+        a = torch.cat([a, torch.zeros(*a.shape[:-1], min_samples - n, dtype=F64)], dim=-1)
+    with torch.no_grad():
+        Y, _ = unmix(sd, forward(plan, a), causal, wiener)
+        return inverse(plan, Y, n)
