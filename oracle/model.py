@@ -33,9 +33,15 @@ def abs_of_real_complex(X: torch.Tensor) -> torch.Tensor:
     return torch.sqrt(X[..., 0] ** 2 + X[..., 1] ** 2)
 
 
-def _bn(x, sd, key, training=False, minima=None):
-    if training:      # batch statistics (nn.BatchNorm2d in train mode); running stats are not touched here
-        y = F.batch_norm(x, None, None, sd[key + ".weight"], sd[key + ".bias"], training=True, eps=BN_EPS)
+def _bn(x, sd, key, training=False, minima=None, stats=None):
+    if training:      # batch statistics (nn.BatchNorm2d in train mode); the running stats of ``sd`` are not touched here
+        rm = rv = None
+        if stats is not None:        # what nn.BatchNorm2d.train() would leave in its buffers (momentum 0.1), on COPIES, next to
+            rm, rv = sd[key + ".running_mean"].detach().clone(), sd[key + ".running_var"].detach().clone()   # the batch statistics
+        y = F.batch_norm(x, rm, rv, sd[key + ".weight"], sd[key + ".bias"], training=True, momentum=0.1, eps=BN_EPS)
+        if stats is not None:
+            xd = x.detach()
+            stats[key] = (xd.mean((0, 2, 3)), xd.var((0, 2, 3), unbiased=False), xd.numel() // xd.shape[1], rm, rv)
         if minima is not None:       # distance of the closest pre-activation to the ReLU kink (tests: subgradient ambiguity)
             minima[key] = float(y.detach().abs().min())
         return y
@@ -45,7 +51,7 @@ def _bn(x, sd, key, training=False, minima=None):
 
 
 def cdae_masks(sd: Dict[str, torch.Tensor], b: int, mag: torch.Tensor,
-               causal: bool, training: bool = False, minima=None) -> torch.Tensor:
+               causal: bool, training: bool = False, minima=None, stats=None) -> torch.Tensor:
     """Sigmoid masks of the four target CDAEs of block ``b``.
 
     mag (B, 2, F, S, T) fp32 -> (4, B, 2, F, S, T).  model.py:213-261 (whiten
@@ -62,11 +68,11 @@ def cdae_masks(sd: Dict[str, torch.Tensor], b: int, mag: torch.Tensor,
         p = f"{pre}cdaes.{t}."
         y = F.pad(x, (T - 1, 0)) if causal else x
         y = F.conv2d(y, sd[p + "0.weight"], stride=(1, hop))
-        y = F.relu(_bn(y, sd, p + "1", training, minima))
+        y = F.relu(_bn(y, sd, p + "1", training, minima, stats))
         y = F.conv2d(y, sd[p + "3.weight"])
-        y = F.relu(_bn(y, sd, p + "4", training, minima))
+        y = F.relu(_bn(y, sd, p + "4", training, minima, stats))
         y = F.conv_transpose2d(y, sd[p + "6.weight"])
-        y = F.relu(_bn(y, sd, p + "7", training, minima))
+        y = F.relu(_bn(y, sd, p + "7", training, minima, stats))
         y = F.conv_transpose2d(y, sd[p + "9.weight"], sd[p + "9.bias"], stride=(1, hop))
         y = torch.sigmoid(y)
         y = y[..., :Fb, : S * T]

@@ -192,3 +192,74 @@ def separate(plan: oslicqt.Plan, sd: Dict[str, torch.Tensor], audio: torch.Tenso
     with torch.no_grad():
         Y, _ = unmix(sd, forward(plan, a), causal, wiener)
         return inverse(plan, Y, n)
+
+
+# --------------------------------------------------------------------------
+# training step: loss, gradients, BatchNorm statistics, AdamW
+# --------------------------------------------------------------------------
+def block_gradients(sd: Dict[str, torch.Tensor], b: int, Xb: torch.Tensor, Ytb: torch.Tensor, causal: bool, wiener: bool,
+                    nblocks: int, dtype: torch.dtype = F64, params: Dict[str, torch.Tensor] = None):
+    """Block ``b``'s share of one training step (``oracle.loss.training_gradients``), from COEFFICIENTS: Xb (B, 2, F, S, T, 2) mix,
+    Ytb (4, B, 2, F, S, T, 2) targets.  Both losses are means over blocks, so the share of a block is its own term over
+    ``nblocks`` and its gradients do not depend on the other blocks.  Autograd in ``dtype`` over ``omodel.cdae_masks(training=True)``,
+    the post-filter and ``oloss.complex_mse`` / ``oloss.mask_sum``; float32 gives the fp32 oracle's arithmetic on the same input.
+    Returns (mse_b, mask_b, {key: grad}, {bn key: min |BatchNorm output|}, {bn key: (batch mean, biased batch variance, count,
+    running_mean, running_var after the step as F.batch_norm(training=True) leaves them)}).  ``params`` (the block's tensors in
+    ``dtype``) replaces the promoted state dict: the finite-difference test moves them."""
+    from . import loss as oloss
+    pre = f"sliced_umx.{b}."
+    if params is None:
+        params = {k: v.to(dtype) for k, v in sd.items() if k.startswith(pre) and v.is_floating_point()}
+    p = {k: (v.detach().clone().requires_grad_(True) if k.endswith(oloss.TRAINABLE_SUFFIXES) else v) for k, v in params.items()}
+    minima, stats = {}, {}
+    X = Xb.to(dtype)
+    mag = omodel.abs_of_real_complex(X)
+    m = omodel.cdae_masks(p, b, mag, causal, training=True, minima=minima, stats=stats)
+    Ymag = m * mag
+    if not wiener:
+        Y = omodel.phasemix_sep(X, Ymag)
+    elif dtype == F64:
+        Y = blockwise_wiener(X, Ymag)
+    else:
+        Y = omodel.blockwise_wiener(X, Ymag)
+    mse = oloss.complex_mse([Y], [Ytb.to(dtype)]) / nblocks
+    msk = oloss.mask_sum([m]) / nblocks
+    (mse + msk).backward()
+    grads = {k: v.grad for k, v in p.items() if v.requires_grad}
+    return float(mse.detach()), float(msk.detach()), grads, minima, stats
+
+
+def training_gradients(plan: oslicqt.Plan, sd: Dict[str, torch.Tensor], X_list: List[torch.Tensor], Yt_list: List[torch.Tensor],
+                       causal: bool, wiener: bool, dtype: torch.dtype = F64):
+    """One forward + backward of the training step from the coefficients of the mix and of the targets (lists over blocks):
+    (mse, mask, {key: grad}, {bn key: min |BatchNorm output|}, {bn key: statistics}) over all blocks, the loss terms summed in
+    float64.  Any of the four (causal, wiener) combinations."""
+    nb = len(plan.blocks)
+    assert len(X_list) == len(Yt_list) == nb
+    mse = msk = 0.0
+    grads, minima, stats = {}, {}, {}
+    for b in range(nb):
+        a, c, g, mi, st = block_gradients(sd, b, X_list[b], Yt_list[b], causal, wiener, nb, dtype)
+        mse, msk = mse + a, msk + c
+        grads.update(g), minima.update(mi), stats.update(st)
+    return mse, msk, grads, minima, stats
+
+
+def adamw_step(p, g, m, v, step: int, lr: float, wd: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    """One ``torch.optim.AdamW`` update in float64 (decoupled decay, bias-corrected moments; the constants are Python doubles):
+    returns (p, m, v) after step number ``step`` (1-based)."""
+    b1, b2 = betas
+    p, g, m, v = (t.to(F64) for t in (p, g, m, v))
+    p = p * (1.0 - lr * wd)
+    m = torch.lerp(m, g, 1.0 - b1)
+    v = (v * b2).addcmul(g, g, value=1.0 - b2)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    denom = (v.sqrt() / math.sqrt(bc2)).add(eps)
+    return p.addcdiv(m, denom, value=-(lr / bc1)), m, v
+
+
+def bn_running(old_mean, old_var, batch_mean, batch_var_biased, count: int, momentum: float = 0.1):
+    """The running buffers of ``nn.BatchNorm2d.train()`` after one batch, float64: the UNBIASED batch variance goes in."""
+    om, ov, bm, bv = (t.to(F64) for t in (old_mean, old_var, batch_mean, batch_var_biased))
+    unbiased = bv * (count / (count - 1.0)) if count > 1 else bv
+    return (1.0 - momentum) * om + momentum * bm, (1.0 - momentum) * ov + momentum * unbiased

@@ -14,19 +14,16 @@ may not exceed 16 for fp32 and bf16x6 arithmetic.  The measured tables are in
 profiles/ref64_parity.json, the worst ratio behind every M in DESIGN.md section 2.  With XSQ_REF64_TABLES=<file> the tables of
 a run are written there as JSON.
 """
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref64
+from oracle.parity import M_CAP, Tables
 from xumx_slicq_amd.synth import synth_audio
 
 pytestmark = pytest.mark.gpu
 RMS_TOL, MAX_TOL = 1e-4, 1e-3             # the contractual bar of tests/test_model_gpu.py, kept beside the tight one
-M_CAP = 16
 
 # stage -> M, with the worst e_gpu / E measured on MI355X behind it (DESIGN.md section 2, profiles/ref64_parity.json).  The stage's M
 # holds the default path; an A/B arm whose algorithm has a larger constant has its own, "stage/arm", by the same rule.
@@ -43,22 +40,14 @@ M = {
 }
 assert all(m <= M_CAP and m & (m - 1) == 0 for m in M.values())
 
-_TABLES = {}
+_T = Tables("ref64_parity", M)
+_TABLES, _judge = _T.tables, _T.judge
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _dump_tables():
     yield
-    path = os.environ.get("XSQ_REF64_TABLES")
-    if path:
-        worst = {}
-        for stage, cases in _TABLES.items():
-            for case, rec in cases.items():
-                key = rec.get("M_key", stage)
-                if rec["worst_ratio"] > worst.get(key, {"worst_ratio": 0.0})["worst_ratio"]:
-                    worst[key] = {"worst_ratio": rec["worst_ratio"], "case": case, "at": rec.get("worst_at", ""), "M": M.get(key)}
-        with open(path, "w") as f:
-            json.dump({"M": worst, "tables": _TABLES}, f, indent=0, sort_keys=True)
+    _T.dump()
 
 
 @pytest.fixture(scope="module")
@@ -88,30 +77,6 @@ def _arm(eng, arm):
 
 
 ARMS = ["default", "rocfft", "dense_bands", "short_inline"]
-
-
-def _judge(stage, case, e_gpu, e_cpu, labels, full_table=False, arm=None):
-    """Print the table, record it, and return the failures of  e_gpu <= M * E  (E = largest e_cpu, per metric)."""
-    key = f"{stage}/{arm}" if f"{stage}/{arm}" in M else stage
-    bound = M[key]
-    (g_rms, g_max), (c_rms, c_max) = e_gpu, e_cpu
-    g_rms, g_max, c_rms, c_max = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (g_rms, g_max, c_rms, c_max))
-    assert g_rms.shape == g_max.shape == c_rms.shape == c_max.shape == (len(labels),), (g_rms.shape, c_rms.shape, len(labels))
-    E_rms, E_max = float(c_rms.max()), float(c_max.max())
-    ratio = np.maximum(g_rms / E_rms, g_max / E_max)
-    w = int(np.argmax(ratio))
-    print(f"\n[{stage}] {case}: E_rms {E_rms:.3e} E_max {E_max:.3e}; worst e_gpu / E = {ratio[w]:.2f} at {labels[w]} (M = {bound})")
-    print("  index / class                      e_gpu rms   e_gpu max   e_cpu rms   e_cpu max   ratio")
-    for i, lab in enumerate(labels):
-        print(f"  {lab:34s} {g_rms[i]:.3e}   {g_max[i]:.3e}   {c_rms[i]:.3e}   {c_max[i]:.3e}   {ratio[i]:.2f}")
-    rec = {"M_key": key, "E_rms": E_rms, "E_max": E_max, "worst_ratio": float(ratio[w]), "worst_at": labels[w],
-           "worst_e_gpu_rms": float(g_rms.max()), "worst_e_gpu_max": float(g_max.max())}
-    if full_table:
-        rec["table"] = {"label": list(labels), "e_gpu_rms": g_rms.tolist(), "e_gpu_max": g_max.tolist(),
-                        "e_cpu_rms": c_rms.tolist(), "e_cpu_max": c_max.tolist()}
-    _TABLES.setdefault(stage, {})[case] = rec
-    bad = [f"{labels[i]}: e_gpu rms {g_rms[i]:.3e} max {g_max[i]:.3e} = {ratio[i]:.2f} x E" for i in np.nonzero(ratio > bound)[0]]
-    return bad, float(ratio[w])
 
 
 def _band_labels(plan, rows=None):

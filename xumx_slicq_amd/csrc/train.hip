@@ -568,13 +568,13 @@ __global__ void k_input_grad_final(const double* __restrict__ part, const float*
 // ---- AdamW (torch.optim.AdamW semantics: decoupled weight decay, bias-corrected moments) ----------------------
 __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                         const unsigned char* __restrict__ trainable, int64_t n, float lr, float wd, float b1, float b2,
-                        float eps, float bc1, float bc2) {
+                        float omb1, float omb2, float eps, float bc1, float bc2) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !trainable[i]) return;
     float w = p[i] * (1.f - lr * wd);
     const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     w -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
     p[i] = w;
@@ -1101,9 +1101,12 @@ int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S
     // ---- update ---------------------------------------------------------------------------------------
     if (apply_update) {
         Tr->step += 1;
-        const float b1 = 0.9f, b2 = 0.999f;
+        // 1 - beta and the bias corrections are formed in double and rounded once, as torch.optim.AdamW hands them to its fp32
+        // kernels: 1.f - 0.999f is 1.3e-5 (relative) below 0.001, which went straight into the checkpointed exp_avg_sq
+        const double b1 = 0.9, b2 = 0.999;
         { XSQ_PROF("train_adamw", stream); hipLaunchKernelGGL(k_adamw, grid1(Tr->nparams), dim3(256), 0, stream, Tr->d_params, gp, Tr->d_m, Tr->d_v, Tr->d_trainable,
-                           Tr->nparams, lr, wd, b1, b2, 1e-8f, 1.f - powf(b1, (float)Tr->step), 1.f - powf(b2, (float)Tr->step)); }
+                           Tr->nparams, lr, wd, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f,
+                           (float)(1.0 - pow(b1, (double)Tr->step)), (float)(1.0 - pow(b2, (double)Tr->step))); }
     }
     XSQ_HIP(hipGetLastError());
     // loss scalars: per-block terms to pinned host memory behind an event (ring slot = ticket % LOSS_RING)
