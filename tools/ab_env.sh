@@ -1,5 +1,5 @@
 # A/B of diagnostic environment switches on the headline bench (one process per setting; differences below ~2 % are noise).
-# usage: tools/ab_env.sh OUTDIR "NAME=ENV..." ...      e.g.  tools/ab_env.sh gpurun_out/ab "base=" "late=XSQ_CDAE_VARIANT=512"
+# usage: tools/ab_env.sh OUTDIR "NAME=ENV..." ...      e.g.  tools/ab_env.sh out/ab "base=" "complex=XSQ_D4_SYM=0"
 O=$1; shift
 mkdir -p $O
 for spec in "$@"; do

@@ -1,6 +1,6 @@
 # One SQ counter pass over the headline bench (2 steps) and a per-kernel table: matrix-pipe busy, vector-ALU issue utilisation,
 # share of wave cycles in s_waitcnt, LDS bank-conflict cycles per LDS-active... for the kernels matching FILTER (regex).
-# usage (GPU box): tools/pmc_quick.sh OUTDIR [FILTER]     (XSQ_LIB / XSQ_CDAE_VARIANT etc. pass through)
+# usage (GPU box): tools/pmc_quick.sh OUTDIR [FILTER]     (XSQ_LIB etc. pass through)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}      # (resolved before the cd: the scripts run from /tmp)
 cd /tmp && export TMPDIR=/tmp
 O=$R/$1; F=${2:-wino|slab}

@@ -592,288 +592,176 @@ namespace xsq {
 // ------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------
-}  // namespace xsq
-namespace xsq {
 
 // F(4, 4) weights of layers 2 / 3 (cdae_wino4.h: an A/B arm, off by default) are built with a model only when XSQ_WINO4=1 is set at
 // xsq_model_create -- 7 / 5 of the F(2, 4) pool on top, and their share of the fp64 transform at load time
 static bool wino4_wanted() { return getenv("XSQ_WINO4") && atoi(getenv("XSQ_WINO4")) != 0; }
 
-static const int L23_MT = 1;     // 256-row tiles (MT = 2) measured slower: 192 VGPR -> 2 waves per SIMD (L3 1.51 -> 1.74 ms)
-
 static int kf_of(int F) { return F < 10 ? 1 : (F < 20 ? 3 : 5); }   // model.py:112-117
 
-static int get_cdae_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int mt23 = L23_MT, bool n16 = false, bool tgt_outer = false) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(layer + 16 * mt23 + (n16 ? 128 : 0) + (tgt_outer ? 256 : 0), Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    std::vector<TileDev> t;
-    // longest tiles first: order the blocks by the K of this layer, descending
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    auto kof = [&](int b) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        return layer == 1 ? 2 * d.kf * d.T : (layer >= 4 ? d.kf * 2 * CS : d.kf * 4 * CS);
-    };
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return kof(x) > kof(y); });
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        int64_t M; int N;
-        switch (layer) {
-            case 1: M = (int64_t)Bn * d.F1 * T1; N = CS; break;
-            case 2: M = (int64_t)Bn * d.F2 * T2; N = CS; break;
-            case 3: M = (int64_t)Bn * d.F1 * T1; N = CS; break;
-            case 4: M = (int64_t)Bn * d.F * 2 * S; N = d.T; break;
-            default: M = (int64_t)Bn * d.F * (T1 + 1); N = d.T; break;     // 6: layer-4 operator as layer-1 data gradient
-        }
-        if (layer == 1 || layer == 4 || layer == 6) {
-            // the four targets read the same input (L1: whitened magnitude) / the same mix X (L4 epilogue):
-            // keep their tiles of one (row, column) patch adjacent so the re-reads hit the XCD's L2
-            auto push = [&](int64_t m0, int n0, int tgt) {
-                const int rem = N - n0;      // n16 (layer 4, fp32 inference): widths 16 / 32 / 48 / 64, see gemm_tile.h XW = 2
-                const int kind = n16 ? (rem <= 16 ? 2 : rem <= 32 ? 1 : rem <= 48 ? 3 : 0) : (rem <= 32 ? 1 : 0);
-                t.push_back(TileDev{b * 4 + tgt, (int)m0, n0, kind});
-            };
-            if (tgt_outer) {
-                // layer 4 storing masks only: the targets share nothing (each reads its own layer-3 activations), while
-                // the column tiles of a row block share its operand rows and neighbouring row blocks share rows through the
-                // frequency taps: one (block, target) after the other (r4t: 0.689 -> 0.675 ms; target innermost and
-                // column tiles adjacent per target measured 0.694)
-                for (int tgt = 0; tgt < NT; ++tgt)
-                    for (int64_t m0 = 0; m0 < M; m0 += 128)
-                        for (int n0 = 0; n0 < N; n0 += 64) push(m0, n0, tgt);
-            } else {
-                for (int64_t m0 = 0; m0 < M; m0 += 128)
-                    for (int n0 = 0; n0 < N; n0 += 64)
-                        for (int tgt = 0; tgt < NT; ++tgt) push(m0, n0, tgt);
+static int get_cdae_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, bool n16 = false, bool tgt_outer = false) {
+    const TileKey key{TileKind::CdaeGemm, Bn, S, layer, (n16 ? 1 : 0) | (tgt_outer ? 2 : 0)};
+    return cached_tiles<TileDev>(Mo->mu, Mo->tiles, key, out, [&](std::vector<TileDev>& t) {
+        const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
+        // longest tiles first: order the blocks by the K of this layer, descending
+        const std::vector<int> order = order_descending(Mo->nblocks, [&](int b) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            return layer == 1 ? 2 * d.kf * d.T : (layer >= 4 ? d.kf * 2 * CS : d.kf * 4 * CS);
+        });
+        for (int b : order) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            int64_t M; int N;
+            switch (layer) {
+                case 1: M = (int64_t)Bn * d.F1 * T1; N = CS; break;
+                case 2: M = (int64_t)Bn * d.F2 * T2; N = CS; break;
+                case 3: M = (int64_t)Bn * d.F1 * T1; N = CS; break;
+                case 4: M = (int64_t)Bn * d.F * 2 * S; N = d.T; break;
+                default: M = (int64_t)Bn * d.F * (T1 + 1); N = d.T; break;     // 6: layer-4 operator as layer-1 data gradient
             }
-        } else {
-            for (int tgt = 0; tgt < NT; ++tgt) push_group_tiles(t, b * 4 + tgt, M, N, 128 * mt23);
+            if (layer == 1 || layer == 4 || layer == 6) {
+                // the four targets read the same input (L1: whitened magnitude) / the same mix X (L4 epilogue):
+                // keep their tiles of one (row, column) patch adjacent so the re-reads hit the XCD's L2
+                auto push = [&](int64_t m0, int n0, int tgt) {
+                    const int rem = N - n0;      // n16 (layer 4, fp32 inference): widths 16 / 32 / 48 / 64, see gemm_tile.h XW = 2
+                    const int kind = n16 ? (rem <= 16 ? 2 : rem <= 32 ? 1 : rem <= 48 ? 3 : 0) : (rem <= 32 ? 1 : 0);
+                    t.push_back(TileDev{b * 4 + tgt, (int)m0, n0, kind});
+                };
+                if (tgt_outer) {
+                    // layer 4 storing masks only: the targets share nothing (each reads its own layer-3 activations), while
+                    // the column tiles of a row block share its operand rows and neighbouring row blocks share rows through the
+                    // frequency taps: one (block, target) after the other (r4t: 0.689 -> 0.675 ms; target innermost and
+                    // column tiles adjacent per target measured 0.694)
+                    for (int tgt = 0; tgt < NT; ++tgt)
+                        for (int64_t m0 = 0; m0 < M; m0 += 128)
+                            for (int n0 = 0; n0 < N; n0 += 64) push(m0, n0, tgt);
+                } else {
+                    for (int64_t m0 = 0; m0 < M; m0 += 128)
+                        for (int n0 = 0; n0 < N; n0 += 64)
+                            for (int tgt = 0; tgt < NT; ++tgt) push(m0, n0, tgt);
+                }
+            } else {
+                for (int tgt = 0; tgt < NT; ++tgt) push_group_tiles(t, b * 4 + tgt, M, N);
+            }
         }
-    }
-    TileTable tt;
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc(&tt.d_tiles, t.size() * sizeof(TileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(TileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    });
+}
+
+// the blocks by their frequency taps, descending: the order of every table of layers 2 to 4 below
+static std::vector<int> blocks_by_taps(const xsq_model* Mo) {
+    return order_descending(Mo->nblocks, [&](int b) { return Mo->blocks[b].kf; });
 }
 
 // tiles of the slab kernels (cdae_slab.h): 256 consecutive rows inside one batch item, all 64 columns
-static int get_slab_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int max_kf = 1 << 30) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(layer + 64 + (max_kf < (1 << 30) ? 1000 * max_kf : 0), Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Mo->blocks[x].kf > Mo->blocks[y].kf; });
-    std::vector<SlabTileDev> t;
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        if (d.kf > max_kf) continue;
-        const int64_t perb = layer == 2 ? (int64_t)d.F2 * T2 : (int64_t)d.F1 * T1;
-        for (int tgt = 0; tgt < NT; ++tgt) {
-            const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
-            const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
-            SlabTileDev e;
-            e.kf = d.kf;
-            if (layer == 2) { e.Fo = d.F2; e.Fi = d.F1; e.in_off = off1; e.out_off = off2; e.shift_off = d.s2[tgt]; e.w_off = d.w2[tgt]; }
-            else { e.Fo = d.F1; e.Fi = d.F2; e.in_off = off2; e.out_off = off1; e.shift_off = d.s3[tgt]; e.w_off = d.w3[tgt]; }
-            const int To = layer == 2 ? T2 : T1;
-            e.pad = 0;
-            for (int bi = 0; bi < Bn; ++bi)
-                for (int64_t r = 0; r < perb; r += SLAB_ROWS) {
-                    e.m0 = (int)(bi * perb + r); e.b = bi; e.f0 = (int)(r / To); e.t0 = (int)(r % To);
-                    t.push_back(e);
-                }
+static int get_slab_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out) {
+    return cached_tiles<SlabTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeSlab, Bn, S, layer, 0}, out, [&](std::vector<SlabTileDev>& t) {
+        const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
+        for (int b : blocks_by_taps(Mo)) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            const int64_t perb = layer == 2 ? (int64_t)d.F2 * T2 : (int64_t)d.F1 * T1;
+            for (int tgt = 0; tgt < NT; ++tgt) {
+                const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
+                const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
+                SlabTileDev e;
+                e.kf = d.kf;
+                if (layer == 2) { e.Fo = d.F2; e.Fi = d.F1; e.in_off = off1; e.out_off = off2; e.shift_off = d.s2[tgt]; e.w_off = d.w2[tgt]; }
+                else { e.Fo = d.F1; e.Fi = d.F2; e.in_off = off2; e.out_off = off1; e.shift_off = d.s3[tgt]; e.w_off = d.w3[tgt]; }
+                const int To = layer == 2 ? T2 : T1;
+                e.pad = 0;
+                for (int bi = 0; bi < Bn; ++bi)
+                    for (int64_t r = 0; r < perb; r += SLAB_ROWS) {
+                        e.m0 = (int)(bi * perb + r); e.b = bi; e.f0 = (int)(r / To); e.t0 = (int)(r % To);
+                        t.push_back(e);
+                    }
+            }
         }
-    }
-    TileTable tt;                    // (d_tiles holds SlabTileDev entries for this key: cast at the launch sites)
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(SlabTileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(SlabTileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    });
 }
 
-// tiles of the Winograd kernels (cdae_wino.h): 64 consecutive output PAIRS of one batch item in the flattened (f, pair) space
-static int get_wino_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int min_kf = 0) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(layer + 96 + 1000 * min_kf, Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Mo->blocks[x].kf > Mo->blocks[y].kf; });
-    std::vector<WinoTileDev> t;
-    const int To = layer == 2 ? T2 : T1, P = (To + 1) / 2;
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        if (d.kf < min_kf) continue;
-        for (int tgt = 0; tgt < NT; ++tgt) {
-            const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
-            const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
-            WinoTileDev e;
-            e.kf = d.kf; e.P = P;
-            if (layer == 2) { e.Fo = d.F2; e.Fi = d.F1; e.in_off = off1; e.out_off = off2; e.shift_off = d.s2[tgt]; e.u_off = d.u2[tgt]; }
-            else { e.Fo = d.F1; e.Fi = d.F2; e.in_off = off2; e.out_off = off1; e.shift_off = d.s3[tgt]; e.u_off = d.u3[tgt]; }
-            const int perb = e.Fo * P;
-            e.pad0 = e.pad1 = 0;
-            for (int bi = 0; bi < Bn; ++bi)
-                for (int Q = 0; Q < perb; Q += WN_PAIRS) {
-                    e.Q0 = Q; e.b = bi;
-                    t.push_back(e);
-                }
+// tiles of the Winograd kernels, `outs` outputs per entry of a tile: F(2, 4) (cdae_wino.h; outs = 2) -- 64 consecutive output
+// PAIRS of one batch item in the flattened (f, pair) space -- or F(4, 4) (cdae_wino4.h; outs = 4) -- 64 consecutive QUADS
+static int get_wino_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int outs = 2) {
+    return cached_tiles<WinoTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeWino, Bn, S, layer, outs}, out, [&](std::vector<WinoTileDev>& t) {
+        const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
+        const int To = layer == 2 ? T2 : T1, P = (To + outs - 1) / outs, len = outs == 4 ? W4_QUADS : WN_PAIRS;
+        for (int b : blocks_by_taps(Mo)) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            for (int tgt = 0; tgt < NT; ++tgt) {
+                const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
+                const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
+                WinoTileDev e;
+                e.kf = d.kf; e.P = P;
+                if (layer == 2) { e.Fo = d.F2; e.Fi = d.F1; e.in_off = off1; e.out_off = off2; e.shift_off = d.s2[tgt]; e.u_off = (outs == 4 ? d.uq2 : d.u2)[tgt]; }
+                else { e.Fo = d.F1; e.Fi = d.F2; e.in_off = off2; e.out_off = off1; e.shift_off = d.s3[tgt]; e.u_off = (outs == 4 ? d.uq3 : d.u3)[tgt]; }
+                const int perb = e.Fo * P;
+                e.pad0 = e.pad1 = 0;
+                for (int bi = 0; bi < Bn; ++bi)
+                    for (int Q = 0; Q < perb; Q += len) {
+                        e.Q0 = Q; e.b = bi;
+                        t.push_back(e);
+                    }
+            }
         }
-    }
-    TileTable tt;                    // (d_tiles holds WinoTileDev entries for this key: cast at the launch site)
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(WinoTileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(WinoTileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
-}
-
-// tiles of the F(4, 4) kernels (cdae_wino4.h): 64 consecutive output QUADS of one batch item in the flattened (f, quad) space
-static int get_wino4_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(layer + 192, Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Mo->blocks[x].kf > Mo->blocks[y].kf; });
-    std::vector<WinoTileDev> t;
-    const int To = layer == 2 ? T2 : T1, P = (To + 3) / 4;
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        for (int tgt = 0; tgt < NT; ++tgt) {
-            const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
-            const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
-            WinoTileDev e;
-            e.kf = d.kf; e.P = P;
-            if (layer == 2) { e.Fo = d.F2; e.Fi = d.F1; e.in_off = off1; e.out_off = off2; e.shift_off = d.s2[tgt]; e.u_off = d.uq2[tgt]; }
-            else { e.Fo = d.F1; e.Fi = d.F2; e.in_off = off2; e.out_off = off1; e.shift_off = d.s3[tgt]; e.u_off = d.uq3[tgt]; }
-            const int perb = e.Fo * P;
-            e.pad0 = e.pad1 = 0;
-            for (int bi = 0; bi < Bn; ++bi)
-                for (int Q = 0; Q < perb; Q += W4_QUADS) {
-                    e.Q0 = Q; e.b = bi;
-                    t.push_back(e);
-                }
-        }
-    }
-    TileTable tt;                    // (d_tiles holds WinoTileDev entries for this key: cast at the launch site)
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(WinoTileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(WinoTileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    });
 }
 
 // tiles of the layer-1 F(2, 2) kernel (cdae_l1f.h): 64 consecutive output PAIRS of one batch item in the flattened (f1, pair)
 // space; the four targets of a patch adjacent (they read the same whitened magnitudes: the re-reads hit the XCD's L2)
 static int get_l1f_tiles(xsq_model* Mo, int Bn, int S, TileTable* out) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(1 + 160, Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = 2 * S - 1, P = (T1 + 1) / 2;
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Mo->blocks[x].nch1 > Mo->blocks[y].nch1; });
-    std::vector<L1fTileDev> t;
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        L1fTileDev e;
-        e.kf = d.kf; e.F = d.F; e.F1 = d.F1; e.hop = d.hop; e.nchunks = d.nch1; e.P = P;
-        e.in_off = (int64_t)Bn * 2 * S * d.cum;
-        const int total = Bn * d.F1 * P;                   // tiles run across batch items: (b, f1, pair) flattened
-        e.pad0 = 0;
-        for (int Q = 0; Q < total; Q += LF_PAIRS)
-            for (int tgt = 0; tgt < NT; ++tgt) {
-                e.Q0 = Q;
-                e.out_off = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);
-                e.shift_off = d.s1[tgt]; e.u_off = d.u1[tgt];
-                t.push_back(e);
-            }
-    }
-    TileTable tt;                    // (d_tiles holds L1fTileDev entries for this key: cast at the launch site)
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(L1fTileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(L1fTileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    return cached_tiles<L1fTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeL1f, Bn, S, 1, 0}, out, [&](std::vector<L1fTileDev>& t) {
+        const int T1 = 2 * S - 1, P = (T1 + 1) / 2;
+        for (int b : order_descending(Mo->nblocks, [&](int b) { return Mo->blocks[b].nch1; })) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            L1fTileDev e;
+            e.kf = d.kf; e.F = d.F; e.F1 = d.F1; e.hop = d.hop; e.nchunks = d.nch1; e.P = P;
+            e.in_off = (int64_t)Bn * 2 * S * d.cum;
+            const int total = Bn * d.F1 * P;                   // tiles run across batch items: (b, f1, pair) flattened
+            e.pad0 = 0;
+            for (int Q = 0; Q < total; Q += LF_PAIRS)
+                for (int tgt = 0; tgt < NT; ++tgt) {
+                    e.Q0 = Q;
+                    e.out_off = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);
+                    e.shift_off = d.s1[tgt]; e.u_off = d.u1[tgt];
+                    t.push_back(e);
+                }
+        }
+    });
 }
 
 // tiles of the layer-4 F(2, 2) kernel (cdae_l4f.h): 64 consecutive output PAIRS of one batch item in the flattened (f, pair)
 // space x one column tile of <= 64 columns; one (block, target) after the other (the targets share nothing; the column tiles
 // of a row block share its operand rows, neighbouring row blocks share rows through the frequency taps)
-// taps = 0: the one-tap blocks (cdae_l4f_kernel); taps = 1: the multi-tap blocks, whose weight tiles of all taps fit the LDS of
-// cdae_l4f_taps_kernel (kf * 3 * 16 NCB rows <= L4_RES_ROWS) -- a launch of their own; multi-tap blocks that do not fit stay with
-// taps = 0 (one row tile per workgroup, weights re-staged per tap)
-static bool l4f_resident(const CdaeBlockDev& d) {
-    const int cols = l4f_cols(d.T);
-    return d.kf > 1 && cols <= 32 && d.kf * 3 * cols <= L4_RES_ROWS;
-}
-static int get_l4f_tiles(xsq_model* Mo, int Bn, int S, TileTable* out, int taps = 0) {
-    std::lock_guard<std::mutex> lk(Mo->mu);
-    auto key = std::make_tuple(4 + 160 + 32 * taps, Bn, S);
-    auto it = Mo->tiles.find(key);
-    if (it != Mo->tiles.end()) { *out = it->second; return XSQ_OK; }
-    const int T1 = 2 * S - 1, P = S;
-    std::vector<int> order(Mo->nblocks);
-    for (int b = 0; b < Mo->nblocks; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Mo->blocks[x].kf > Mo->blocks[y].kf; });
-    std::vector<L4fTileDev> t;
-    for (int b : order) {
-        const CdaeBlockDev& d = Mo->blocks[b];
-        // XSQ_L4F_RESIDENT=1 (A/B arm, off): the multi-tap blocks on cdae_l4f_taps_kernel, a launch of their own with all taps' weight
-        // tiles resident -- measured SLOWER (0.570-0.572 against 0.541-0.542 ms for the layer, profiles/r11_ab_runs.txt r11res)
-        static const bool res_on = getenv("XSQ_L4F_RESIDENT") && atoi(getenv("XSQ_L4F_RESIDENT")) != 0;
-        if ((l4f_resident(d) && res_on) != (taps != 0)) continue;
-        const int W = d.T, cols = l4f_cols(W);
-        const int64_t FST = (int64_t)d.F * S * d.T;
-        L4fTileDev e;
-        e.kf = d.kf; e.F = d.F; e.hop = d.hop; e.P = P; e.x_off = (int)((int64_t)Bn * 2 * S * d.cum);
-        const int total = Bn * d.F * P;                    // tiles run across batch items: (b, f, pair) flattened
-        const int rtiles = (total + L4_PAIRS - 1) / L4_PAIRS;
-        // one tap: a workgroup keeps its column tile's weights in LDS for a run of consecutive row tiles (cdae_l4f.h); runs of
-        // equal length, at most l4f_run row tiles
-        static const int l4f_run = getenv("XSQ_L4F_RUN") ? std::max(1, atoi(getenv("XSQ_L4F_RUN"))) : 6;
-        const int nruns = (d.kf == 1 || taps) ? (rtiles + l4f_run - 1) / l4f_run : rtiles;
-        for (int tgt = 0; tgt < NT; ++tgt) {
-            e.in_off = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);
-            e.out_off = (int64_t)Bn * 8 * S * d.cum + (int64_t)tgt * Bn * 2 * FST;
-            e.bias_off = d.b4[tgt];
-            for (int r = 0; r < nruns; ++r) {
-                const int t0 = (int)((int64_t)rtiles * r / nruns), t1 = (int)((int64_t)rtiles * (r + 1) / nruns);
-                for (int n0 = 0; n0 < cols; n0 += 64) {
-                    e.Q0 = t0 * L4_PAIRS; e.run = t1 - t0; e.n0 = n0;
-                    e.u_off = d.u4[tgt] + (int64_t)3 * CS * n0;
-                    t.push_back(e);
+static const int L4F_RUN = 6;        // row tiles of a one-tap workgroup's run (1: +2.5 %, 24: slower; profiles/r11_ab_runs.txt r11k)
+static int get_l4f_tiles(xsq_model* Mo, int Bn, int S, TileTable* out) {
+    return cached_tiles<L4fTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeL4f, Bn, S, 4, 0}, out, [&](std::vector<L4fTileDev>& t) {
+        const int T1 = 2 * S - 1, P = S;
+        for (int b : blocks_by_taps(Mo)) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            const int W = d.T, cols = l4f_cols(W);
+            const int64_t FST = (int64_t)d.F * S * d.T;
+            L4fTileDev e;
+            e.kf = d.kf; e.F = d.F; e.hop = d.hop; e.P = P; e.x_off = (int)((int64_t)Bn * 2 * S * d.cum);
+            const int total = Bn * d.F * P;                    // tiles run across batch items: (b, f, pair) flattened
+            const int rtiles = (total + L4_PAIRS - 1) / L4_PAIRS;
+            // one tap: a workgroup keeps its column tile's weights in LDS for a run of consecutive row tiles (cdae_l4f.h): runs of
+            // equal length, at most L4F_RUN row tiles.  Several taps: one row tile per workgroup, weights re-staged per tap (all
+            // taps resident on a launch of their own measured SLOWER: 0.570-0.572 against 0.541-0.542 ms for the layer,
+            // profiles/r11_ab_runs.txt r11res)
+            const int nruns = d.kf == 1 ? (rtiles + L4F_RUN - 1) / L4F_RUN : rtiles;
+            for (int tgt = 0; tgt < NT; ++tgt) {
+                e.in_off = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);
+                e.out_off = (int64_t)Bn * 8 * S * d.cum + (int64_t)tgt * Bn * 2 * FST;
+                e.bias_off = d.b4[tgt];
+                for (int r = 0; r < nruns; ++r) {
+                    const int t0 = (int)((int64_t)rtiles * r / nruns), t1 = (int)((int64_t)rtiles * (r + 1) / nruns);
+                    for (int n0 = 0; n0 < cols; n0 += 64) {
+                        e.Q0 = t0 * L4_PAIRS; e.run = t1 - t0; e.n0 = n0;
+                        e.u_off = d.u4[tgt] + (int64_t)3 * CS * n0;
+                        t.push_back(e);
+                    }
                 }
             }
         }
-    }
-    TileTable tt;                    // (d_tiles holds L4fTileDev entries for this key: cast at the launch site)
-    tt.ntiles = (int)t.size();
-    XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(L4fTileDev)));
-    XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(L4fTileDev), hipMemcpyHostToDevice));
-    Mo->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    });
 }
 
 static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
@@ -913,29 +801,51 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
     XSQ_REQUIRE(nparams == xsq_model_num_params(nblocks, F, T),
                 "xsq_model_create: got %lld parameters, the block table needs %lld", (long long)nparams,
                 (long long)xsq_model_num_params(nblocks, F, T));
-    struct PlanLike { std::vector<BlockHost> blocks; int nblocks; int64_t sumFT; } PL;
-    PL.nblocks = nblocks; PL.sumFT = 0;
+    std::vector<BlockHost> table;
+    int64_t sumFT = 0;
     for (int b = 0; b < nblocks; ++b) {
         XSQ_REQUIRE(F[b] >= 1 && T[b] >= 4 && T[b] % 4 == 0, "xsq_model_create: block %d has F=%d T=%d", b, F[b], T[b]);
         XSQ_REQUIRE(F[b] - 2 * (kf_of(F[b]) - 1) >= 1, "xsq_model_create: block with F=%d too small", F[b]);
-        PL.blocks.push_back(BlockHost{0, F[b], T[b], PL.sumFT});
-        PL.sumFT += (int64_t)F[b] * T[b];
+        table.push_back(BlockHost{0, F[b], T[b], sumFT});
+        sumFT += (int64_t)F[b] * T[b];
     }
-    PlanLike* P = &PL;
     xsq_model* Mo = new xsq_model();
     *partial = Mo;
-    Mo->causal = causal ? 1 : 0; Mo->nblocks = nblocks; Mo->sumFT = PL.sumFT; Mo->table = PL.blocks;
+    Mo->causal = causal ? 1 : 0; Mo->nblocks = nblocks; Mo->sumFT = sumFT; Mo->table = table;
     Mo->wino4 = wino4_wanted();
-    const double eps = 1e-5;
     std::vector<float> pool, upool, mean, scale;
-    std::vector<int64_t> cum(P->nblocks + 1, 0);
-    std::vector<int> blockF(P->nblocks);
+    std::vector<int64_t> cum(nblocks + 1, 0);
+    std::vector<int> blockF(nblocks);
     const float* p = params;
     int cumF1 = 0, cumF2 = 0;
     int64_t cumF = 0;
     auto alloc = [&](size_t n) { size_t o = pool.size(); pool.resize(o + n, 0.f); return (int64_t)o; };
-    for (int bi = 0; bi < P->nblocks; ++bi) {
-        const BlockHost& hb = P->blocks[bi];
+    // BatchNorm (inference) folded into the convolution before it: the scale of channel co; its shift goes into the pool
+    auto bn_fold = [&](const float* bn, int C, int co, int64_t shift_off) {
+        const float *bw = bn, *bb = bn + C, *rm = bn + 2 * C, *rv = bn + 3 * C;
+        const double s = (double)bw[co] / std::sqrt((double)rv[co] + 1e-5);
+        pool[shift_off + co] = (float)((double)bb[co] - (double)rm[co] * s);
+        return s;
+    };
+    // Winograd along the time taps: U_j = sum_dt G[j][dt] w[dt] of the FOLDED fp32 weights at wsrc (what the direct kernels
+    // contract with), summed in fp64, as [df][chunk][component][col < 51][k] tiles of UDF floats per frequency tap
+    auto wino_weights = [&](const double (*G)[4], int ncomp, int UDF, int (*u_off)(int, int, int), int64_t wsrc, int kf) {
+        const int K2 = kf * 4 * CS;
+        const int64_t u = (int64_t)upool.size();
+        upool.resize(upool.size() + (size_t)kf * UDF, 0.f);
+        for (int df = 0; df < kf; ++df)
+            for (int j = 0; j < ncomp; ++j)
+                for (int col = 0; col < WN_COLS; ++col)
+                    for (int ci = 0; ci < CS; ++ci) {
+                        double acc = 0.0;
+                        for (int dt = 0; dt < 4; ++dt)
+                            acc += G[j][dt] * (double)pool[wsrc + (size_t)col * K2 + (df * 4 + dt) * CS + ci];
+                        upool[u + (size_t)df * UDF + u_off(j, col, ci)] = (float)acc;
+                    }
+        return u;
+    };
+    for (int bi = 0; bi < nblocks; ++bi) {
+        const BlockHost& hb = table[bi];
         CdaeBlockDev d;
         memset(&d, 0, sizeof(d));
         d.F = hb.F; d.T = hb.T; d.hop = hb.T / 2; d.kf = kf_of(hb.F);
@@ -950,13 +860,12 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
         for (int t = 0; t < NT; ++t) {
             // ---- L1: Conv2d weight (50,2,kf,W); BN(50)
             const float* w = p; p += (size_t)H1 * 2 * kf * W;
-            const float *bw = p, *bb = p + H1, *rm = p + 2 * H1, *rv = p + 3 * H1; p += 4 * H1;
+            const float* bn = p; p += 4 * H1;
             const int K1 = 2 * kf * W;
             d.w1[t] = alloc((size_t)64 * d.ld1);                 // Wt[n = co][k]
             d.s1[t] = alloc(64);
             for (int co = 0; co < H1; ++co) {
-                const double s = (double)bw[co] / std::sqrt((double)rv[co] + eps);
-                pool[d.s1[t] + co] = (float)((double)bb[co] - (double)rm[co] * s);
+                const double s = bn_fold(bn, H1, co, d.s1[t]);
                 for (int k = 0; k < K1; ++k)       // k = (ci*kf + df)*W + dt, the weight's own order
                     pool[d.w1[t] + (size_t)co * d.ld1 + k] = (float)((double)w[(size_t)co * K1 + k] * s);
             }
@@ -983,13 +892,12 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
             }
             // ---- L2: Conv2d weight (51,50,kf,4); BN(51);  k = (df*4 + dt)*52 + c1
             w = p; p += (size_t)H2 * H1 * kf * 4;
-            bw = p; bb = p + H2; rm = p + 2 * H2; rv = p + 3 * H2; p += 4 * H2;
+            bn = p; p += 4 * H2;
             const int K2 = kf * 4 * CS;
             d.w2[t] = alloc((size_t)64 * K2);                    // K2 % 16 == 0
             d.s2[t] = alloc(64);
             for (int co = 0; co < H2; ++co) {
-                const double s = (double)bw[co] / std::sqrt((double)rv[co] + eps);
-                pool[d.s2[t] + co] = (float)((double)bb[co] - (double)rm[co] * s);
+                const double s = bn_fold(bn, H2, co, d.s2[t]);
                 for (int ci = 0; ci < H1; ++ci)
                     for (int df = 0; df < kf; ++df)
                         for (int dt = 0; dt < 4; ++dt)
@@ -999,53 +907,22 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
             // ---- L3: ConvTranspose2d weight (51,50,kf,4) = (in,out,kH,kW); BN(50)
             //      out3[c3,f3,t3] = sum w[c2,c3,df,dt] out2[c2,f3-df,t3-dt];  k = (df*4 + dt')*52 + c2, dt' = 3-dt
             w = p; p += (size_t)H2 * H1 * kf * 4;
-            bw = p; bb = p + H1; rm = p + 2 * H1; rv = p + 3 * H1; p += 4 * H1;
+            bn = p; p += 4 * H1;
             d.w3[t] = alloc((size_t)64 * K2);
             d.s3[t] = alloc(64);
             for (int co = 0; co < H1; ++co) {
-                const double s = (double)bw[co] / std::sqrt((double)rv[co] + eps);
-                pool[d.s3[t] + co] = (float)((double)bb[co] - (double)rm[co] * s);
+                const double s = bn_fold(bn, H1, co, d.s3[t]);
                 for (int ci = 0; ci < H2; ++ci)
                     for (int df = 0; df < kf; ++df)
                         for (int dt = 0; dt < 4; ++dt)
                             pool[d.w3[t] + (size_t)co * K2 + (df * 4 + (3 - dt)) * CS + ci] =
                                 (float)((double)w[(((size_t)ci * H1 + co) * kf + df) * 4 + dt] * s);
             }
-            // ---- Winograd F(2, 4) along the time taps (cdae_wino.h): U_j = sum_dt G[j][dt] w[dt] of the FOLDED fp32 weights above
-            //      (what the direct kernels contract with), summed in fp64, as [df][chunk][component][col < 51][k] tiles
-            for (int layer = 2; layer <= 3; ++layer) {
-                const int64_t wsrc = layer == 2 ? d.w2[t] : d.w3[t];
-                const int64_t u = (int64_t)upool.size();
-                upool.resize(upool.size() + (size_t)kf * WN_UDF, 0.f);
-                (layer == 2 ? d.u2[t] : d.u3[t]) = u;
-                for (int df = 0; df < kf; ++df)
-                    for (int j = 0; j < 5; ++j)
-                        for (int col = 0; col < WN_COLS; ++col)
-                            for (int ci = 0; ci < CS; ++ci) {
-                                double acc = 0.0;
-                                for (int dt = 0; dt < 4; ++dt)
-                                    acc += WN_G[j][dt] * (double)pool[wsrc + (size_t)col * K2 + (df * 4 + dt) * CS + ci];
-                                upool[u + (size_t)df * WN_UDF + wino_u_off(j, col, ci)] = (float)acc;
-                            }
-            }
-            // ---- Winograd F(4, 4) along the time taps (cdae_wino4.h), the same way: seven components
-            for (int layer = 2; layer <= 3; ++layer) {
-                (layer == 2 ? d.uq2[t] : d.uq3[t]) = -1;
-                if (!Mo->wino4) continue;
-                const int64_t wsrc = layer == 2 ? d.w2[t] : d.w3[t];
-                const int64_t u = (int64_t)upool.size();
-                upool.resize(upool.size() + (size_t)kf * W4_UDF, 0.f);
-                (layer == 2 ? d.uq2[t] : d.uq3[t]) = u;
-                for (int df = 0; df < kf; ++df)
-                    for (int j = 0; j < W4_NC; ++j)
-                        for (int col = 0; col < WN_COLS; ++col)
-                            for (int ci = 0; ci < CS; ++ci) {
-                                double acc = 0.0;
-                                for (int dt = 0; dt < 4; ++dt)
-                                    acc += W4_G[j][dt] * (double)pool[wsrc + (size_t)col * K2 + (df * 4 + dt) * CS + ci];
-                                upool[u + (size_t)df * W4_UDF + wino4_u_off(j, col, ci)] = (float)acc;
-                            }
-            }
+            // ---- Winograd F(2, 4) along the time taps (cdae_wino.h), five components, then F(4, 4) (cdae_wino4.h), seven
+            d.u2[t] = wino_weights(WN_G, 5, WN_UDF, wino_u_off, d.w2[t], kf);
+            d.u3[t] = wino_weights(WN_G, 5, WN_UDF, wino_u_off, d.w3[t], kf);
+            d.uq2[t] = Mo->wino4 ? wino_weights(W4_G, W4_NC, W4_UDF, wino4_u_off, d.w2[t], kf) : -1;
+            d.uq3[t] = Mo->wino4 ? wino_weights(W4_G, W4_NC, W4_UDF, wino4_u_off, d.w3[t], kf) : -1;
             // ---- L4: ConvTranspose2d weight (50,2,kf,W) = (in,out,kH,kW); bias(2)
             //      k = (df*2 + (1 - tap))*52 + c3 (tap 1 first: CdaeL4Op) ;  n = c*hop + dtlo ;  kernel column = dtlo + tap*hop
             w = p; p += (size_t)H1 * 2 * kf * W;
@@ -1082,7 +959,7 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
         }
         Mo->blocks.push_back(d);
     }
-    cum[P->nblocks] = P->sumFT;
+    cum[nblocks] = sumFT;
     Mo->sumF = cumF; Mo->sumF1 = cumF1; Mo->sumF2 = cumF2;
     if (p - params != nparams) {
         set_error("xsq_model_create: internal parameter walk mismatch");
@@ -1175,8 +1052,20 @@ int cdae_launch_magnitude(const xsq_model* Mo, const float* X, float* xin, const
     return XSQ_OK;
 }
 
+// one workgroup of `threads` per entry of a tile table of T
+template <class T>
+static void launch_tiles(void (*kernel)(CdaeArgs, const T*, int), int threads, const CdaeArgs& a, const TileTable& tt, hipStream_t stream) {
+    if (tt.ntiles) hipLaunchKernelGGL(kernel, dim3(tt.ntiles), dim3(threads), 0, stream, a, (const T*)tt.d_tiles, tt.ntiles);
+}
+
+// the slab kernel of a precision mode: split bf16x3 operands, fp32 operands cut in the kernel (bf16x6), or fp32 with exact-width
+// columns and the next slab fetched in its own slot (no registers held across the MFMA slots: no scratch)
+template <bool TRANSPOSED>
+static auto slab_kernel(bool bf3, bool bf6) {
+    return bf3 ? cdae_slab_kernel<TRANSPOSED, 1> : bf6 ? cdae_slab_kernel<TRANSPOSED, 2> : cdae_slab_kernel<TRANSPOSED, 3, true>;
+}
+
 int cdae_launch_layer(xsq_model* Mo, int layer, const CdaeArgs& a, hipStream_t stream, const char* prof_name) {
-    TileTable tt;
     // layers 1 and 4 read their operand rows through buffer descriptors with 32-bit byte offsets and out-of-range switches
     // (common.h), layer 4 stores its masks that way: a block's whitened magnitudes / masks of one target and its layer-3
     // activations stay below 2^30 bytes
@@ -1189,117 +1078,82 @@ int cdae_launch_layer(xsq_model* Mo, int layer, const CdaeArgs& a, hipStream_t s
             XSQ_REQUIRE((int64_t)2 * a.Bn * d.F * a.S * d.T < ((int64_t)1 << 31),
                         "xsq_cdae_forward: B=%d S=%d overflows the 32-bit offsets of a block; split the batch", a.Bn, a.S);
     if (layer == 4 && a.gx8) layer = 6;
+
     const bool bf3 = a.split != 0;      // set by xsq_cdae_forward (inference only); operands are in the split format
     const bool bf1 = Mo->precision == 3;       // training only (xsq_train_set_precision mode 1): operands rounded to bf16, one MFMA per product
     const bool bf6 = Mo->precision == 2 || bf1; // fp32 operands, cut (or rounded) in the kernel (any operator / epilogue: also the training step)
-    // Diagnostic A/B switches (default 0 = the product configuration; results stay correct in every setting):
-    //   1 bf16x3 generic engine with 256-row tiles      2 ... with 32-value K-steps      4 no slab kernels at all
-    //   8 no slab kernels on the fp32 path              64 fp32 slab kernels padded to 64 columns (MODE 0)
-    //   128 generic fp32 engine padded to 64 columns    256 layer 4 with 32/64-column tiles only
-    //   512 fp32 slab kernels request the next slab a whole df ahead (28 VGPRs held across the MFMA slots, spilled: r01)
-    static const int variant = getenv("XSQ_CDAE_VARIANT") ? atoi(getenv("XSQ_CDAE_VARIANT")) : 0;
-    const int mt23 = bf3 && (variant & 1) ? 2 : L23_MT;
-    const bool xw = !bf3 && !bf6 && !a.raw && !a.xin8 && !a.gx8 && layer <= 3 && !(variant & 128);   // fp32 inference: no column padding
-    if (!(variant & 4) && (layer == 2 || layer == 3) && (layer == 2 ? a.T2 : a.T1) >= 86 && !a.raw && !a.xin8 && !a.gx8 &&
-        (bf3 || bf6 || !(variant & 8))) {
+    const bool inference = !a.raw && !a.xin8 && !a.gx8;
+    const bool fp32 = inference && !bf3 && !bf6;      // fp32 inference: the fast-convolution kernels, and no column padding elsewhere
+
+    TileTable tt;
+    int rc;
+    const int To = layer == 2 ? a.T2 : a.T1;
+    if ((layer == 2 || layer == 3) && To >= 86 && inference) {
         // slab kernels: the tile's distinct input positions held once in LDS (cdae_slab.h); they address a (block, target)'s
         // input through 32-bit float offsets
         for (const CdaeBlockDev& d : Mo->blocks)
             XSQ_REQUIRE((int64_t)4 * CS * a.Bn * a.T1 * d.F1 < ((int64_t)1 << 30), "xsq_cdae_forward: B=%d S=%d overflows the 32-bit "
                         "offsets of a block's activations; split the batch", a.Bn, a.S);
+        const char* name = prof_name ? prof_name : (layer == 2 ? "cdae_l2_slab" : "cdae_l3_slab");      // its own event name: one kernel, one name
         // fp32: Winograd F(2, 4) along the four time taps (cdae_wino.h) -- 5 instead of 8 MFMA products per output pair;
-        // rows of >= 64 pairs, i.e. To >= 127.  xsq_model_set_winograd(0) / XSQ_CDAE_VARIANT=2048: the direct slab kernels.
-        if (!bf3 && !bf6 && a.upool && (Mo->winograd & 1) && !(variant & 2048) && ((layer == 2 ? a.T2 : a.T1) + 1) / 2 >= WN_PAIRS) {
+        // rows of >= 64 pairs, i.e. To >= 127.  xsq_model_set_winograd(0): the direct slab kernels.
+        const bool wino = fp32 && a.upool && (Mo->winograd & 1) && (To + 1) / 2 >= WN_PAIRS;
+        if (wino && (Mo->winograd & 8) && Mo->wino4 && (To + 3) / 4 >= W4_QUADS) {
             // bit 8: F(4, 4) (cdae_wino4.h) -- 7 products per output quad instead of 10; rows of >= 64 quads, i.e. To >= 253
-            if ((Mo->winograd & 8) && Mo->wino4 && ((layer == 2 ? a.T2 : a.T1) + 3) / 4 >= W4_QUADS) {
-                int rcq = get_wino4_tiles(Mo, layer, a.Bn, a.S, &tt);
-                if (rcq) return rcq;
-                XSQ_PROF(prof_name ? prof_name : (layer == 2 ? "cdae_l2_slab" : "cdae_l3_slab"), stream);
-                if (layer == 2) hipLaunchKernelGGL((cdae_wino4_kernel<false>), dim3(tt.ntiles), dim3(512), 0, stream, a, (const WinoTileDev*)tt.d_tiles, tt.ntiles);
-                else hipLaunchKernelGGL((cdae_wino4_kernel<true>), dim3(tt.ntiles), dim3(512), 0, stream, a, (const WinoTileDev*)tt.d_tiles, tt.ntiles);
-                return XSQ_OK;
-            }
-            // XSQ_WINO_MIN_KF (A/B): blocks with fewer frequency taps stay on the direct kernel (their tiles are short: a
-            // prologue per 64 pairs and tap), the Winograd kernel takes the rest
-            static const int min_kf = getenv("XSQ_WINO_MIN_KF") ? atoi(getenv("XSQ_WINO_MIN_KF")) : 0;
-            int rcw = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, min_kf);
-            if (rcw) return rcw;
-            XSQ_PROF(prof_name ? prof_name : (layer == 2 ? "cdae_l2_slab" : "cdae_l3_slab"), stream);
-            if (layer == 2) hipLaunchKernelGGL((cdae_wino_kernel<false>), dim3(tt.ntiles), dim3(256), 0, stream, a, (const WinoTileDev*)tt.d_tiles, tt.ntiles);
-            else hipLaunchKernelGGL((cdae_wino_kernel<true>), dim3(tt.ntiles), dim3(256), 0, stream, a, (const WinoTileDev*)tt.d_tiles, tt.ntiles);
-            if (min_kf > 1) {
-                TileTable ts;
-                if ((rcw = get_slab_tiles(Mo, layer, a.Bn, a.S, &ts, min_kf - 1))) return rcw;
-                if (layer == 2) hipLaunchKernelGGL((cdae_slab_kernel<false, 3, true>), dim3(ts.ntiles), dim3(512), 0, stream, a, (const SlabTileDev*)ts.d_tiles, ts.ntiles);
-                else hipLaunchKernelGGL((cdae_slab_kernel<true, 3, true>), dim3(ts.ntiles), dim3(512), 0, stream, a, (const SlabTileDev*)ts.d_tiles, ts.ntiles);
-            }
-            return XSQ_OK;
+            if ((rc = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, 4))) return rc;
+            XSQ_PROF(name, stream);
+            launch_tiles<WinoTileDev>(layer == 2 ? cdae_wino4_kernel<false> : cdae_wino4_kernel<true>, 512, a, tt, stream);
+        } else if (wino) {
+            if ((rc = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, 2))) return rc;
+            XSQ_PROF(name, stream);
+            launch_tiles<WinoTileDev>(layer == 2 ? cdae_wino_kernel<false> : cdae_wino_kernel<true>, 256, a, tt, stream);
+        } else {
+            if ((rc = get_slab_tiles(Mo, layer, a.Bn, a.S, &tt))) return rc;
+            XSQ_PROF(name, stream);
+            launch_tiles<SlabTileDev>(layer == 2 ? slab_kernel<false>(bf3, bf6) : slab_kernel<true>(bf3, bf6), 512, a, tt, stream);
         }
-        int rc = get_slab_tiles(Mo, layer, a.Bn, a.S, &tt);
-        if (rc) return rc;
-        XSQ_PROF(prof_name ? prof_name : (layer == 2 ? "cdae_l2_slab" : "cdae_l3_slab"), stream);      // its own event name: one kernel, one name
-#define XSQ_SLAB(TR_, MODE_) hipLaunchKernelGGL((cdae_slab_kernel<TR_, MODE_>), dim3(tt.ntiles), dim3(512), 0, stream, a, (const SlabTileDev*)tt.d_tiles, tt.ntiles)
-        const bool exw = !(variant & 64);      // fp32: exact-width columns (MODE 3) unless switched back to MODE 0
-#define XSQ_SLAB_LATE(TR_) hipLaunchKernelGGL((cdae_slab_kernel<TR_, 3, true>), dim3(tt.ntiles), dim3(512), 0, stream, a, (const SlabTileDev*)tt.d_tiles, tt.ntiles)
-        const bool late = !(variant & 512);      // fp32 exact-width kernel: next slab fetched in its own slot (no registers held across the MFMA slots: no scratch)
-        if (layer == 2) { if (bf3) XSQ_SLAB(false, 1); else if (bf6) XSQ_SLAB(false, 2); else if (exw && late) XSQ_SLAB_LATE(false); else if (exw) XSQ_SLAB(false, 3); else XSQ_SLAB(false, 0); }
-        else { if (bf3) XSQ_SLAB(true, 1); else if (bf6) XSQ_SLAB(true, 2); else if (exw && late) XSQ_SLAB_LATE(true); else if (exw) XSQ_SLAB(true, 3); else XSQ_SLAB(true, 0); }
-#undef XSQ_SLAB_LATE
-#undef XSQ_SLAB
         return XSQ_OK;
     }
-    if (layer == 1 && !bf3 && !bf6 && !a.raw && !a.xin8 && !a.gx8 && !a.causal && a.upool && (Mo->winograd & 2)) {
+    if (layer == 1 && fp32 && !a.causal && a.upool && (Mo->winograd & 2)) {
         // fp32 inference, non-causal: F(2, 2) along the hop (cdae_l1f.h) -- three half-window products per output pair
         // instead of four.  xsq_model_set_winograd without bit 2: the implicit GEMM below.
-        int rcf = get_l1f_tiles(Mo, a.Bn, a.S, &tt);
-        if (rcf) return rcf;
+        if ((rc = get_l1f_tiles(Mo, a.Bn, a.S, &tt))) return rc;
         XSQ_PROF(prof_name ? prof_name : "cdae_l1_gemm", stream);
-        hipLaunchKernelGGL(cdae_l1f_kernel, dim3(tt.ntiles), dim3(256), 0, stream, a, (const L1fTileDev*)tt.d_tiles, tt.ntiles);
+        launch_tiles<L1fTileDev>(cdae_l1f_kernel, 256, a, tt, stream);
         return XSQ_OK;
     }
     bool l4f_fits = true;            // cdae_l4f.h runs several frequency taps only on column tiles of <= 32 columns
     for (const CdaeBlockDev& d : Mo->blocks) l4f_fits = l4f_fits && (d.kf == 1 || d.T <= 32);
-    if (layer == 4 && l4f_fits && !bf3 && !bf6 && !a.raw && !a.xin8 && !a.gx8 && !a.causal && (a.Y || a.masks) && a.upool && (Mo->winograd & 4)) {
+    if (layer == 4 && l4f_fits && fp32 && !a.causal && (a.Y || a.masks) && a.upool && (Mo->winograd & 4)) {
         // fp32 inference, non-causal: F(2, 2) along the hop (cdae_l4f.h) -- masks only (the separator's path) or with the
         // estimates materialised (the module API): one kernel, the same masks bit for bit
         for (const CdaeBlockDev& d : Mo->blocks)
             XSQ_REQUIRE((int64_t)8 * 2 * a.Bn * d.F * a.S * d.T < ((int64_t)1 << 31) && (int64_t)a.Bn * 2 * a.S * d.cum < ((int64_t)1 << 31),
                         "xsq_cdae_forward: B=%d S=%d overflows the 32-bit offsets of a block's coefficients; split the batch", a.Bn, a.S);
-        int rcf = get_l4f_tiles(Mo, a.Bn, a.S, &tt);
-        if (rcf) return rcf;
-        TileTable t2;
-        if ((rcf = get_l4f_tiles(Mo, a.Bn, a.S, &t2, 1))) return rcf;
+        if ((rc = get_l4f_tiles(Mo, a.Bn, a.S, &tt))) return rc;
         XSQ_PROF(prof_name ? prof_name : "cdae_l4_gemm", stream);
-        if (t2.ntiles) {           // the multi-tap blocks first (the longest tiles of the layer)
-            if (a.Y) hipLaunchKernelGGL(cdae_l4f_taps_kernel<true>, dim3(t2.ntiles), dim3(256), 0, stream, a, (const L4fTileDev*)t2.d_tiles, t2.ntiles);
-            else hipLaunchKernelGGL(cdae_l4f_taps_kernel<false>, dim3(t2.ntiles), dim3(256), 0, stream, a, (const L4fTileDev*)t2.d_tiles, t2.ntiles);
-        }
-        if (tt.ntiles) {
-            if (a.Y) hipLaunchKernelGGL(cdae_l4f_kernel<true>, dim3(tt.ntiles), dim3(256), 0, stream, a, (const L4fTileDev*)tt.d_tiles, tt.ntiles);
-            else hipLaunchKernelGGL(cdae_l4f_kernel<false>, dim3(tt.ntiles), dim3(256), 0, stream, a, (const L4fTileDev*)tt.d_tiles, tt.ntiles);
-        }
+        launch_tiles<L4fTileDev>(a.Y ? cdae_l4f_kernel<true> : cdae_l4f_kernel<false>, 256, a, tt, stream);
         return XSQ_OK;
     }
-    const bool n16 = !bf3 && !bf6 && layer == 4 && !a.raw && !a.xin8 && !a.gx8 && !(variant & 256);      // fp32 inference: 16-column granularity
-    const bool tgt_outer = layer == 4 && !a.Y && !a.gx8;        // masks only (the separator's path, also with Wiener-EM from the masks)
-    int rc = get_cdae_tiles(Mo, layer, a.Bn, a.S, &tt, mt23, n16, tgt_outer);
-    if (rc) return rc;
-#define XSQ_LAUNCH(OP, MT_, XW_)                                                                                    \
+    // the implicit GEMMs.  Layers 2 / 3 on 128-row tiles: 256-row tiles (MT = 2) measured slower: 192 VGPR -> 2 waves per SIMD
+    // (L3 1.51 -> 1.74 ms)
+    const bool n16 = fp32 && layer == 4;                        // fp32 inference: 16-column granularity
+    const bool tgt_outer = layer == 4 && !a.Y;                  // masks only (the separator's path, also with Wiener-EM from the masks)
+    if ((rc = get_cdae_tiles(Mo, layer, a.Bn, a.S, &tt, n16, tgt_outer))) return rc;
+    // XW_: the exact-width form of the fp32 engine that fp32 inference runs (gemm_tile.h: 1 = layers 1 to 3, 2 = layer 4)
+#define XSQ_LAUNCH(OP, XW_)                                                                                         \
     do {                                                                                                            \
         if (bf1) hipLaunchKernelGGL((grouped_gemm_bf6_kernel<OP, true>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);      \
-        else if (bf6) hipLaunchKernelGGL((grouped_gemm_bf6_kernel<OP>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);      \
-        else if (!bf3 && xw) hipLaunchKernelGGL((grouped_gemm_kernel<OP, 1, XW_>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles); \
-        else if (!bf3) hipLaunchKernelGGL((grouped_gemm_kernel<OP, MT_>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);         \
-        else if (variant & 2) hipLaunchKernelGGL((grouped_gemm_bf3_kernel<OP, MT_, 2>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles); \
-        else hipLaunchKernelGGL((grouped_gemm_bf3_kernel<OP, MT_, 1>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles); \
+        else if (bf6) hipLaunchKernelGGL((grouped_gemm_bf6_kernel<OP>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);       \
+        else if (bf3) hipLaunchKernelGGL((grouped_gemm_bf3_kernel<OP>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);       \
+        else if (fp32) hipLaunchKernelGGL((grouped_gemm_kernel<OP, 1, XW_>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);  \
+        else hipLaunchKernelGGL((grouped_gemm_kernel<OP>), dim3(tt.ntiles), dim3(256), 0, stream, OP{a}, tt.d_tiles, tt.ntiles);                    \
     } while (0)
     switch (layer) {
-        case 1: { XSQ_PROF(prof_name ? prof_name : "cdae_l1_gemm", stream); if (a.causal) XSQ_LAUNCH(CdaeL1CausalOp, 1, 1); else XSQ_LAUNCH(CdaeL1Op, 1, 1); } break;
-        case 2: { XSQ_PROF(prof_name ? prof_name : "cdae_l2_gemm", stream); if (mt23 == 2) XSQ_LAUNCH(CdaeL2Op, 2, 0); else XSQ_LAUNCH(CdaeL2Op, 1, 1); } break;
-        case 3: { XSQ_PROF(prof_name ? prof_name : "cdae_l3_gemm", stream); if (mt23 == 2) XSQ_LAUNCH(CdaeL3Op, 2, 0); else XSQ_LAUNCH(CdaeL3Op, 1, 1); } break;
-        default: { XSQ_PROF(prof_name ? prof_name : "cdae_l4_gemm", stream);
-            if (n16) hipLaunchKernelGGL((grouped_gemm_kernel<CdaeL4Op, 1, 2>), dim3(tt.ntiles), dim3(256), 0, stream, CdaeL4Op{a}, tt.d_tiles, tt.ntiles);
-            else XSQ_LAUNCH(CdaeL4Op, 1, 0); } break;
+        case 1: { XSQ_PROF(prof_name ? prof_name : "cdae_l1_gemm", stream); if (a.causal) XSQ_LAUNCH(CdaeL1CausalOp, 1); else XSQ_LAUNCH(CdaeL1Op, 1); } break;
+        case 2: { XSQ_PROF(prof_name ? prof_name : "cdae_l2_gemm", stream); XSQ_LAUNCH(CdaeL2Op, 1); } break;
+        case 3: { XSQ_PROF(prof_name ? prof_name : "cdae_l3_gemm", stream); XSQ_LAUNCH(CdaeL3Op, 1); } break;
+        default: { XSQ_PROF(prof_name ? prof_name : "cdae_l4_gemm", stream); XSQ_LAUNCH(CdaeL4Op, 2); } break;
     }
 #undef XSQ_LAUNCH
     return XSQ_OK;

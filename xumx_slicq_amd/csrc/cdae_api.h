@@ -53,7 +53,7 @@ struct xsq_model {
     int64_t* d_cum = nullptr;      // (nblocks+1) cumulative F*T, for the elementwise kernels
     int* d_blockF = nullptr;       // (nblocks)
     std::mutex mu;
-    std::map<std::tuple<int, int, int>, xsq::TileTable> tiles;   // (layer, B, S)
+    std::map<xsq::TileKey, xsq::TileTable> tiles;
 };
 
 namespace xsq {

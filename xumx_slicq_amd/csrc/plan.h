@@ -1,5 +1,6 @@
 // Host-side plan object behind the C ABI (include/xumx_slicq_hip.h).
 #pragma once
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -18,9 +19,52 @@ struct FftPlan {
 };
 
 struct TileTable {
-    TileDev* d_tiles = nullptr;
+    TileDev* d_tiles = nullptr;     // (entries of the builder's own type: cast at the launch sites)
     int ntiles = 0;
 };
+
+// Key of a cached tile table: the builder, the call shape and the builder's own parameters, each in a field of its own --
+// two builders, or two parameter sets of one builder, cannot meet in one key.
+enum class TileKind { BandGemm, Dft4Full, CdaeGemm, CdaeSlab, CdaeWino, CdaeL1f, CdaeL4f };
+struct TileKey {
+    TileKind kind;
+    int rows, S;        // call shape: rows of the transform (S = `share`) / batch items and slices of the CDAE
+    int sub, flags;     // which table of the builder (CDAE layer, band class) / its switches, named at the builder
+    bool operator<(const TileKey& o) const {
+        return std::tie(kind, rows, S, sub, flags) < std::tie(o.kind, o.rows, o.S, o.sub, o.flags);
+    }
+};
+
+// The table of `key` from the owner's cache, or built by fill(std::vector<T>&), uploaded and inserted.  An empty table has no
+// allocation (d_tiles null, ntiles 0); a failed copy frees what it allocated.
+template <class T, class Fill>
+static int cached_tiles(std::mutex& mu, std::map<TileKey, TileTable>& cache, const TileKey& key, TileTable* out, Fill&& fill) {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) { *out = it->second; return XSQ_OK; }
+    std::vector<T> t;
+    fill(t);
+    TileTable tt;
+    tt.ntiles = (int)t.size();
+    if (!t.empty()) {
+        XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(T)));
+        const hipError_t e = hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(tt.d_tiles);
+        XSQ_HIP(e);
+    }
+    cache[key] = tt;
+    *out = tt;
+    return XSQ_OK;
+}
+
+// the indices 0 .. n - 1 ordered by key(i), descending, stable (longest tiles first: a launch ends on short tiles)
+template <class KeyFn>
+static std::vector<int> order_descending(int n, KeyFn key) {
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key(x) > key(y); });
+    return order;
+}
 
 struct BlockHost {
     int first_band, F, T;
@@ -66,5 +110,5 @@ struct xsq_plan {
     // caches keyed by the call shape
     std::mutex mu;
     std::map<std::pair<int, int>, xsq::FftPlan> fft;              // (direction, batch)
-    std::map<std::tuple<int, int, int>, xsq::TileTable> tiles;   // (kind, rows, 0)
+    std::map<xsq::TileKey, xsq::TileTable> tiles;
 };

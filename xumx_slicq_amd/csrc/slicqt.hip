@@ -287,36 +287,18 @@ __global__ __launch_bounds__(256) void k_remix_combine(RemixArgs a) {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static int upload_tiles(const std::vector<TileDev>& t, TileTable* tt) {
-    tt->ntiles = (int)t.size();
-    tt->d_tiles = nullptr;
-    if (t.empty()) return XSQ_OK;
-    XSQ_HIP(hipMalloc(&tt->d_tiles, t.size() * sizeof(TileDev)));
-    XSQ_HIP(hipMemcpy(tt->d_tiles, t.data(), t.size() * sizeof(TileDev), hipMemcpyHostToDevice));
-    return XSQ_OK;
-}
-
 // dense-GEMM tiles: all bands, or only the short ones when the radix-4 kernel takes the rest
 static int get_band_tiles(xsq_plan* P, int rows, TileTable* out) {
-    std::lock_guard<std::mutex> lk(P->mu);
     const bool r4 = P->band_radix4 && P->nbands4 > 0;
-    auto key = std::make_tuple(r4 ? 2 : 0, rows, 0);
-    auto it = P->tiles.find(key);
-    if (it != P->tiles.end()) { *out = it->second; return XSQ_OK; }
-    std::vector<TileDev> t;
-    // longest tiles first (K = 2*Lg grows along the band table): the launch ends on short tiles
-    if (r4) {
-        for (int i = (int)P->bands4_small.size() - 1; i >= 0; --i)
-            push_group_tiles(t, P->bands4_small[i], rows, 2 * P->bands[P->bands4_small[i]].Lg);
-    } else {
-        for (int j = P->nbands - 1; j >= 0; --j) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg);
-    }
-    TileTable tt;
-    int rc = upload_tiles(t, &tt);
-    if (rc) return rc;
-    P->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    return cached_tiles<TileDev>(P->mu, P->tiles, TileKey{TileKind::BandGemm, rows, 0, 0, r4 ? 1 : 0}, out, [&](std::vector<TileDev>& t) {
+        // longest tiles first (K = 2*Lg grows along the band table): the launch ends on short tiles
+        if (r4) {
+            for (int i = (int)P->bands4_small.size() - 1; i >= 0; --i)
+                push_group_tiles(t, P->bands4_small[i], rows, 2 * P->bands[P->bands4_small[i]].Lg);
+        } else {
+            for (int j = P->nbands - 1; j >= 0; --j) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg);
+        }
+    });
 }
 
 // tiles of the radix-4 kernel (band_dft4_full_kernel): 32 rows x every column of the band; TileDev.narrow = number of
@@ -328,29 +310,17 @@ static int get_band_tiles(xsq_plan* P, int rows, TileTable* out) {
 // cls: 0 = every band (one launch of the 10-block kernel), 1 = bands of more than 5 blocks, 2 = bands of at most 5 blocks
 // (their own instantiation: four workgroups per CU, band_dft4.h)
 static int get_dft4_full_tiles(xsq_plan* P, int rows, TileTable* out, int share = 0, int cls = 0, bool sym = false) {
-    std::lock_guard<std::mutex> lk(P->mu);
-    auto key = std::make_tuple(3 + 16 * cls + (sym ? 256 : 0), rows, share);
-    auto it = P->tiles.find(key);
-    if (it != P->tiles.end()) { *out = it->second; return XSQ_OK; }
-    std::vector<Tile4Dev> t;
-    const Band4Dev* b4 = reinterpret_cast<const Band4Dev*>(P->bands4_host.data());
-    const int span = share > 0 ? share : rows, copies = share > 0 ? rows / share : 1;
-    for (int i = P->nbands4 - 1; i >= 0; --i) {
-        int ncb = (2 * P->bands4_m[i] + 15) / 16;
-        if ((cls == 1 && ncb <= 5) || (cls == 2 && ncb > 5)) continue;
-        if (sym) ncb = (P->bands4_m[i] / 2 + 1 + 15) / 16;        // band_dft4s.h: blocks of the outputs k = 0 .. m / 2
-        for (int m0 = 0; m0 < span; m0 += D4H_ROWS)
-            for (int k = 0; k < copies; ++k) t.push_back(Tile4Dev{m0 + k * span, ncb, b4[i]});
-    }
-    TileTable tt;                     // (d_tiles holds Tile4Dev entries for this key: cast at the launch sites)
-    tt.ntiles = (int)t.size();
-    if (!t.empty()) {
-        XSQ_HIP(hipMalloc(&tt.d_tiles, t.size() * sizeof(Tile4Dev)));
-        XSQ_HIP(hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(Tile4Dev), hipMemcpyHostToDevice));
-    }
-    P->tiles[key] = tt;
-    *out = tt;
-    return XSQ_OK;
+    return cached_tiles<Tile4Dev>(P->mu, P->tiles, TileKey{TileKind::Dft4Full, rows, share, cls, sym ? 1 : 0}, out, [&](std::vector<Tile4Dev>& t) {
+        const Band4Dev* b4 = reinterpret_cast<const Band4Dev*>(P->bands4_host.data());
+        const int span = share > 0 ? share : rows, copies = share > 0 ? rows / share : 1;
+        for (int i = P->nbands4 - 1; i >= 0; --i) {
+            int ncb = (2 * P->bands4_m[i] + 15) / 16;
+            if ((cls == 1 && ncb <= 5) || (cls == 2 && ncb > 5)) continue;
+            if (sym) ncb = (P->bands4_m[i] / 2 + 1 + 15) / 16;        // band_dft4s.h: blocks of the outputs k = 0 .. m / 2
+            for (int m0 = 0; m0 < span; m0 += D4H_ROWS)
+                for (int k = 0; k < copies; ++k) t.push_back(Tile4Dev{m0 + k * span, ncb, b4[i]});
+        }
+    });
 }
 
 // The radix-4 band kernel reaches operands and results through buffer descriptors per band block / tile with 32-bit byte
