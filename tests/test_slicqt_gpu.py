@@ -208,9 +208,13 @@ def test_packed_butterflies_are_a_diagnostic_build_only(fb):
         eng.set_packed_fft(False)
 
 
-def test_complex_product_band_kernel_arm_agrees_with_the_default(fb, tmp_path):
-    """XSQ_D4_SYM=0 keeps the complex-product radix-4 kernel (csrc/band_dft4.h) as an A/B arm beside the default pair-contracted
-    form (csrc/band_dft4s.h, a quarter of the matrix work).  The switch is read once per process: the arm runs in a child."""
+@pytest.mark.parametrize("arm_env", [{"XSQ_D4_SYM": "0"}, {"XSQ_D4_MIN_LG": "48"}], ids=["XSQ_D4_SYM=0", "XSQ_D4_MIN_LG=48"])
+def test_complex_product_band_kernel_arm_agrees_with_the_default(fb, tmp_path, arm_env):
+    """The two process switches of the transform (csrc/slicqt.hip, Switches), each against the default.  XSQ_D4_SYM=0 keeps the
+    complex-product radix-4 kernel (csrc/band_dft4.h) as an A/B arm beside the default pair-contracted form (csrc/band_dft4s.h, a
+    quarter of the matrix work).  XSQ_D4_MIN_LG=48 moves the bands with 24 <= Lg < 48 from the radix-4 kernel to the dense engine:
+    test_radix4_band_kernel_matches_dense_gemm holds ALL bands on the dense engine to the same bounds, and this arm moves a subset.
+    The switches are read once per process: the arm runs in a child."""
     import os
     import subprocess
     import sys
@@ -227,7 +231,7 @@ def test_complex_product_band_kernel_arm_agrees_with_the_default(fb, tmp_path):
             "base = NSGTBase('bark', 262, 32.9, device='cuda'); enc, dec = make_filterbanks(base)\n"
             "x = synth_audio(%d, seed=31, nb_samples=1).cuda(); C = enc(x); y = dec([c.clone() for c in C], %d)\n"
             "torch.save({'C': [c.cpu() for c in C], 'y': y.cpu()}, %r)\n" % (ROOT, n, n, str(out)))
-    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, XSQ_D4_SYM="0"), timeout=600, capture_output=True)
+    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, **arm_env), timeout=600, capture_output=True)
     arm = torch.load(out)
     for i in range(70):
         assert float((C[i].cpu() - arm["C"][i]).abs().max()) < 1e-4, i

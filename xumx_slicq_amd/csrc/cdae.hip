@@ -764,8 +764,6 @@ static int get_l4f_tiles(xsq_model* Mo, int Bn, int S, TileTable* out) {
     });
 }
 
-static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace xsq
 
 using namespace xsq;
@@ -965,20 +963,14 @@ static int model_build(xsq_model** out, int nblocks, const int32_t* F, const int
         set_error("xsq_model_create: internal parameter walk mismatch");
         return XSQ_ERR_ARG;
     }
-#define UP(dst, vec, T)                                                                           \
-    do {                                                                                          \
-        XSQ_HIP(hipMalloc(&(dst), (vec).size() * sizeof(T)));                                     \
-        XSQ_HIP(hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(T), hipMemcpyHostToDevice)); \
-    } while (0)
-    UP(Mo->d_pool, pool, float);
-    UP(Mo->d_upool, upool, float);
+    if (int rc = upload(Mo->d_pool, pool)) return rc;
+    if (int rc = upload(Mo->d_upool, upool)) return rc;
     Mo->pool_floats = (int64_t)pool.size();
-    UP(Mo->d_mean, mean, float);
-    UP(Mo->d_scale, scale, float);
-    UP(Mo->d_blocks, Mo->blocks, CdaeBlockDev);
-    UP(Mo->d_cum, cum, int64_t);
-    UP(Mo->d_blockF, blockF, int);
-#undef UP
+    if (int rc = upload(Mo->d_mean, mean)) return rc;
+    if (int rc = upload(Mo->d_scale, scale)) return rc;
+    if (int rc = upload(Mo->d_blocks, Mo->blocks)) return rc;
+    if (int rc = upload(Mo->d_cum, cum)) return rc;
+    if (int rc = upload(Mo->d_blockF, blockF)) return rc;
     *partial = nullptr;
     *out = Mo;
     return XSQ_OK;
@@ -1034,8 +1026,8 @@ int xsq_model_destroy(xsq_model* Mo) {
 size_t xsq_cdae_workspace(const xsq_model* Mo, int Bn, int S) {
     if (!Mo || Bn <= 0 || S < 3) return 0;
     const int64_t T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    return al((size_t)Bn * 2 * S * Mo->sumFT * 4) + 2 * al((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4) +
-           al((size_t)CS * Bn * T2 * 4 * Mo->sumF2 * 4) + 256;
+    return al256((size_t)Bn * 2 * S * Mo->sumFT * 4) + 2 * al256((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4) +
+           al256((size_t)CS * Bn * T2 * 4 * Mo->sumF2 * 4) + 256;
 }
 
 }  // extern "C"
@@ -1209,9 +1201,9 @@ int xsq_cdae_forward_xin(xsq_model* Mo, const float* X, int Bn, int S, float* Y,
     hipStream_t stream = (hipStream_t)stream_;
     const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
     char* w = (char*)ws;
-    float* xin = (float*)w;  w += al((size_t)Bn * 2 * S * Mo->sumFT * 4);
-    float* act1 = (float*)w; w += al((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4);
-    float* act3 = (float*)w; w += al((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4);
+    float* xin = (float*)w;  w += al256((size_t)Bn * 2 * S * Mo->sumFT * 4);
+    float* act1 = (float*)w; w += al256((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4);
+    float* act3 = (float*)w; w += al256((size_t)CS * Bn * T1 * 4 * Mo->sumF1 * 4);
     float* act2 = (float*)w;
     const int split = Mo->precision == 1 ? 1 : 0;
     if (!xin_ready) cdae_launch_magnitude(Mo, X, xin, Mo->d_mean, Mo->d_scale, Bn, S, stream, split);

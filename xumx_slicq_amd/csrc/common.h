@@ -33,6 +33,8 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+// byte counts of workspace regions: every region starts on a 256-byte boundary
+static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 // Sixteen zero bytes in device memory: an out-of-range operand load can be pointed here instead of being
 // branched around (used by the band operators of slicqt.hip, whose loads must stay unpredicated next to the

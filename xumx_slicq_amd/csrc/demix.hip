@@ -50,8 +50,6 @@ struct ForwardPlan {
     size_t ext_floats = 0;           // window-maximum tables of the split sets (zeroed at the start of every call)
 };
 
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace
 
 struct xsq_demixer {

@@ -145,12 +145,13 @@ static int loss_tables(int nblocks, const int32_t* F, const int32_t* T, int Bn, 
     first[nblocks] = (int)work.size();
     LossTables t;
     t.nwork = (int)work.size();
-    XSQ_HIP(hipMalloc(&t.d_work, work.size() * sizeof(LossWork)));
-    XSQ_HIP(hipMemcpy(t.d_work, work.data(), work.size() * sizeof(LossWork), hipMemcpyHostToDevice));
-    XSQ_HIP(hipMalloc(&t.d_inv, inv.size() * sizeof(double)));
-    XSQ_HIP(hipMemcpy(t.d_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
-    XSQ_HIP(hipMalloc(&t.d_first, first.size() * sizeof(int)));
-    XSQ_HIP(hipMemcpy(t.d_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+    int rc = upload(t.d_work, work);
+    if (!rc) rc = upload(t.d_inv, inv);
+    if (!rc) rc = upload(t.d_first, first);
+    if (rc) {       // not in the cache yet: nothing else would free what this call allocated
+        (void)hipFree(t.d_work); (void)hipFree(t.d_inv); (void)hipFree(t.d_first);
+        return rc;
+    }
     g_loss_tables[key] = t;
     *out = t;
     return XSQ_OK;

@@ -29,14 +29,29 @@ enum class TileKind { BandGemm, Dft4Full, CdaeGemm, CdaeSlab, CdaeWino, CdaeL1f,
 struct TileKey {
     TileKind kind;
     int rows, S;        // call shape: rows of the transform (S = `share`) / batch items and slices of the CDAE
-    int sub, flags;     // which table of the builder (CDAE layer, band class) / its switches, named at the builder
+    int sub, flags;     // which table of the builder (CDAE layer) / its switches, named at the builder
     bool operator<(const TileKey& o) const {
         return std::tie(kind, rows, S, sub, flags) < std::tie(o.kind, o.rows, o.S, o.sub, o.flags);
     }
 };
 
+// `count` elements at src -> a fresh device allocation at dst.  No elements: dst stays null and the call succeeds; a failed copy
+// frees what it allocated and leaves dst null.  (dst may be declared with another element type than T, or as void*.)
+template <class D, class T>
+static int upload(D*& dst, const T* src, size_t count) {
+    dst = nullptr;
+    if (!count) return XSQ_OK;
+    XSQ_HIP(hipMalloc((void**)&dst, count * sizeof(T)));
+    const hipError_t e = hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dst); dst = nullptr; }
+    XSQ_HIP(e);
+    return XSQ_OK;
+}
+template <class D, class T>
+static int upload(D*& dst, const std::vector<T>& vec) { return upload(dst, vec.data(), vec.size()); }
+
 // The table of `key` from the owner's cache, or built by fill(std::vector<T>&), uploaded and inserted.  An empty table has no
-// allocation (d_tiles null, ntiles 0); a failed copy frees what it allocated.
+// allocation (d_tiles null, ntiles 0).
 template <class T, class Fill>
 static int cached_tiles(std::mutex& mu, std::map<TileKey, TileTable>& cache, const TileKey& key, TileTable* out, Fill&& fill) {
     std::lock_guard<std::mutex> lk(mu);
@@ -46,12 +61,7 @@ static int cached_tiles(std::mutex& mu, std::map<TileKey, TileTable>& cache, con
     fill(t);
     TileTable tt;
     tt.ntiles = (int)t.size();
-    if (!t.empty()) {
-        XSQ_HIP(hipMalloc((void**)&tt.d_tiles, t.size() * sizeof(T)));
-        const hipError_t e = hipMemcpy(tt.d_tiles, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(tt.d_tiles);
-        XSQ_HIP(e);
-    }
+    if (int rc = upload(tt.d_tiles, t)) return rc;
     cache[key] = tt;
     *out = tt;
     return XSQ_OK;

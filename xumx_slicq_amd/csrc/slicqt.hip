@@ -301,21 +301,40 @@ static int get_band_tiles(xsq_plan* P, int rows, TileTable* out) {
     });
 }
 
-// tiles of the radix-4 kernel (band_dft4_full_kernel): 32 rows x every column of the band; TileDev.narrow = number of
-// 16-column blocks.
+// Bands at least this long take the radix-4 kernel, shorter ones the dense engine.  Measured with the full-width kernel
+// (r03o, sum of the four band kernels): 64 -> 1.53 ms, 48 -> 1.485, 32 -> 1.49, 16 -> 1.53; again with the buffer-addressed
+// kernel (r4f, four full chunks): 48 -> 1.285 ms, 40 -> 1.272, 32 -> 1.280, 24 -> 1.252, 16 -> 1.304.
+#ifndef XSQ_D4_MIN_LG_DEFAULT
+#define XSQ_D4_MIN_LG_DEFAULT 24
+#endif
+
+// Process switches, read once (a function-local static: initialised under the language's lock).
+//   XSQ_D4_SYM=0      the complex-product radix-4 kernel (band_dft4.h) instead of the pair-contracted default (band_dft4s.h);
+//                     tests/test_slicqt_gpu.py holds the two arms together
+//   XSQ_D4_MIN_LG=n   bands at least n (>= 16) long take the radix-4 kernel, shorter ones the dense engine: the split point
+//                     behind XSQ_D4_MIN_LG_DEFAULT, which bench.py reads for its flop split
+struct Switches {
+    bool d4_sym = true;
+    int d4_min_lg = XSQ_D4_MIN_LG_DEFAULT;
+    Switches() {
+        if (const char* e = getenv("XSQ_D4_SYM")) d4_sym = atoi(e) != 0;
+        if (const char* e = getenv("XSQ_D4_MIN_LG")) d4_min_lg = atoi(e) >= 16 ? atoi(e) : d4_min_lg;
+    }
+};
+static const Switches& switches() { static const Switches sw; return sw; }
+
+// tiles of the radix-4 kernels: 32 rows x every column of the band; TileDev.narrow = number of 16-column blocks -- of the
+// band's 2m columns (band_dft4.h), or with `sym` of its outputs k = 0 .. m / 2 (band_dft4s.h).
 // `share` > 0 (masked synthesis): rows r and r + share, r + 2*share, ... read the same mix rows (the targets of one
 // (sample, channel, slice)); their tiles are made neighbours so the mix is fetched once per XCD.  When share is not a
 // multiple of the tile height the last tile of a copy runs into the next copy's first rows and recomputes them
 // (same values, written twice).
-// cls: 0 = every band (one launch of the 10-block kernel), 1 = bands of more than 5 blocks, 2 = bands of at most 5 blocks
-// (their own instantiation: four workgroups per CU, band_dft4.h)
-static int get_dft4_full_tiles(xsq_plan* P, int rows, TileTable* out, int share = 0, int cls = 0, bool sym = false) {
-    return cached_tiles<Tile4Dev>(P->mu, P->tiles, TileKey{TileKind::Dft4Full, rows, share, cls, sym ? 1 : 0}, out, [&](std::vector<Tile4Dev>& t) {
+static int get_dft4_full_tiles(xsq_plan* P, int rows, TileTable* out, int share, bool sym) {
+    return cached_tiles<Tile4Dev>(P->mu, P->tiles, TileKey{TileKind::Dft4Full, rows, share, 0, sym ? 1 : 0}, out, [&](std::vector<Tile4Dev>& t) {
         const Band4Dev* b4 = reinterpret_cast<const Band4Dev*>(P->bands4_host.data());
         const int span = share > 0 ? share : rows, copies = share > 0 ? rows / share : 1;
         for (int i = P->nbands4 - 1; i >= 0; --i) {
             int ncb = (2 * P->bands4_m[i] + 15) / 16;
-            if ((cls == 1 && ncb <= 5) || (cls == 2 && ncb > 5)) continue;
             if (sym) ncb = (P->bands4_m[i] / 2 + 1 + 15) / 16;        // band_dft4s.h: blocks of the outputs k = 0 .. m / 2
             for (int m0 = 0; m0 < span; m0 += D4H_ROWS)
                 for (int k = 0; k < copies; ++k) t.push_back(Tile4Dev{m0 + k * span, ncb, b4[i]});
@@ -334,44 +353,19 @@ static int d4_ranges_ok(const xsq_plan* P, int64_t rows, const char* who) {
     return XSQ_OK;
 }
 
-// the radix-4 band kernel over every eligible band, one launch of the 10-block instantiation (three workgroups per CU).
-// XSQ_D4_SPLIT=1 (A/B switch, measured no faster: synthesis 0.940-0.948 vs 0.916-0.945 ms, analysis 0.309-0.316 vs
-// 0.291-0.301): the bands of at most five 16-column blocks in their own instantiation -- 35 KB of LDS, 96 registers,
-// four workgroups per CU -- launched behind the wide ones.
+// The radix-4 band kernel over every eligible band, in one launch: the pair-contracted form (band_dft4s.h), or with
+// XSQ_D4_SYM=0 the complex-product form (band_dft4.h) in its 10-block instantiation (three workgroups per CU).  A masked
+// synthesis takes the instantiation that multiplies the mask in.
 template <bool FWD>
 static int launch_dft4(xsq_plan* P, const Band4Args& a4, int rows, int share, hipStream_t stream) {
-    static const bool split = getenv("XSQ_D4_SPLIT") && atoi(getenv("XSQ_D4_SPLIT")) == 1;
-    // the pair-contracted form (band_dft4s.h) is the default; XSQ_D4_SYM=0 runs the complex-product form (band_dft4.h)
-    static const bool sym = !(getenv("XSQ_D4_SYM") && atoi(getenv("XSQ_D4_SYM")) == 0);
+    const bool sym = switches().d4_sym;
     const bool masked = !FWD && a4.mask != nullptr;
     TileTable t;
-    int rc;
-    if (sym) {
-        if ((rc = get_dft4_full_tiles(P, rows, &t, share, 0, true))) return rc;
-        if (!t.ntiles) return XSQ_OK;
-        if constexpr (!FWD) {
-            if (masked) { hipLaunchKernelGGL((band_dft4s_kernel<false, true>), dim3(t.ntiles), dim3(256), 0, stream, a4, (const Tile4Dev*)t.d_tiles, t.ntiles); return XSQ_OK; }
-        }
-        hipLaunchKernelGGL((band_dft4s_kernel<FWD, false>), dim3(t.ntiles), dim3(256), 0, stream, a4, (const Tile4Dev*)t.d_tiles, t.ntiles);
-        return XSQ_OK;
-    }
-    auto launch = [&](auto ncbmax) {
-        constexpr int N = decltype(ncbmax)::value;
-        if (!t.ntiles) return;
-        if constexpr (!FWD) {
-            if (masked) { hipLaunchKernelGGL((band_dft4_full_kernel<false, N, true>), dim3(t.ntiles), dim3(D4H_NT), 0, stream, a4, (const Tile4Dev*)t.d_tiles, t.ntiles); return; }
-        }
-        hipLaunchKernelGGL((band_dft4_full_kernel<FWD, N, false>), dim3(t.ntiles), dim3(D4H_NT), 0, stream, a4, (const Tile4Dev*)t.d_tiles, t.ntiles);
-    };
-    if (!split) {
-        if ((rc = get_dft4_full_tiles(P, rows, &t, share, 0))) return rc;
-        launch(std::integral_constant<int, 10>{});
-        return XSQ_OK;
-    }
-    if ((rc = get_dft4_full_tiles(P, rows, &t, share, 1))) return rc;
-    launch(std::integral_constant<int, 10>{});
-    if ((rc = get_dft4_full_tiles(P, rows, &t, share, 2))) return rc;
-    launch(std::integral_constant<int, 5>{});
+    if (int rc = get_dft4_full_tiles(P, rows, &t, share, sym)) return rc;
+    if (!t.ntiles) return XSQ_OK;
+    auto kernel = masked ? band_dft4s_kernel<false, true> : band_dft4s_kernel<FWD, false>;
+    if (!sym) kernel = masked ? band_dft4_full_kernel<false, 10, true> : band_dft4_full_kernel<FWD, 10, false>;
+    hipLaunchKernelGGL(kernel, dim3(t.ntiles), dim3(sym ? 256 : D4H_NT), 0, stream, a4, (const Tile4Dev*)t.d_tiles, t.ntiles);
     return XSQ_OK;
 }
 
@@ -426,36 +420,383 @@ static int run_fft(const FftPlan& f, void* in, void* out, void* work, hipStream_
     return XSQ_OK;
 }
 
-static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
-// Bands at least this long take the radix-4 kernel, shorter ones the dense engine.  Measured with the full-width kernel
-// (r03o, sum of the four band kernels): 64 -> 1.53 ms, 48 -> 1.485, 32 -> 1.49, 16 -> 1.53; again with the buffer-addressed
-// kernel (r4f, four full chunks): 48 -> 1.285 ms, 40 -> 1.272, 32 -> 1.280, 24 -> 1.252, 16 -> 1.304.
-#ifndef XSQ_D4_MIN_LG_DEFAULT
-#define XSQ_D4_MIN_LG_DEFAULT 24
-#endif
-#ifndef XSQ_FFT_NT_FWD
-#define XSQ_FFT_NT_FWD 512
-#endif
-#ifndef XSQ_FFT_NT_INV
-#define XSQ_FFT_NT_INV 512
-#endif
-
-// threads per row of the slice FFT kernels (slice_fft.h): XSQ_FFT_THREADS = "fwd,inv" of 256 / 512 overrides the
-// defaults (diagnostic A/B switch; same results bit for bit)
-static int fft_threads(int inverse) {
-    static int u[2] = {-1, -1};
-    if (u[0] < 0) {
-        int f = XSQ_FFT_NT_FWD, i = XSQ_FFT_NT_INV;
-        if (const char* e = getenv("XSQ_FFT_THREADS")) { if (sscanf(e, "%d,%d", &f, &i) < 2) i = f; }
-        u[0] = f == 512 ? 512 : 256; u[1] = i == 512 ? 512 : 256;
-    }
-    return u[inverse ? 1 : 0];
-}
-
 static inline bool lds_fft(const xsq_plan* P) { return P->fft_backend == 0 && P->L == FFT_L && P->d_tgt != nullptr; }
 static inline FftTables fft_tables(const xsq_plan* P) {
     return FftTables{P->d_T, P->d_T + FFT_R1 * FFT_M1, P->d_T + FFT_R1 * FFT_M1 + FFT_R2 * FFT_R3};
+}
+
+// ------------------------------------------------------------------------------------------
+// plan creation: one function per family of tables; plan_build calls them in order and uploads what they made
+// ------------------------------------------------------------------------------------------
+constexpr double PI2 = 6.283185307179586476925286766559;
+
+// The short bands inside k_slice_irfft (slice_fft.h, SHORT): their transformed windows wait in LDS from this spectrum bin on,
+// above every short band and below the end of the slice spectrum, and one launch holds at most this many radix-4
+// butterflies, small DFTs and scratch entries per gather phase (the kernel's U1 / U2 / UG register arrays).
+constexpr int SHORT_SCRATCH0 = 4096;
+constexpr int SHORT_MAX_BUTTERFLIES = 1280, SHORT_MAX_DFTS = 768, SHORT_MAX_PHASE_ENTRIES = 1280;
+// The four-phases-in-flight gather of k_slice_irfft (slice_fft.h, FAST4) holds one phase as entry pairs in registers: this
+// many entries at 512 threads (the kernel's UP pairs per lane).
+constexpr int FAST4_MAX_PHASE_ENTRIES = 2 * 512 * ((4864 / 2 + 1 + 511) / 512);
+
+// The arguments of xsq_plan_create, and what more than one stage derives from them.
+struct PlanArgs {
+    int L, tr, nbands;
+    const int32_t *Lg, *c;
+    const float* g;
+    const double* gd;
+    const float* tw;
+    std::vector<int64_t> g_off;     // first sample of band j's windows inside g / gd (the bands' windows lie back to back)
+
+    // (-1)^(c_j / 2), and sample q of the band's two windows with the sign and the transform's scale folded in.  The dense
+    // matrices, the window pool of the radix-4 kernel and the short-band schedule all take them from here: the engines are
+    // interchangeable per band only while these agree to the bit.
+    double sign(int j) const { return ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0; }
+    double analysis_window(int j, int q) const { return (double)g[g_off[j] + q] * sign(j) / Lg[j]; }
+    double synthesis_window(int j, int q) const { return gd[g_off[j] + q] * Lg[j] * sign(j) / L; }
+};
+
+// blocks = runs of equal band length (nsgt/nsgtf.py:66-78), and the band table (without .ent: build_slice_fft_tables)
+static int build_band_tables(xsq_plan* P, const PlanArgs& A) {
+    const int L = A.L, nbands = A.nbands;
+    const int32_t *Lg = A.Lg, *c = A.c;
+    P->L = L; P->tr = A.tr; P->h = L / 4; P->nbins = L / 2 + 1; P->nbands = nbands;
+    int64_t cum = 0;
+    for (int j = 0; j < nbands;) {
+        int k = j;
+        while (k + 1 < nbands && Lg[k + 1] == Lg[j]) ++k;
+        P->blocks.push_back(BlockHost{j, k - j + 1, Lg[j], cum});
+        cum += (int64_t)(k - j + 1) * Lg[j];
+        j = k + 1;
+    }
+    P->nblocks = (int)P->blocks.size();
+    P->sumFT = cum;
+    int64_t woff = 0;
+    for (const BlockHost& b : P->blocks) {
+        for (int f = 0; f < b.F; ++f) {
+            const int j = b.first_band + f;
+            if (Lg[j] % 4 != 0 || c[j] % 2 != 0 || Lg[j] > L / 2) {
+                set_error("xsq_plan_create: band %d has Lg=%d c=%d (need Lg%%4==0, c even, Lg<=L/2)", j, Lg[j], c[j]);
+                return XSQ_ERR_ARG;
+            }
+            BandDev d;
+            d.Lg = Lg[j]; d.bin0 = c[j] - Lg[j] / 2; d.f = f; d.F = b.F; d.cum = b.cum;
+            d.ldw = (int)round_up(2 * Lg[j], 16); d.w_off = woff; d.ent = 0;
+            woff += round_up(2 * Lg[j], 64) * d.ldw;
+            P->bands.push_back(d);
+        }
+    }
+    return XSQ_OK;
+}
+
+// Per-band real-ified DFT matrices of the dense engine, stored transposed, Wt[n][k] (K contiguous, as the tile engine wants
+// its B operand).
+// analysis: k = 2p+ri over the band's window in spectrum order (bin = bin0 + p, window
+// index q = (p + Lg/2) mod Lg since windows are stored peak-at-0), n = 2t+ro over coefficients;
+// synthesis: k = 2t+ri over coefficients, n = 2p+ro over spectrum positions.
+static void build_dense_matrices(const xsq_plan* P, const PlanArgs& A, std::vector<float>& Wf, std::vector<float>& Wi) {
+    const BandDev& last = P->bands.back();
+    const size_t floats = (size_t)(last.w_off + round_up(2 * last.Lg, 64) * last.ldw);
+    Wf.assign(floats, 0.f);
+    Wi.assign(floats, 0.f);
+    for (int j = 0; j < A.nbands; ++j) {
+        const BandDev& d = P->bands[j];
+        const int n = d.Lg, ld = d.ldw;
+        std::vector<double> cs(n), sn(n);
+        for (int r = 0; r < n; ++r) { cs[r] = std::cos(PI2 * r / n); sn[r] = std::sin(PI2 * r / n); }
+        float* wf = Wf.data() + d.w_off;
+        float* wi = Wi.data() + d.w_off;
+        for (int p = 0; p < n; ++p) {
+            const int q = (p + n / 2) % n;
+            const int bin = d.bin0 + p;
+            const double conj = (bin < 0 || bin > A.L / 2) ? -1.0 : 1.0;  // mirrored bin: input is conj(U)
+            const double ga = A.analysis_window(j, q);
+            const double gs = A.synthesis_window(j, q);
+            for (int t = 0; t < n; ++t) {
+                const int r = (int)(((int64_t)q * t) % n);
+                // analysis: w = ga * e^{+i 2 pi q t / n};  (a_re + i conj a_im) * w
+                const double wr = ga * cs[r], wim = ga * sn[r];
+                wf[(size_t)(2 * t) * ld + 2 * p] = (float)wr;                    // re <- re
+                wf[(size_t)(2 * t + 1) * ld + 2 * p] = (float)wim;               // im <- re
+                wf[(size_t)(2 * t) * ld + 2 * p + 1] = (float)(-conj * wim);     // re <- im
+                wf[(size_t)(2 * t + 1) * ld + 2 * p + 1] = (float)(conj * wr);   // im <- im
+                // synthesis: rows are coefficients t, columns spectrum positions p:
+                // w = gs * e^{-i 2 pi q t / n}
+                const double vr = gs * cs[r], vi = -gs * sn[r];
+                wi[(size_t)(2 * p) * ld + 2 * t] = (float)vr;                    // re <- re
+                wi[(size_t)(2 * p + 1) * ld + 2 * t] = (float)vi;                // im <- re
+                wi[(size_t)(2 * p) * ld + 2 * t + 1] = (float)(-vi);             // re <- im
+                wi[(size_t)(2 * p + 1) * ld + 2 * t + 1] = (float)vr;            // im <- im
+            }
+        }
+    }
+}
+
+// spectrum coverage (which bands add into bin k), as a CSR over the bins: the gather of the rocFFT path
+static void build_coverage(const xsq_plan* P, std::vector<int>& cov_ptr, std::vector<int>& cov_band) {
+    cov_ptr.assign(P->nbins + 1, 0);
+    std::vector<std::vector<int>> cov(P->nbins);
+    for (int j = 0; j < P->nbands; ++j)
+        for (int p = 0; p < P->bands[j].Lg; ++p) {
+            const int k = P->bands[j].bin0 + p;
+            if (k >= 0 && k <= P->L / 2) cov[k].push_back(j);
+        }
+    for (int k = 0; k < P->nbins; ++k) {
+        cov_ptr[k + 1] = cov_ptr[k] + (int)cov[k].size();
+        cov_band.insert(cov_band.end(), cov[k].begin(), cov[k].end());
+    }
+}
+
+// Tables of the hand-written slice FFT (L == FFT_L): the twiddles T, and the phase-ordered entry table of the inverse gather
+// -- bands j with j % 4 == ph are laid out back to back; .ent of every band and phase_begin are set here.  False when bands
+// of one phase overlap inside [0, L/2]: the gather then has no table (and the plan runs rocFFT).
+static bool build_slice_fft_tables(xsq_plan* P, std::vector<float2>& T, std::vector<int>& tgt, std::vector<unsigned short>& tgt16) {
+    const int L = P->L, nbands = P->nbands;
+    auto W = [&](int64_t j) {   // exp(-2 pi i j / L), argument reduced exactly
+        j %= L;
+        return make_float2((float)std::cos(PI2 * j / L), (float)(-std::sin(PI2 * j / L)));
+    };
+    for (int k1 = 0; k1 < FFT_R1; ++k1)
+        for (int m = 0; m < FFT_M1; ++m) T.push_back(W(2 * (int64_t)k1 * m));
+    for (int k2 = 0; k2 < FFT_R2; ++k2)
+        for (int n3 = 0; n3 < FFT_R3; ++n3) T.push_back(W(2 * (int64_t)FFT_R1 * n3 * k2));
+    for (int k = 0; k <= FFT_N; ++k) T.push_back(W(k));
+    bool ok = true;
+    for (int ph = 0; ph < 4; ++ph) {
+        P->phase_begin[ph] = (int)tgt.size();
+        int last_end = -(1 << 30);
+        for (int j = ph; j < nbands; j += 4) {
+            BandDev& b = P->bands[j];
+            b.ent = (int)tgt.size();
+            const int lo = b.bin0 < 0 ? 0 : b.bin0;
+            if (lo < last_end) ok = false;
+            last_end = b.bin0 + b.Lg > L / 2 + 1 ? L / 2 + 1 : b.bin0 + b.Lg;
+            for (int q = 0; q < b.Lg; ++q) {
+                const int k = b.bin0 + q;
+                tgt.push_back(k >= 0 && k <= L / 2 ? k : -1);
+            }
+        }
+    }
+    P->phase_begin[4] = (int)tgt.size();
+    // the same table as 16-bit bins (0xFFFF = none) + pad entries: pairs of entries load as one dword
+    tgt16.assign(tgt.size() + 2, 0xFFFFu);
+    for (size_t i = 0; i < tgt.size(); ++i) tgt16[i] = tgt[i] >= 0 ? (unsigned short)tgt[i] : 0xFFFFu;
+    return ok;
+}
+
+// Tables of the radix-4 band kernels (band_dft4.h, band_dft4s.h) over the bands with Lg >= the split point; the other bands
+// go to bands4_small (the dense engine, gemm_tile.h) and get their flag in is_short.
+static void build_radix4_tables(xsq_plan* P, const PlanArgs& A, std::vector<Band4Dev>& b4, std::vector<float>& pf, std::vector<float>& pi,
+                                std::vector<char>& is_short) {
+    const int d4_min_lg = switches().d4_min_lg;
+    is_short.assign(A.nbands, 0);
+    std::map<int, int64_t> doff, twoff, coff;
+    auto alloc2 = [&](size_t n) { size_t o = pf.size(); pf.resize(o + n, 0.f); pi.resize(o + n, 0.f); return (int64_t)o; };    // analysis / synthesis pools
+    for (int j = 0; j < A.nbands; ++j) {
+        const BandDev& b = P->bands[j];
+        if (b.Lg < d4_min_lg || b.Lg > 4 * D4_MPAD) { P->bands4_small.push_back(j); is_short[j] = 1; continue; }
+        const int n = b.Lg, m = n / 4;
+        Band4Dev d;
+        memset(&d, 0, sizeof(d));
+        d.Lg = n; d.m = m; d.bin0 = b.bin0; d.f = b.f; d.F = b.F; d.ent = b.ent; d.cum = b.cum; d.jband = j;
+        d.ldd = (int)round_up(2 * m, 16);
+        if (!doff.count(m)) {       // Dt[n' = (k, ro)][kk = (t1, ri)] of exp(-+2 pi i k t1 / m)
+            const int64_t o = alloc2((size_t)round_up(2 * m, 64) * d.ldd);
+            doff[m] = o;
+            for (int k = 0; k < m; ++k)
+                for (int t1 = 0; t1 < m; ++t1) {
+                    const int r = (int)(((int64_t)k * t1) % m);
+                    const double cr = std::cos(PI2 * r / m), si = std::sin(PI2 * r / m);
+                    for (int dir = 0; dir < 2; ++dir) {       // 0: analysis e^{+}, 1: synthesis e^{-}
+                        std::vector<float>& pool = dir ? pi : pf;
+                        const double dre = cr, dim = dir ? -si : si;
+                        pool[o + (size_t)(2 * k) * d.ldd + 2 * t1] = (float)dre;
+                        pool[o + (size_t)(2 * k) * d.ldd + 2 * t1 + 1] = (float)(-dim);
+                        pool[o + (size_t)(2 * k + 1) * d.ldd + 2 * t1] = (float)dim;
+                        pool[o + (size_t)(2 * k + 1) * d.ldd + 2 * t1 + 1] = (float)dre;
+                    }
+                }
+        }
+        d.d_off = doff[m];
+        d.K2 = m / 2 + 1; d.ldc = (int)round_up(d.K2, 8);
+        if (!coff.count(m)) {       // band_dft4s.h: Ct[k][n] = cos(2 pi n k / m), St[k][n] = sin(..) with the direction's sign
+            const size_t csz = (size_t)round_up(d.K2, 16) * d.ldc;
+            const int64_t o = alloc2(2 * csz);
+            coff[m] = o;
+            for (int k = 0; k < d.K2; ++k)
+                for (int nn = 0; nn < d.K2; ++nn) {
+                    const int r = (int)(((int64_t)k * nn) % m);
+                    const double cr = std::cos(PI2 * r / m), si = (nn == 0 || 2 * nn == m) ? 0.0 : std::sin(PI2 * r / m);
+                    pf[o + (size_t)k * d.ldc + nn] = (float)cr;
+                    pi[o + (size_t)k * d.ldc + nn] = (float)cr;
+                    pf[o + csz + (size_t)k * d.ldc + nn] = (float)(-si);     // analysis e^{+}: X[k] = P + i Q = P - i Q'
+                    pi[o + csz + (size_t)k * d.ldc + nn] = (float)si;        // synthesis e^{-}: X[k] = P - i Q
+                }
+        }
+        d.c_off = coff[m];
+        if (!twoff.count(n)) {      // twiddles w^(r t1), r = 1..3: [3][round_up(m, 8)] complex
+            const int mpad = (m + 7) & ~7;
+            const int64_t o = alloc2((size_t)3 * mpad * 2);
+            twoff[n] = o;
+            for (int r = 1; r <= 3; ++r)
+                for (int t1 = 0; t1 < m; ++t1) {
+                    const int e = (r * t1) % n;
+                    const double cr = std::cos(PI2 * e / n), si = std::sin(PI2 * e / n);
+                    pf[o + 2 * ((size_t)(r - 1) * mpad + t1)] = (float)cr;
+                    pf[o + 2 * ((size_t)(r - 1) * mpad + t1) + 1] = (float)si;
+                    pi[o + 2 * ((size_t)(r - 1) * mpad + t1)] = (float)cr;
+                    pi[o + 2 * ((size_t)(r - 1) * mpad + t1) + 1] = (float)(-si);
+                }
+        }
+        d.tw_off = twoff[n];
+        d.win_off = alloc2((size_t)round_up(n, 4));
+        for (int q = 0; q < n; ++q) {
+            pf[d.win_off + q] = (float)A.analysis_window(j, q);
+            pi[d.win_off + q] = (float)A.synthesis_window(j, q);
+        }
+        b4.push_back(d);
+        P->bands4_m.push_back(m);
+        P->d4_max_block = std::max<int64_t>(P->d4_max_block, (int64_t)b.F * b.Lg);
+    }
+    P->nbands4 = (int)b4.size();
+    P->bands4_host.assign(reinterpret_cast<const unsigned char*>(b4.data()),
+                          reinterpret_cast<const unsigned char*>(b4.data()) + b4.size() * sizeof(Band4Dev));
+}
+
+// Schedule of the short bands inside k_slice_irfft (slice_fft.h: ShortSched).  Eligible: every band the radix-4 kernel does
+// not take has Lg = 4m with 4 <= m <= 15 and lies below the scratch area, the scratch area fits above it, every short band of
+// a gather phase precedes every long one, and the work fits the kernel's register arrays.  False: no schedule (the short
+// bands stay on the dense engine).
+struct ShortTables {
+    std::vector<ShortItem1> item1;
+    std::vector<float2> tw1;
+    std::vector<int> codes, stgt;
+    std::vector<float> swd;
+    int nent = 0;
+};
+static bool build_short_schedule(xsq_plan* P, const PlanArgs& A, const std::vector<char>& is_short, ShortTables& H) {
+    const int L = A.L, nbands = A.nbands;
+    bool ok = true;
+    int nent = 0, maxbin = 0;
+    for (int j : P->bands4_small) {
+        const BandDev& b = P->bands[j];
+        if (b.Lg % 4 != 0 || b.Lg < 16 || b.Lg > 60) ok = false;
+        nent += b.Lg;
+        maxbin = std::max(maxbin, b.bin0 + b.Lg);
+    }
+    if (maxbin >= SHORT_SCRATCH0 || SHORT_SCRATCH0 + nent > FFT_N + 1) ok = false;
+    if (!ok) return false;
+    std::vector<std::pair<int, int>> item2;     // (m, code)
+    H.nent = nent;
+    H.stgt.assign((size_t)nent, -1);
+    H.swd.assign((size_t)nent, 0.f);
+    int sc = 0;
+    for (int ph = 0; ph < 4; ++ph) {
+        P->short_begin[ph] = sc;
+        for (int j : P->bands4_small) {
+            if (j % 4 != ph) continue;
+            const BandDev& b = P->bands[j];
+            const int n = b.Lg, m = n / 4;
+            for (int t1 = 0; t1 < m; ++t1) {
+                H.item1.push_back(ShortItem1{(int)b.cum, b.F, b.f, n, t1, sc});
+                for (int r = 1; r <= 3; ++r) {
+                    const int e = (r * t1) % n;
+                    H.tw1.push_back(make_float2((float)std::cos(PI2 * e / n), (float)(-std::sin(PI2 * e / n))));
+                }
+            }
+            for (int r = 0; r < 4; ++r) {
+                item2.push_back({m, ((sc + r * m) << 4) | m});
+                for (int k = 0; k < m; ++k) {
+                    const int q = 4 * k + r;
+                    const int bin = b.bin0 + (q + n / 2) % n;
+                    H.stgt[sc + r * m + k] = (bin >= 0 && bin <= L / 2) ? bin : -1;
+                    H.swd[sc + r * m + k] = (float)A.synthesis_window(j, q);
+                }
+            }
+            sc += n;
+        }
+    }
+    P->short_begin[4] = sc;
+    std::stable_sort(item2.begin(), item2.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+    for (auto& it : item2) H.codes.push_back(it.second);
+    // the gather of the long bands starts behind the short ones of each phase (bands of a phase are in band order)
+    for (int ph = 0; ph < 4; ++ph) {
+        int lo = P->phase_begin[ph + 1];
+        for (int j = ph; j < nbands; j += 4)
+            if (!is_short[j]) { lo = P->bands[j].ent; break; }
+        P->phase_long[ph] = lo;
+        // every short band of the phase must precede every long one, or the split gather would skip entries
+        for (int j = ph; j < nbands; j += 4)
+            if (is_short[j] && P->bands[j].ent >= lo) ok = false;
+    }
+    if (!(ok && H.item1.size() <= SHORT_MAX_BUTTERFLIES && H.codes.size() <= SHORT_MAX_DFTS && sc <= nent)) return false;
+    for (int ph = 0; ph < 4; ++ph)
+        if (P->short_begin[ph + 1] - P->short_begin[ph] > SHORT_MAX_PHASE_ENTRIES) return false;
+    return true;
+}
+
+static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
+                      const float* g, const double* gd, const float* tw) {
+    PlanArgs A{L, tr, nbands, Lg, c, g, gd, tw, std::vector<int64_t>(nbands, 0)};
+    for (int j = 1; j < nbands; ++j) A.g_off[j] = A.g_off[j - 1] + Lg[j - 1];
+    int rc;
+    if ((rc = build_band_tables(P, A))) return rc;
+
+    std::vector<float> Wf, Wi;
+    build_dense_matrices(P, A, Wf, Wi);
+    if ((rc = upload(P->d_Wf, Wf))) return rc;
+    if ((rc = upload(P->d_Wi, Wi))) return rc;
+
+    std::vector<int> cov_ptr, cov_band;
+    build_coverage(P, cov_ptr, cov_band);
+    if ((rc = upload(P->d_cov_ptr, cov_ptr))) return rc;
+    if ((rc = upload(P->d_cov_band, cov_band))) return rc;
+
+    bool phase_table = false;
+    if (L == FFT_L) {
+        std::vector<float2> T;
+        std::vector<int> tgt;
+        std::vector<unsigned short> tgt16;
+        phase_table = build_slice_fft_tables(P, T, tgt, tgt16);
+        if ((rc = upload(P->d_T, T))) return rc;
+        if (phase_table) {
+            if ((rc = upload(P->d_tgt, tgt))) return rc;
+            if ((rc = upload(P->d_tgt16, tgt16))) return rc;
+        }
+    }
+    // the band table, once .ent is known.  The kernels read .ent only beside a phase table (lds_fft): without one the device
+    // copy carries 0 there, the host copy and the Band4Dev entries the offsets.
+    {
+        std::vector<BandDev> dev = P->bands;
+        if (!phase_table) for (BandDev& b : dev) b.ent = 0;
+        if ((rc = upload(P->d_bands, dev))) return rc;
+    }
+
+    std::vector<char> is_short;
+    {
+        std::vector<Band4Dev> b4;
+        std::vector<float> pf, pi;
+        build_radix4_tables(P, A, b4, pf, pi, is_short);
+        if (P->nbands4) {
+            if ((rc = upload(P->d_bands4, b4))) return rc;
+            if ((rc = upload(P->d_pool4f, pf))) return rc;
+            if ((rc = upload(P->d_pool4i, pi))) return rc;
+        }
+    }
+    if ((rc = upload(P->d_tw, tw, (size_t)L))) return rc;
+
+    // (needs the LDS slice FFT's gather table, and both kinds of band)
+    ShortTables H;
+    if (P->d_tgt != nullptr && P->nbands4 > 0 && !P->bands4_small.empty() && build_short_schedule(P, A, is_short, H)) {
+        if ((rc = upload(P->d_s_item1, H.item1))) return rc;
+        if ((rc = upload(P->d_s_tw1, H.tw1))) return rc;
+        if ((rc = upload(P->d_s_item2, H.codes))) return rc;
+        if ((rc = upload(P->d_s_tgt, H.stgt))) return rc;
+        if ((rc = upload(P->d_s_wd, H.swd))) return rc;
+        P->short_n1 = (int)H.item1.size(); P->short_n2 = (int)H.codes.size();
+        P->short_nent = H.nent; P->short_sc0 = SHORT_SCRATCH0;
+    }
+    return XSQ_OK;
 }
 
 }  // namespace xsq
@@ -475,9 +816,6 @@ int xsq_abi_version(void) { return XSQ_ABI_VERSION; }
 const char* xsq_build_info(void) { return "arch=" XSQ_BUILD_ARCH "; flags=" XSQ_BUILD_FLAGS "; date=" __DATE__ " " __TIME__; }
 const char* xsq_last_error(void) { return g_err; }
 
-static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
-                      const float* g, const double* gd, const float* tw);
-
 int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
                     const float* g, const double* gd, const float* tw) {
     XSQ_REQUIRE(out && Lg && c && g && gd && tw, "xsq_plan_create: null argument");
@@ -489,326 +827,6 @@ int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg
         return rc;
     }
     *out = P;
-    return XSQ_OK;
-}
-
-static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
-                      const float* g, const double* gd, const float* tw) {
-    P->L = L; P->tr = tr; P->h = L / 4; P->nbins = L / 2 + 1; P->nbands = nbands;
-    // blocks = runs of equal band length (nsgt/nsgtf.py:66-78)
-    int64_t cum = 0;
-    for (int j = 0; j < nbands;) {
-        int k = j;
-        while (k + 1 < nbands && Lg[k + 1] == Lg[j]) ++k;
-        P->blocks.push_back(BlockHost{j, k - j + 1, Lg[j], cum});
-        cum += (int64_t)(k - j + 1) * Lg[j];
-        j = k + 1;
-    }
-    P->nblocks = (int)P->blocks.size();
-    P->sumFT = cum;
-    int64_t woff = 0, goff = 0;
-    std::vector<int64_t> g_off(nbands);
-    for (const BlockHost& b : P->blocks) {
-        for (int f = 0; f < b.F; ++f) {
-            const int j = b.first_band + f;
-            if (Lg[j] % 4 != 0 || c[j] % 2 != 0 || Lg[j] > L / 2) {
-                set_error("xsq_plan_create: band %d has Lg=%d c=%d (need Lg%%4==0, c even, Lg<=L/2)", j, Lg[j], c[j]);
-                return XSQ_ERR_ARG;
-            }
-            BandDev d;
-            d.Lg = Lg[j]; d.bin0 = c[j] - Lg[j] / 2; d.f = f; d.F = b.F; d.cum = b.cum;
-            d.ldw = (int)round_up(2 * Lg[j], 16); d.w_off = woff; d.ent = 0;
-            woff += round_up(2 * Lg[j], 64) * d.ldw;
-            P->bands.push_back(d);
-            g_off[j] = goff;
-            goff += Lg[j];
-        }
-    }
-    // ---- per-band real-ified DFT matrices --------------------------------------------
-    // stored transposed, Wt[n][k] (K contiguous, as the tile engine wants its B operand).
-    // analysis: k = 2p+ri over the band's window in spectrum order (bin = bin0 + p, window
-    // index q = (p + Lg/2) mod Lg since windows are stored peak-at-0), n = 2t+ro over coefficients;
-    // synthesis: k = 2t+ri over coefficients, n = 2p+ro over spectrum positions.
-    std::vector<float> Wf((size_t)woff, 0.f), Wi((size_t)woff, 0.f);
-    const double PI2 = 6.283185307179586476925286766559;
-    for (int j = 0; j < nbands; ++j) {
-        const BandDev& d = P->bands[j];
-        const int n = d.Lg, ld = d.ldw;
-        const double sign = ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0;
-        std::vector<double> cs(n), sn(n);
-        for (int r = 0; r < n; ++r) { cs[r] = std::cos(PI2 * r / n); sn[r] = std::sin(PI2 * r / n); }
-        float* wf = Wf.data() + d.w_off;
-        float* wi = Wi.data() + d.w_off;
-        for (int p = 0; p < n; ++p) {
-            const int q = (p + n / 2) % n;
-            const int bin = d.bin0 + p;
-            const double conj = (bin < 0 || bin > L / 2) ? -1.0 : 1.0;  // mirrored bin: input is conj(U)
-            const double ga = (double)g[g_off[j] + q] * sign / n;
-            const double gs = gd[g_off[j] + q] * n * sign / L;
-            for (int t = 0; t < n; ++t) {
-                const int r = (int)(((int64_t)q * t) % n);
-                // analysis: w = ga * e^{+i 2 pi q t / n};  (a_re + i conj a_im) * w
-                const double wr = ga * cs[r], wim = ga * sn[r];
-                wf[(size_t)(2 * t) * ld + 2 * p] = (float)wr;                    // re <- re
-                wf[(size_t)(2 * t + 1) * ld + 2 * p] = (float)wim;               // im <- re
-                wf[(size_t)(2 * t) * ld + 2 * p + 1] = (float)(-conj * wim);     // re <- im
-                wf[(size_t)(2 * t + 1) * ld + 2 * p + 1] = (float)(conj * wr);   // im <- im
-                // synthesis: rows are coefficients t, columns spectrum positions p:
-                // w = gs * e^{-i 2 pi q t / n}
-                const double vr = gs * cs[r], vi = -gs * sn[r];
-                wi[(size_t)(2 * p) * ld + 2 * t] = (float)vr;                    // re <- re
-                wi[(size_t)(2 * p + 1) * ld + 2 * t] = (float)vi;                // im <- re
-                wi[(size_t)(2 * p) * ld + 2 * t + 1] = (float)(-vi);             // re <- im
-                wi[(size_t)(2 * p + 1) * ld + 2 * t + 1] = (float)vr;            // im <- im
-            }
-        }
-    }
-    // ---- spectrum coverage (which bands add into bin k) ----------------------------------
-    std::vector<int> cov_ptr(P->nbins + 1, 0), cov_band;
-    {
-        std::vector<std::vector<int>> cov(P->nbins);
-        for (int j = 0; j < nbands; ++j)
-            for (int p = 0; p < P->bands[j].Lg; ++p) {
-                const int k = P->bands[j].bin0 + p;
-                if (k >= 0 && k <= L / 2) cov[k].push_back(j);
-            }
-        for (int k = 0; k < P->nbins; ++k) {
-            cov_ptr[k + 1] = cov_ptr[k] + (int)cov[k].size();
-            cov_band.insert(cov_band.end(), cov[k].begin(), cov[k].end());
-        }
-    }
-#define UP(dst, vec, T)                                                                           \
-    do {                                                                                          \
-        XSQ_HIP(hipMalloc(&(dst), (vec).size() * sizeof(T)));                                     \
-        XSQ_HIP(hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(T), hipMemcpyHostToDevice)); \
-    } while (0)
-    UP(P->d_Wf, Wf, float);
-    UP(P->d_Wi, Wi, float);
-    UP(P->d_bands, P->bands, BandDev);
-    UP(P->d_cov_ptr, cov_ptr, int);
-    UP(P->d_cov_band, cov_band, int);
-#undef UP
-    if (L == FFT_L) {   // tables of the hand-written slice FFT
-        auto W = [&](int64_t j) {   // exp(-2 pi i j / L), argument reduced exactly
-            j %= L;
-            return make_float2((float)std::cos(PI2 * j / L), (float)(-std::sin(PI2 * j / L)));
-        };
-        std::vector<float2> T;
-        for (int k1 = 0; k1 < FFT_R1; ++k1)
-            for (int m = 0; m < FFT_M1; ++m) T.push_back(W(2 * (int64_t)k1 * m));
-        for (int k2 = 0; k2 < FFT_R2; ++k2)
-            for (int n3 = 0; n3 < FFT_R3; ++n3) T.push_back(W(2 * (int64_t)FFT_R1 * n3 * k2));
-        for (int k = 0; k <= FFT_N; ++k) T.push_back(W(k));
-        XSQ_HIP(hipMalloc(&P->d_T, T.size() * sizeof(float2)));
-        XSQ_HIP(hipMemcpy(P->d_T, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice));
-        // phase-ordered entry table of the inverse gather: bands j with j % 4 == ph are laid out back
-        // to back; valid only if the bands of one phase are pairwise disjoint inside [0, L/2]
-        std::vector<int> tgt;
-        bool ok = true;
-        for (int ph = 0; ph < 4; ++ph) {
-            P->phase_begin[ph] = (int)tgt.size();
-            int last_end = -(1 << 30);
-            for (int j = ph; j < nbands; j += 4) {
-                BandDev& b = P->bands[j];
-                b.ent = (int)tgt.size();
-                const int lo = b.bin0 < 0 ? 0 : b.bin0;
-                if (lo < last_end) ok = false;
-                last_end = b.bin0 + b.Lg > L / 2 + 1 ? L / 2 + 1 : b.bin0 + b.Lg;
-                for (int q = 0; q < b.Lg; ++q) {
-                    const int k = b.bin0 + q;
-                    tgt.push_back(k >= 0 && k <= L / 2 ? k : -1);
-                }
-            }
-        }
-        P->phase_begin[4] = (int)tgt.size();
-        if (ok) {
-            XSQ_HIP(hipMalloc(&P->d_tgt, tgt.size() * sizeof(int)));
-            XSQ_HIP(hipMemcpy(P->d_tgt, tgt.data(), tgt.size() * sizeof(int), hipMemcpyHostToDevice));
-            std::vector<unsigned short> t16(tgt.size() + 2, 0xFFFFu);
-            for (size_t i = 0; i < tgt.size(); ++i) t16[i] = tgt[i] >= 0 ? (unsigned short)tgt[i] : 0xFFFFu;
-            XSQ_HIP(hipMalloc(&P->d_tgt16, t16.size() * sizeof(unsigned short)));
-            XSQ_HIP(hipMemcpy(P->d_tgt16, t16.data(), t16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-            // the device copy of the band table was uploaded before .ent was known
-            XSQ_HIP(hipMemcpy(P->d_bands, P->bands.data(), P->bands.size() * sizeof(BandDev), hipMemcpyHostToDevice));
-        }
-    }
-    {   // ---- radix-4 band kernel tables (band_dft4.h): bands with Lg >= d4_min_lg -------------------------
-        std::vector<Band4Dev> b4;
-        std::vector<float> pf, pi;      // analysis / synthesis pools
-        // bands at least this long take the radix-4 kernel (XSQ_D4_MIN_LG: diagnostic A/B of the split point)
-        int d4_min_lg = XSQ_D4_MIN_LG_DEFAULT;
-        if (const char* e = getenv("XSQ_D4_MIN_LG")) d4_min_lg = atoi(e) >= 16 ? atoi(e) : d4_min_lg;
-        std::map<int, int64_t> doff, twoff, coff;
-        auto alloc2 = [&](size_t n) { size_t o = pf.size(); pf.resize(o + n, 0.f); pi.resize(o + n, 0.f); return (int64_t)o; };
-        for (int j = 0; j < nbands; ++j) {
-            const BandDev& b = P->bands[j];
-            if (b.Lg < d4_min_lg || b.Lg > 4 * D4_MPAD) { P->bands4_small.push_back(j); continue; }   // dense engine (gemm_tile.h)
-            const int n = b.Lg, m = n / 4;
-            Band4Dev d;
-            memset(&d, 0, sizeof(d));
-            d.Lg = n; d.m = m; d.bin0 = b.bin0; d.f = b.f; d.F = b.F; d.ent = b.ent; d.cum = b.cum; d.jband = j;
-            d.ldd = (int)round_up(2 * m, 16);
-            if (!doff.count(m)) {       // Dt[n' = (k, ro)][kk = (t1, ri)] of exp(-+2 pi i k t1 / m)
-                const int64_t o = alloc2((size_t)round_up(2 * m, 64) * d.ldd);
-                doff[m] = o;
-                for (int k = 0; k < m; ++k)
-                    for (int t1 = 0; t1 < m; ++t1) {
-                        const int r = (int)(((int64_t)k * t1) % m);
-                        const double cr = std::cos(PI2 * r / m), si = std::sin(PI2 * r / m);
-                        for (int dir = 0; dir < 2; ++dir) {       // 0: analysis e^{+}, 1: synthesis e^{-}
-                            std::vector<float>& pool = dir ? pi : pf;
-                            const double dre = cr, dim = dir ? -si : si;
-                            pool[o + (size_t)(2 * k) * d.ldd + 2 * t1] = (float)dre;
-                            pool[o + (size_t)(2 * k) * d.ldd + 2 * t1 + 1] = (float)(-dim);
-                            pool[o + (size_t)(2 * k + 1) * d.ldd + 2 * t1] = (float)dim;
-                            pool[o + (size_t)(2 * k + 1) * d.ldd + 2 * t1 + 1] = (float)dre;
-                        }
-                    }
-            }
-            d.d_off = doff[m];
-            d.K2 = m / 2 + 1; d.ldc = (int)round_up(d.K2, 8);
-            if (!coff.count(m)) {       // band_dft4s.h: Ct[k][n] = cos(2 pi n k / m), St[k][n] = sin(..) with the direction's sign
-                const size_t csz = (size_t)round_up(d.K2, 16) * d.ldc;
-                const int64_t o = alloc2(2 * csz);
-                coff[m] = o;
-                for (int k = 0; k < d.K2; ++k)
-                    for (int nn = 0; nn < d.K2; ++nn) {
-                        const int r = (int)(((int64_t)k * nn) % m);
-                        const double cr = std::cos(PI2 * r / m), si = (nn == 0 || 2 * nn == m) ? 0.0 : std::sin(PI2 * r / m);
-                        pf[o + (size_t)k * d.ldc + nn] = (float)cr;
-                        pi[o + (size_t)k * d.ldc + nn] = (float)cr;
-                        pf[o + csz + (size_t)k * d.ldc + nn] = (float)(-si);     // analysis e^{+}: X[k] = P + i Q = P - i Q'
-                        pi[o + csz + (size_t)k * d.ldc + nn] = (float)si;        // synthesis e^{-}: X[k] = P - i Q
-                    }
-            }
-            d.c_off = coff[m];
-            if (!twoff.count(n)) {      // twiddles w^(r t1), r = 1..3: [3][round_up(m, 8)] complex
-                const int mpad = (m + 7) & ~7;
-                const int64_t o = alloc2((size_t)3 * mpad * 2);
-                twoff[n] = o;
-                for (int r = 1; r <= 3; ++r)
-                    for (int t1 = 0; t1 < m; ++t1) {
-                        const int e = (r * t1) % n;
-                        const double cr = std::cos(PI2 * e / n), si = std::sin(PI2 * e / n);
-                        pf[o + 2 * ((size_t)(r - 1) * mpad + t1)] = (float)cr;
-                        pf[o + 2 * ((size_t)(r - 1) * mpad + t1) + 1] = (float)si;
-                        pi[o + 2 * ((size_t)(r - 1) * mpad + t1)] = (float)cr;
-                        pi[o + 2 * ((size_t)(r - 1) * mpad + t1) + 1] = (float)(-si);
-                    }
-            }
-            d.tw_off = twoff[n];
-            d.win_off = alloc2((size_t)round_up(n, 4));
-            const double sign = ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0;
-            for (int q = 0; q < n; ++q) {
-                pf[d.win_off + q] = (float)((double)g[g_off[j] + q] * sign / n);
-                pi[d.win_off + q] = (float)(gd[g_off[j] + q] * n * sign / L);
-            }
-            b4.push_back(d);
-            P->bands4_m.push_back(m);
-            P->d4_max_block = std::max<int64_t>(P->d4_max_block, (int64_t)b.F * b.Lg);
-        }
-        P->nbands4 = (int)b4.size();
-        P->bands4_host.assign(reinterpret_cast<const unsigned char*>(b4.data()),
-                              reinterpret_cast<const unsigned char*>(b4.data()) + b4.size() * sizeof(Band4Dev));
-        if (P->nbands4) {
-            XSQ_HIP(hipMalloc(&P->d_bands4, b4.size() * sizeof(Band4Dev)));
-            XSQ_HIP(hipMemcpy(P->d_bands4, b4.data(), b4.size() * sizeof(Band4Dev), hipMemcpyHostToDevice));
-            XSQ_HIP(hipMalloc(&P->d_pool4f, pf.size() * sizeof(float)));
-            XSQ_HIP(hipMemcpy(P->d_pool4f, pf.data(), pf.size() * sizeof(float), hipMemcpyHostToDevice));
-            XSQ_HIP(hipMalloc(&P->d_pool4i, pi.size() * sizeof(float)));
-            XSQ_HIP(hipMemcpy(P->d_pool4i, pi.data(), pi.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-    }
-    XSQ_HIP(hipMalloc(&P->d_tw, (size_t)L * sizeof(float)));
-    XSQ_HIP(hipMemcpy(P->d_tw, tw, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    // ---- short bands inside k_slice_irfft (slice_fft.h: ShortSched) ----------------------------------------
-    // eligible: the LDS slice FFT is in use, every band the radix-4 kernel does not take has Lg = 4m with
-    // 4 <= m <= 15 and lies below the scratch area, and the scratch area fits above it
-    if (P->d_tgt != nullptr && P->nbands4 > 0 && !P->bands4_small.empty()) {
-        bool ok = true;
-        int nent = 0, maxbin = 0;
-        for (int j : P->bands4_small) {
-            const BandDev& b = P->bands[j];
-            if (b.Lg % 4 != 0 || b.Lg < 16 || b.Lg > 60) ok = false;
-            nent += b.Lg;
-            maxbin = std::max(maxbin, b.bin0 + b.Lg);
-        }
-        const int sc0 = 4096;
-        if (maxbin >= sc0 || sc0 + nent > FFT_N + 1) ok = false;
-        if (ok) {
-            std::vector<ShortItem1> item1;
-            std::vector<float2> tw1;
-            std::vector<std::pair<int, int>> item2;     // (m, code)
-            std::vector<int> stgt((size_t)nent, -1);
-            std::vector<float> swd((size_t)nent, 0.f);
-            int sc = 0;
-            for (int ph = 0; ph < 4; ++ph) {
-                P->short_begin[ph] = sc;
-                for (int j : P->bands4_small) {
-                    if (j % 4 != ph) continue;
-                    const BandDev& b = P->bands[j];
-                    const int n = b.Lg, m = n / 4;
-                    const double sign = ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0;
-                    for (int t1 = 0; t1 < m; ++t1) {
-                        item1.push_back(ShortItem1{(int)b.cum, b.F, b.f, n, t1, sc});
-                        for (int r = 1; r <= 3; ++r) {
-                            const int e = (r * t1) % n;
-                            tw1.push_back(make_float2((float)std::cos(PI2 * e / n), (float)(-std::sin(PI2 * e / n))));
-                        }
-                    }
-                    for (int r = 0; r < 4; ++r) {
-                        item2.push_back({m, ((sc + r * m) << 4) | m});
-                        for (int k = 0; k < m; ++k) {
-                            const int q = 4 * k + r;
-                            const int bin = b.bin0 + (q + n / 2) % n;
-                            stgt[sc + r * m + k] = (bin >= 0 && bin <= L / 2) ? bin : -1;
-                            swd[sc + r * m + k] = (float)(gd[g_off[j] + q] * n * sign / L);
-                        }
-                    }
-                    sc += n;
-                }
-            }
-            P->short_begin[4] = sc;
-            std::stable_sort(item2.begin(), item2.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
-            std::vector<int> codes;
-            for (auto& it : item2) codes.push_back(it.second);
-            // the gather of the long bands starts behind the short ones of each phase (bands of a phase are in band order)
-            for (int ph = 0; ph < 4; ++ph) {
-                int lo = P->phase_begin[ph + 1];
-                for (int j = ph; j < nbands; j += 4) {
-                    bool is_short = false;
-                    for (int js : P->bands4_small) is_short = is_short || js == j;
-                    if (!is_short) { lo = P->bands[j].ent; break; }
-                }
-                P->phase_long[ph] = lo;
-                // every short band of the phase must precede every long one, or the split gather would skip entries
-                for (int j = ph; j < nbands; j += 4) {
-                    bool is_short = false;
-                    for (int js : P->bands4_small) is_short = is_short || js == j;
-                    if (is_short && P->bands[j].ent >= lo) ok = false;
-                }
-            }
-            if (ok && item1.size() <= 1280 && codes.size() <= 768 && sc <= nent) {
-                bool fits = true;
-                for (int ph = 0; ph < 4; ++ph) fits = fits && (P->short_begin[ph + 1] - P->short_begin[ph] <= 1280);
-                if (fits) {
-#define UPV(dst, vec, T)                                                                          \
-    do {                                                                                          \
-        XSQ_HIP(hipMalloc((void**)&(dst), (vec).size() * sizeof(T)));                             \
-        XSQ_HIP(hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(T), hipMemcpyHostToDevice)); \
-    } while (0)
-                    UPV(P->d_s_item1, item1, ShortItem1);
-                    UPV(P->d_s_tw1, tw1, float2);
-                    UPV(P->d_s_item2, codes, int);
-                    UPV(P->d_s_tgt, stgt, int);
-                    UPV(P->d_s_wd, swd, float);
-#undef UPV
-                    P->short_n1 = (int)item1.size(); P->short_n2 = (int)codes.size();
-                    P->short_nent = nent; P->short_sc0 = sc0;
-                }
-            }
-        }
-    }
     return XSQ_OK;
 }
 
@@ -901,7 +919,7 @@ size_t xsq_slicqt_forward_workspace(xsq_plan* P, int BC, int64_t n) {
     const size_t rows = (size_t)BC * xsq_plan_num_slices(P, n);
     FftPlan f;
     if (!lds_fft(P) && get_fft(P, 0, (int)rows, &f)) return 0;
-    return al(rows * P->L * 4) + al(rows * P->nbins * 8) + al(f.work_bytes) + 256;
+    return al256(rows * P->L * 4) + al256(rows * P->nbins * 8) + al256(f.work_bytes) + 256;
 }
 
 int xsq_slicqt_forward(xsq_plan* P, const float* x, int BC, int64_t n, float* coef, void* ws,
@@ -940,8 +958,8 @@ int xsq_slicqt_forward_rows_indirect(xsq_plan* P, const float* x, const float* c
     int rc = lds_fft(P) ? XSQ_OK : get_fft(P, 0, rows, &f);
     if (rc) return rc;
     char* w = (char*)ws;
-    float* seg = (float*)w; w += al((size_t)rows * P->L * 4);
-    float* U = (float*)w;   w += al((size_t)rows * P->nbins * 8);
+    float* seg = (float*)w; w += al256((size_t)rows * P->L * 4);
+    float* U = (float*)w;   w += al256((size_t)rows * P->nbins * 8);
     void* fwork = w;
     if ((size_t)(w - (char*)ws) + f.work_bytes > ws_bytes) {
         set_error("xsq_slicqt_forward: workspace too small (%zu needed, %zu given)",
@@ -950,12 +968,11 @@ int xsq_slicqt_forward_rows_indirect(xsq_plan* P, const float* x, const float* c
     }
     if (lds_fft(P)) {
         XSQ_PROF("slice_rfft", stream);
+        auto kernel = k_slice_rfft<512>;
 #if XSQ_PACKED_FFT_KERNELS
-        if (fft_threads(0) == 512 && P->packed_fft) hipLaunchKernelGGL((k_slice_rfft<512, true>), dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot);
-        else
+        if (P->packed_fft) kernel = k_slice_rfft<512, true>;
 #endif
-        if (fft_threads(0) == 512) hipLaunchKernelGGL(k_slice_rfft<512>, dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot);
-        else hipLaunchKernelGGL(k_slice_rfft<256>, dim3(rows), dim3(256), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot);
+        hipLaunchKernelGGL(kernel, dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot);
     } else {
         { XSQ_PROF("slice_window", stream);
         hipLaunchKernelGGL(k_slice_window, dim3((P->L + 255) / 256, rows), dim3(256), 0, stream, x, P->d_tw, seg,
@@ -985,8 +1002,8 @@ size_t xsq_slicqt_inverse_workspace(xsq_plan* P, int BC, int S) {
     const size_t rows = (size_t)BC * S;
     FftPlan f;
     if (!lds_fft(P) && get_fft(P, 1, (int)rows, &f)) return 0;
-    if (lds_fft(P)) return al(rows * P->sumFT * 8) + 256;        // Z only: spectra and segments stay in LDS
-    return al(rows * P->sumFT * 8) + al(rows * P->nbins * 8) + al(rows * P->L * 4) + al(f.work_bytes) + 256;
+    if (lds_fft(P)) return al256(rows * P->sumFT * 8) + 256;        // Z only: spectra and segments stay in LDS
+    return al256(rows * P->sumFT * 8) + al256(rows * P->nbins * 8) + al256(rows * P->L * 4) + al256(f.work_bytes) + 256;
 }
 
 int xsq_slicqt_inverse(xsq_plan* P, const float* coef, int BC, int S, int64_t length, float* y, void* ws,
@@ -1027,9 +1044,9 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
     int rc = lds_fft(P) ? XSQ_OK : get_fft(P, 1, rows, &f);
     if (rc) return rc;
     char* w = (char*)ws;
-    float* Z = (float*)w;    w += al((size_t)rows * P->sumFT * 8);
-    float2* fr = (float2*)w; if (!lds_fft(P)) w += al((size_t)rows * P->nbins * 8);
-    float* seg = (float*)w;  if (!lds_fft(P)) w += al((size_t)rows * P->L * 4);
+    float* Z = (float*)w;    w += al256((size_t)rows * P->sumFT * 8);
+    float2* fr = (float2*)w; if (!lds_fft(P)) w += al256((size_t)rows * P->nbins * 8);
+    float* seg = (float*)w;  if (!lds_fft(P)) w += al256((size_t)rows * P->L * 4);
     void* fwork = w;
     if ((size_t)(w - (char*)ws) + f.work_bytes > ws_bytes) {
         set_error("xsq_slicqt_inverse: workspace too small (%zu needed, %zu given)",
@@ -1067,22 +1084,17 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
             for (int i = 0; i < 5; ++i) SS.begin[i] = P->short_begin[i];
         }
         const ShortIn SI{coef, mask, BC, mask ? BCx : BC};
+        // the four-phases-in-flight gather: the default path's, when the 16-bit table exists and every phase fits its registers
+        bool fast4 = !inl && G.tgt16 != nullptr;
+        for (int ph = 0; ph < 4; ++ph) fast4 = fast4 && (G.begin[ph + 1] - (G.lo[ph] & ~1) <= FAST4_MAX_PHASE_ENTRIES);
+        auto kernel = inl ? k_slice_irfft<512, false, true> : fast4 ? k_slice_irfft<512, false, false, true> : k_slice_irfft<512>;
+#if XSQ_PACKED_FFT_KERNELS
+        if (P->packed_fft && !inl) kernel = fast4 ? k_slice_irfft<512, true, false, true> : k_slice_irfft<512, true>;
+#endif
         for (int parity = 0; parity < 2; ++parity) {
             const int nsl = (S + 1 - parity) / 2;
             OlaArgs O{y, row_offsets, S, P->h, parity, length};
-            const bool sh = SS.n1 > 0;
-            bool fast4 = !sh && fft_threads(1) == 512 && G.tgt16 != nullptr && !getenv("XSQ_FFT_GATHER2");
-            for (int ph = 0; ph < 4; ++ph) fast4 = fast4 && (G.begin[ph + 1] - (G.lo[ph] & ~1) <= 2 * 512 * ((4864 / 2 + 1 + 511) / 512));
-#if XSQ_PACKED_FFT_KERNELS
-            if (fast4 && P->packed_fft) hipLaunchKernelGGL((k_slice_irfft<512, true, false, true>), dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else if (!fast4 && !sh && fft_threads(1) == 512 && P->packed_fft) hipLaunchKernelGGL((k_slice_irfft<512, true>), dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else
-#endif
-            if (fast4) hipLaunchKernelGGL((k_slice_irfft<512, false, false, true>), dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else if (fft_threads(1) == 512 && sh) hipLaunchKernelGGL((k_slice_irfft<512, false, true>), dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else if (fft_threads(1) == 512) hipLaunchKernelGGL(k_slice_irfft<512>, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else if (sh) hipLaunchKernelGGL((k_slice_irfft<256, false, true>), dim3(BC * nsl), dim3(256), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
-            else hipLaunchKernelGGL(k_slice_irfft<256>, dim3(BC * nsl), dim3(256), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
+            hipLaunchKernelGGL(kernel, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
         }
         XSQ_HIP(hipGetLastError());
         return XSQ_OK;
@@ -1112,7 +1124,7 @@ size_t xsq_slicqt_remix_workspace(xsq_plan* P, int R, int B, int S, int wiener) 
     if (!P || R < 1 || R > 4 || B <= 0 || S <= 0) return 0;
     const size_t inv = xsq_slicqt_inverse_workspace(P, R * 2 * B, S);
     if (!inv) return 0;
-    return al((size_t)R * 2 * B * S * P->sumFT * (wiener ? 8 : 4)) + inv;
+    return al256((size_t)R * 2 * B * S * P->sumFT * (wiener ? 8 : 4)) + inv;
 }
 
 int xsq_slicqt_inverse_remix(xsq_plan* P, const float* masks, const float* mix, const float* Y, const float* gains, int R, int B,
@@ -1125,7 +1137,7 @@ int xsq_slicqt_inverse_remix(xsq_plan* P, const float* masks, const float* mix, 
     const int wiener = Y ? 1 : 0, BC = R * 2 * B;
     const size_t need = xsq_slicqt_remix_workspace(P, R, B, S, wiener);
     XSQ_REQUIRE(need && need <= ws_bytes, "xsq_slicqt_inverse_remix: workspace too small (%zu needed, %zu given)", need, ws_bytes);
-    const size_t comb_bytes = al((size_t)BC * S * P->sumFT * (wiener ? 8 : 4));
+    const size_t comb_bytes = al256((size_t)BC * S * P->sumFT * (wiener ? 8 : 4));
     float* comb = (float*)ws;
     RemixArgs a;
     a.src = Y ? Y : masks; a.dst = comb; a.nch = 2 * B; a.R = R; a.S = S; a.cplx = wiener ? 2 : 1;

@@ -685,23 +685,27 @@ static int wg_tables(xsq_train* Tr, int Bn, int S, xsq_train::WgTables* out) {
     wg_build(Tr, Bn, S, &a, &ia, &b, &ib);
     xsq_train::WgTables w;
     w.n23 = (int)a.size(); w.n14 = (int)b.size();
-#define UPW(dst, vec, TY)                                                                         \
-    do {                                                                                          \
-        XSQ_HIP(hipMalloc(&(dst), (vec).size() * sizeof(TY)));                                    \
-        XSQ_HIP(hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(TY), hipMemcpyHostToDevice)); \
-    } while (0)
-    UPW(w.d_t23, a, WgTile); UPW(w.d_i23, ia, WgGroupInfo); UPW(w.d_t14, b, WgTile); UPW(w.d_i14, ib, WgGroupInfo);
     std::vector<BnTile> b1, b2; std::vector<BnInfo> j1, j2;
     bn_build(Tr, Bn, S, 0, &b1, &j1); bn_build(Tr, Bn, S, 1, &b2, &j2);
     w.nbt1 = (int)b1.size(); w.nbt2 = (int)b2.size();
-    UPW(w.d_bt1, b1, BnTile); UPW(w.d_bi1, j1, BnInfo); UPW(w.d_bt2, b2, BnTile); UPW(w.d_bi2, j2, BnInfo);
-#undef UPW
+    int rc = upload(w.d_t23, a);
+    if (!rc) rc = upload(w.d_i23, ia);
+    if (!rc) rc = upload(w.d_t14, b);
+    if (!rc) rc = upload(w.d_i14, ib);
+    if (!rc) rc = upload(w.d_bt1, b1);
+    if (!rc) rc = upload(w.d_bi1, j1);
+    if (!rc) rc = upload(w.d_bt2, b2);
+    if (!rc) rc = upload(w.d_bi2, j2);
+    if (rc) {       // not in the cache yet: nothing else would free what this call allocated
+        (void)hipFree(w.d_t23); (void)hipFree(w.d_i23); (void)hipFree(w.d_t14); (void)hipFree(w.d_i14);
+        (void)hipFree(w.d_bt1); (void)hipFree(w.d_bi1); (void)hipFree(w.d_bt2); (void)hipFree(w.d_bi2);
+        return rc;
+    }
     Tr->wg[{Bn, S}] = w;
     *out = w;
     return XSQ_OK;
 }
 
-static inline size_t alt(size_t x) { return (x + 255) / 256 * 256; }
 static int kf_of_t(int F) { return F < 10 ? 1 : (F < 20 ? 3 : 5); }
 
 extern "C" {
@@ -841,31 +845,24 @@ static int train_build(xsq_train* Tr, int nblocks, const int32_t* F, const int32
                                     (int)(g.p_w1 + (((int64_t)co * 2 + c) * kf + df) * W + dt + tap * hop);
         }
     }
-#define UPV(dst, vec, TY)                                                                         \
-    do {                                                                                          \
-        XSQ_HIP(hipMalloc(&(dst), (vec).size() * sizeof(TY)));                                    \
-        XSQ_HIP(hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(TY), hipMemcpyHostToDevice)); \
-    } while (0)
-    UPV(Tr->d_groups, Tr->groups, TrainGroup);
-    UPV(Tr->d_geo, geo, BlockGeo);
-    UPV(Tr->d_rows, rows, int2);
-    UPV(Tr->d_trainable, trainable, unsigned char);
-    UPV(Tr->d_map_pool, map, int);
-    UPV(Tr->d_map_mean, map_mean, int);
-    UPV(Tr->d_map_scale, map_scale, int);
-    UPV(Tr->d_map_bwd, mapb, int);
+    if (int rc = upload(Tr->d_groups, Tr->groups)) return rc;
+    if (int rc = upload(Tr->d_geo, geo)) return rc;
+    if (int rc = upload(Tr->d_rows, rows)) return rc;
+    if (int rc = upload(Tr->d_trainable, trainable)) return rc;
+    if (int rc = upload(Tr->d_map_pool, map)) return rc;
+    if (int rc = upload(Tr->d_map_mean, map_mean)) return rc;
+    if (int rc = upload(Tr->d_map_scale, map_scale)) return rc;
+    if (int rc = upload(Tr->d_map_bwd, mapb)) return rc;
     std::vector<int> frow1((size_t)4 * Mo->sumF1), frow2((size_t)4 * Mo->sumF2);
     for (int gi = 0; gi < Tr->ngroups; ++gi) {
         const TrainGroup& g = Tr->groups[gi];
         for (int f = 0; f < g.F1; ++f) frow1[4 * g.cumF1 + g.tgt * g.F1 + f] = gi;
         for (int f = 0; f < g.F2; ++f) frow2[4 * g.cumF2 + g.tgt * g.F2 + f] = gi;
     }
-    UPV(Tr->d_frow1, frow1, int);
-    UPV(Tr->d_frow2, frow2, int);
+    if (int rc = upload(Tr->d_frow1, frow1)) return rc;
+    if (int rc = upload(Tr->d_frow2, frow2)) return rc;
     XSQ_HIP(hipMalloc(&Tr->d_pool_bwd, (size_t)extent * 4));
-#undef UPV
-    XSQ_HIP(hipMalloc(&Tr->d_params, (size_t)nparams * 4));
-    XSQ_HIP(hipMemcpy(Tr->d_params, params, (size_t)nparams * 4, hipMemcpyHostToDevice));
+    if (int rc = upload(Tr->d_params, params, (size_t)nparams)) return rc;
     XSQ_HIP(hipMalloc(&Tr->d_grads, (size_t)nparams * 4));
     XSQ_HIP(hipMalloc(&Tr->d_m, (size_t)nparams * 4));
     XSQ_HIP(hipMalloc(&Tr->d_v, (size_t)nparams * 4));
@@ -932,11 +929,11 @@ size_t xsq_train_workspace(const xsq_train* Tr, int Bn, int S, int wiener) {
     const int64_t T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
     const size_t n2 = (size_t)Bn * 2 * S * Mo->sumFT, n8 = 4 * n2;
     const size_t a1 = (size_t)CS * Bn * T1 * 4 * Mo->sumF1, a2 = (size_t)CS * Bn * T2 * 4 * Mo->sumF2;
-    size_t b = alt(n2 * 4) + 6 * alt(a1 * 4) + 3 * alt(a2 * 4) + 2 * alt(n8 * 4) + 2 * alt(n8 * 8);
+    size_t b = al256(n2 * 4) + 6 * al256(a1 * 4) + 3 * al256(a2 * 4) + 2 * al256(n8 * 4) + 2 * al256(n8 * 8);
     const auto sz = train_sizes(Tr, Bn, S);
-    b += alt((size_t)Tr->ngroups * 3 * 256 * 4) + 2 * alt((size_t)Tr->sumF * 4) + alt(sz.first * 8) + alt(sz.second * 4);
-    b += xsq_loss_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S) + alt((size_t)Tr->nblocks * 16) + 4096;
-    if (wiener) b += 2 * alt(xsq_wiener_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S, 5000)) + 4096;
+    b += al256((size_t)Tr->ngroups * 3 * 256 * 4) + 2 * al256((size_t)Tr->sumF * 4) + al256(sz.first * 8) + al256(sz.second * 4);
+    b += xsq_loss_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S) + al256((size_t)Tr->nblocks * 16) + 4096;
+    if (wiener) b += 2 * al256(xsq_wiener_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S, 5000)) + 4096;
     return b;
 }
 
@@ -954,7 +951,7 @@ int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S
     const size_t n2 = (size_t)Bn * 2 * S * Mo->sumFT, n8 = 4 * n2;
     const size_t na1 = (size_t)CS * Bn * T1 * 4 * Mo->sumF1, na2 = (size_t)CS * Bn * T2 * 4 * Mo->sumF2;
     char* w = (char*)ws;
-    auto take = [&](size_t bytes) { void* p = w; w += alt(bytes); return p; };
+    auto take = [&](size_t bytes) { void* p = w; w += al256(bytes); return p; };
     float* xin = (float*)take(n2 * 4);
     float *z1 = (float*)take(na1 * 4), *a1 = (float*)take(na1 * 4), *g1 = (float*)take(na1 * 4);
     float *z2 = (float*)take(na2 * 4), *a2 = (float*)take(na2 * 4), *g2 = (float*)take(na2 * 4);

@@ -606,14 +606,14 @@ static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, i
     WTable t;
     t.nrows = (int)rows.size(); t.nwork = (int)work.size() / 2; t.nblockwin = (int)blockwin.size() / 2;
     t.stat_floats = stat; t.max_frames = maxN;
-    XSQ_HIP(hipMalloc(&t.d_rows, rows.size() * sizeof(WRow)));
-    XSQ_HIP(hipMemcpy(t.d_rows, rows.data(), rows.size() * sizeof(WRow), hipMemcpyHostToDevice));
-    XSQ_HIP(hipMalloc(&t.d_work, work.size() * sizeof(int)));
-    XSQ_HIP(hipMemcpy(t.d_work, work.data(), work.size() * sizeof(int), hipMemcpyHostToDevice));
-    XSQ_HIP(hipMalloc(&t.d_blockwin, blockwin.size() * sizeof(int)));
-    XSQ_HIP(hipMemcpy(t.d_blockwin, blockwin.data(), blockwin.size() * sizeof(int), hipMemcpyHostToDevice));
-    XSQ_HIP(hipMalloc(&t.d_bw_of_work, bw_of_work.size() * sizeof(int)));
-    XSQ_HIP(hipMemcpy(t.d_bw_of_work, bw_of_work.data(), bw_of_work.size() * sizeof(int), hipMemcpyHostToDevice));
+    int rc = upload(t.d_rows, rows);
+    if (!rc) rc = upload(t.d_work, work);
+    if (!rc) rc = upload(t.d_blockwin, blockwin);
+    if (!rc) rc = upload(t.d_bw_of_work, bw_of_work);
+    if (rc) {       // not in the cache yet: nothing else would free what this call allocated
+        (void)hipFree(t.d_rows); (void)hipFree(t.d_work); (void)hipFree(t.d_blockwin); (void)hipFree(t.d_bw_of_work);
+        return rc;
+    }
     g_wtables[key] = t;
     *out = t;
     return XSQ_OK;
