@@ -1,4 +1,4 @@
-"""The table / judge helper of the float64 parity tests (tests/test_ref64_gpu.py, tests/test_ref64_train_gpu.py).
+"""The table / judge helper of the float64 parity tests (tests/test_ref64_gpu.py, tests/test_ref64_train_gpu.py, tests/test_ref64_stress_gpu.py).
 
 TEST INFRASTRUCTURE (see oracle/__init__.py).  One rule for every stage:  e_gpu <= M * E,  e_gpu the kernels' error against
 oracle/ref64.py, E the LARGEST error of the fp32 CPU oracle over the members of the stage on the same input, both by
@@ -20,8 +20,11 @@ class Tables:
     def __init__(self, name: str, M: dict):
         self.name, self.M, self.tables = name, M, {}
 
-    def judge(self, stage, case, e_gpu, e_cpu, labels, full_table=False, arm=None):
-        """Print the table, record it, and return the failures of  e_gpu <= M * E  (E = largest e_cpu, per metric)."""
+    def judge(self, stage, case, e_gpu, e_cpu, labels, full_table=False, arm=None, localise=False):
+        """Print the table, record it, and return the failures of  e_gpu <= M * E  (E = largest e_cpu, per metric).  ``localise``: for
+        a stage whose e_cpu varies widely over its members, the RMS metric of member i is judged against  max(e_cpu[i], median e_cpu)
+        instead of the largest (the maximum alone would let the kernels be  largest / median  times worse than the oracle on a typical
+        member); the max metric keeps the largest e_cpu."""
         M = self.M
         key = f"{stage}/{arm}" if f"{stage}/{arm}" in M else stage
         bound = M[key]
@@ -29,7 +32,8 @@ class Tables:
         g_rms, g_max, c_rms, c_max = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (g_rms, g_max, c_rms, c_max))
         assert g_rms.shape == g_max.shape == c_rms.shape == c_max.shape == (len(labels),), (g_rms.shape, c_rms.shape, len(labels))
         E_rms, E_max = float(c_rms.max()), float(c_max.max())
-        ratio = np.maximum(g_rms / E_rms, g_max / E_max)
+        E_loc = np.maximum(c_rms, np.median(c_rms)) if localise else E_rms
+        ratio = np.maximum(g_rms / E_loc, g_max / E_max)
         w = int(np.argmax(ratio))
         print(f"\n[{stage}] {case}: E_rms {E_rms:.3e} E_max {E_max:.3e}; worst e_gpu / E = {ratio[w]:.2f} at {labels[w]} (M = {bound})")
         print("  index / class                      e_gpu rms   e_gpu max   e_cpu rms   e_cpu max   ratio")
@@ -37,11 +41,13 @@ class Tables:
             print(f"  {lab:34s} {g_rms[i]:.3e}   {g_max[i]:.3e}   {c_rms[i]:.3e}   {c_max[i]:.3e}   {ratio[i]:.2f}")
         rec = {"M_key": key, "E_rms": E_rms, "E_max": E_max, "worst_ratio": float(ratio[w]), "worst_at": labels[w],
                "worst_e_gpu_rms": float(g_rms.max()), "worst_e_gpu_max": float(g_max.max())}
+        if localise:
+            rec["E_rms_median"] = float(np.median(c_rms))
         if full_table:
             rec["table"] = {"label": list(labels), "e_gpu_rms": g_rms.tolist(), "e_gpu_max": g_max.tolist(),
                             "e_cpu_rms": c_rms.tolist(), "e_cpu_max": c_max.tolist()}
         self.tables.setdefault(stage, {})[case] = rec
-        bad = [f"{labels[i]}: e_gpu rms {g_rms[i]:.3e} max {g_max[i]:.3e} = {ratio[i]:.2f} x E" for i in np.nonzero(ratio > bound)[0]]
+        bad = [f"{labels[i]}: e_gpu rms {g_rms[i]:.3e} max {g_max[i]:.3e} = {ratio[i]:.2f} x E" for i in np.nonzero(~(ratio <= bound))[0]]     # (a NaN fails)
         return bad, float(ratio[w])
 
     def record(self, stage, case, rec):
