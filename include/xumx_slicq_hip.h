@@ -324,6 +324,33 @@ int xsq_wiener_em_masked_ext(int nblocks, const int32_t* F, const int32_t* T, co
                              float* Y, int B, int S, int win_len, int batch_group, const float* ext_max,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* More than one EM iteration: norbert.wiener(v, x, iterations = niter, use_softmask=False), the `niter` of the Open-Unmix
+ * family.  The reference's caller pins it to 1 (phase.py:53-58); norbert itself loops, norbert/__init__.py:133-148
+ * (expectation_maximization: v and R are recomputed from the current estimates in every iteration) inside ONE scaling by
+ * max(1, 0.1 max|x|) per window, norbert/__init__.py:247-260 (wiener).  Windows, batch_group and ext_max as above.
+ *   niter   0: Y is the initial estimate (xsq_wiener_em_iter leaves it alone; the masked entry point refuses 0 -- the
+ *              mix-phase estimate mask * X has no EM pass), 1: exactly the launches of xsq_wiener_em /
+ *              xsq_wiener_em_masked_ext (same bits), >= 2: one of the two forms below.  Negative: XSQ_ERR_ARG.
+ *   method  0 auto: resident when the longest window of the call fits, else looped; 1 looped: iteration 1 as above,
+ *           then per iteration the statistics of the current estimates and the apply kernel in place on Y (any window
+ *           length); 2 resident: one workgroup per (row, window) holds the window's frames on chip over all iterations
+ *           -- one read of the inputs, one write of Y, whatever niter is -- for windows of at most
+ *           xsq_wiener_resident_max_window() frames (>= the default 5000), XSQ_ERR_ARG when the call has a longer one.
+ *   The two forms agree to fp32 rounding, not bitwise; each is bitwise reproducible (no atomics in the sums).
+ *   workspace: xsq_wiener_iter_workspace bytes (0 on error).                                                            */
+int xsq_wiener_resident_max_window(void);
+size_t xsq_wiener_iter_workspace(int nblocks, const int32_t* F, const int32_t* T, int B, int S, int win_len, int niter,
+                                 int method);
+/* norbert/__init__.py:133-148, 247-260 on the estimates arena, in place (the many-iteration form of xsq_wiener_em). */
+int xsq_wiener_em_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int B, int S,
+                       int win_len, int batch_group, int niter, int method, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* norbert/__init__.py:133-148, 247-260 fed by the masks (the many-iteration form of xsq_wiener_em_masked_ext; ext_max
+ * may be NULL).  win_len and every S*T_b must be even.                                                              */
+int xsq_wiener_em_masked_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks,
+                              float* Y, int B, int S, int win_len, int batch_group, const float* ext_max, int niter,
+                              int method, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- loss forward (validation half of training.loop, training.py:34-112 with train=False) -------
  * Replaces ComplexMSELossCriterion (loss.py:37-76) and MaskSumLossCriterion (loss.py:79-96).
  *   pred, target  complex arenas, 8*B channels (4 targets, B, 2, ...)
@@ -402,6 +429,9 @@ int xsq_train_set_precision(xsq_train* t, int mode);
  *     xsq_slicqt_forward_rows (+ whitened magnitude) -> xsq_cdae_forward_xin (masks only)
  *       -> wiener == 0: xsq_slicqt_inverse_masked          (mix-phase, the estimate mask * X formed on the way in)
  *          wiener == 1: xsq_wiener_em_masked -> xsq_slicqt_inverse_rows
+ *          wiener >= 2: xsq_wiener_em_masked_iter(niter = wiener, method = auto) -> xsq_slicqt_inverse_rows
+ *   `wiener` is the number of EM iterations in every entry point of this section (0 and 1 keep their earlier meaning
+ *   and bits; negative: XSQ_ERR_ARG).
  *   x_rows: DEVICE int64[2B] element offsets of the input rows (NULL: contiguous (B, 2, n)); out_rows: DEVICE
  *   int64[8B] element offsets of packed channel (target, item, c) in `out`; n = samples per item, n_pad as above.
  * xsq_separator_forward: audio (nb, 2, N) -> out (4, nb, 2, N), both DEVICE fp32 contiguous.  Full chunks are stacked

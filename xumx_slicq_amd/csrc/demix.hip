@@ -87,7 +87,8 @@ static int pass_layout(xsq_demixer* d, const xsq_model* Mo, int B, int64_t n_pad
     L->fwd_bytes = xsq_slicqt_forward_workspace(P, 2 * B, n_pad);
     L->cdae_bytes = xsq_cdae_workspace(Mo, B, S);
     L->inv_bytes = xsq_slicqt_inverse_workspace(P, 8 * B, S);
-    L->wien_bytes = wiener ? xsq_wiener_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000) : 0;
+    L->wien_bytes = wiener >= 2 ? xsq_wiener_iter_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000, wiener, 0)
+                  : wiener ? xsq_wiener_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000) : 0;
     if (!L->fwd_bytes || !L->cdae_bytes || !L->inv_bytes || (wiener && !L->wien_bytes)) {
         const std::string why = xsq_last_error();
         set_error("xsq_demix_pass: B=%d, %lld samples: a stage's workspace query failed (%s)", B, (long long)n_pad, why.c_str());
@@ -143,8 +144,13 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
     if ((rc = xsq_cdae_forward_xin(Mo, X, B, S, nullptr, masks, w + L.cdae, L.cdae_bytes, stream, 1))) return rc;
     if (!wiener && !gains)
         return xsq_slicqt_inverse_masked(P, masks, X, 8 * B, 2 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
-    if (wiener && (rc = xsq_wiener_em_masked_ext(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
-                                                 w + L.wien, L.wien_bytes, stream)))
+    // `wiener` counts the EM iterations: one runs the three launches it always ran, more take the form xsq_wiener_em_masked_iter
+    // chooses (the window-resident kernel: 5000 frames fit)
+    if (wiener == 1 && (rc = xsq_wiener_em_masked_ext(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
+                                                      w + L.wien, L.wien_bytes, stream)))
+        return rc;
+    if (wiener >= 2 && (rc = xsq_wiener_em_masked_iter(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
+                                                       wiener, 0, w + L.wien, L.wien_bytes, stream)))
         return rc;
     if (!gains) return xsq_slicqt_inverse_rows(P, Y, 8 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
     return run_remix(P, wiener ? nullptr : masks, wiener ? nullptr : X, wiener ? Y : nullptr, gains, R, B, S, n, out, out_rows,
@@ -245,7 +251,7 @@ static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
     const int cap = d->max_item_slices > 0 ? d->max_item_slices : default_max_item_slices(P);
     ForwardPlan fp;
     std::vector<SchedPass> sched;
-    build_schedule(P->L, nb, N, cs, max_stack, wiener, cap, &sched);
+    build_schedule(P->L, nb, N, cs, max_stack, wiener ? 1 : 0, cap, &sched);
     std::vector<std::vector<int64_t>> xr, orw;
     for (const SchedPass& sp : sched) {
         PassPlan p;
@@ -348,6 +354,7 @@ int xsq_separator_schedule(int L, int64_t coefs_per_slice, int nb, int64_t N, in
                            int max_item_slices, int64_t* passes, int max_passes) {
     XSQ_REQUIRE(L > 0 && L % 4 == 0 && coefs_per_slice > 0 && nb > 0 && N > 0 && cs > 0 && max_stack > 0 && (passes || max_passes == 0),
                 "xsq_separator_schedule: bad argument");
+    XSQ_REQUIRE(wiener >= 0, "xsq_separator_schedule: wiener=%d iterations", wiener);
     const int64_t lim = ((1ll << 31) - 1) / (16 * std::max<int64_t>(coefs_per_slice, L / 2 + 1));
     const int dflt = (int)std::min<int64_t>(lim, 65535 / 8);
     const int cap = max_item_slices > 0 ? std::min(max_item_slices, dflt) : dflt;
@@ -369,7 +376,7 @@ int xsq_demixer_set_max_rows(xsq_demixer* d, int max_item_slices) {
 }
 
 size_t xsq_demix_pass_workspace(xsq_demixer* d, const xsq_model* Mo, int B, int64_t n_pad, int wiener) {
-    if (!d || !Mo || B <= 0 || n_pad <= 0) return 0;
+    if (!d || !Mo || B <= 0 || n_pad <= 0 || wiener < 0) return 0;
     PassLayout L;
     return pass_layout(d, Mo, B, n_pad, wiener, &L) ? 0 : L.total;
 }
@@ -380,6 +387,7 @@ int xsq_demix_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const int64_t*
     XSQ_REQUIRE(B > 0 && n > 0 && n_pad >= n, "xsq_demix_pass: B=%d n=%lld n_pad=%lld", B, (long long)n, (long long)n_pad);
     if (group <= 0) group = B;
     XSQ_REQUIRE(B % group == 0, "xsq_demix_pass: group=%d does not divide B=%d", group, B);
+    XSQ_REQUIRE(wiener >= 0, "xsq_demix_pass: wiener=%d iterations", wiener);
     return run_pass(d, Mo, x, nullptr, x_rows, B, n, n_pad, group, wiener, out, out_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -388,9 +396,10 @@ int xsq_separator_workspace(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
     XSQ_REQUIRE(d && Mo && main_bytes && tail_bytes, "xsq_separator_workspace: null argument");
     XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "xsq_separator_workspace: nb=%d N=%lld chunk_size=%lld max_stack=%d",
                 nb, (long long)N, (long long)cs, max_stack);
+    XSQ_REQUIRE(wiener >= 0, "xsq_separator_workspace: wiener=%d iterations", wiener);
     std::lock_guard<std::mutex> lk(d->mu);
     ForwardPlan* fp;
-    int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener ? 1 : 0, &fp);
+    int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, &fp);
     if (rc) return rc;
     *main_bytes = fp->main_bytes;
     *tail_bytes = fp->tail_bytes;
@@ -423,11 +432,12 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
     XSQ_REQUIRE(d && Mo && (audio || x_slot) && out && ws, "xsq_separator_forward: null argument");
     XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "xsq_separator_forward: nb=%d N=%lld chunk_size=%lld max_stack=%d",
                 nb, (long long)N, (long long)cs, max_stack);
+    XSQ_REQUIRE(wiener >= 0, "xsq_separator_forward: wiener=%d iterations", wiener);
     hipStream_t main = (hipStream_t)stream_, side = (hipStream_t)tail_stream_;
     ForwardPlan* fp;
     {
         std::lock_guard<std::mutex> lk(d->mu);
-        int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener ? 1 : 0, &fp);
+        int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, &fp);
         if (rc) return rc;
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(main, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) fp->pinned = true;

@@ -15,6 +15,13 @@
 // Three launches: k_wiener_stats (raw sums + max per row/window, fixed-order LDS tree, no atomics
 // -> bitwise reproducible), k_wiener_finalize (window max, R), k_wiener_apply (elementwise 2x2
 // solve, in place on Y).  All reads/writes are contiguous along the frame axis.
+// More iterations (niter of the Open-Unmix family; norbert/__init__.py:133-148 loops, :247-260 scales ONCE
+// around the loop): xsq_wiener_em_iter / xsq_wiener_em_masked_iter below.  niter = 1 runs exactly the three
+// launches above.  niter >= 2 runs either the looped form (iteration 1 as above, then per iteration the
+// statistics of the current estimates and the apply kernel in place; any window length) or the
+// window-resident form (one workgroup per (row, window) keeps the window's frames in registers over all
+// iterations: one read, one write; windows of at most xsq_wiener_resident_max_window() frames) --
+// wiener_iter.h.  `method` chooses: 0 = resident when the window fits, 1 = looped, 2 = resident.
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -567,6 +574,8 @@ __global__ __launch_bounds__(256) void k_wiener_window_max(const float2* __restr
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(ext_max) + bw_of_work[blockIdx.x], __builtin_bit_cast(unsigned, m));
 }
 
+#include "wiener_iter.h"      // niter > 1: k_wiener_stats_iter (looped form), k_wiener_resident (window-resident form)
+
 // ------------------------------------------------------------------------------------------------
 static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int group, WTable* out) {
     std::vector<int> key;
@@ -762,6 +771,114 @@ int xsq_wiener_em_masked_ext(int nblocks, const int32_t* F, const int32_t* T, co
                        (const float2*)X, masks, (float2*)Y, t.d_rows, stats, Bn, S, win_len); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
+}
+
+
+// ---- niter iterations (norbert/__init__.py:133-148, 247-260) -----------------------------------------------------------
+int xsq_wiener_resident_max_window(void) { return RES_MAX_WINDOW; }
+
+// the longest window a call runs: win_len, or the longest row when that is shorter
+static int64_t longest_window(int nblocks, const int32_t* T, int S, int win_len) {
+    int64_t maxN = 0;
+    for (int k = 0; k < nblocks; ++k) maxN = std::max<int64_t>(maxN, (int64_t)S * T[k]);
+    return std::min<int64_t>(win_len, maxN);
+}
+
+// workspace: the statistics of xsq_wiener_workspace | max |x|^2 per (block, group, window) of the resident form
+static size_t iter_stats_bytes(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len) {
+    return (xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len) + 255) / 256 * 256;
+}
+
+size_t xsq_wiener_iter_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int niter, int method) {
+    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0 || niter < 0 || method < 0 || method > 2) return 0;
+    return iter_stats_bytes(nblocks, F, T, Bn, S, win_len) + (size_t)xsq_wiener_num_windows(nblocks, F, T, Bn, S, win_len, 1) * 4 + 256;
+}
+
+// shared argument checks of the two entry points; no HIP call.  *resident: the form the call takes (niter >= 2).
+static int check_iter(const char* who, int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int* batch_group,
+                      int niter, int method, size_t ws_bytes, bool* resident) {
+    XSQ_REQUIRE(niter >= 0, "%s: niter=%d", who, niter);
+    XSQ_REQUIRE(method >= 0 && method <= 2, "%s: method=%d (0 auto, 1 looped, 2 resident)", who, method);
+    const bool fits = longest_window(nblocks, T, S, win_len) <= RES_MAX_WINDOW;
+    XSQ_REQUIRE(method != 2 || fits, "%s: the resident form holds windows of at most %d frames (this call's longest has %lld)", who,
+                RES_MAX_WINDOW, (long long)longest_window(nblocks, T, S, win_len));
+    if (*batch_group <= 0) *batch_group = Bn;
+    XSQ_REQUIRE(Bn % *batch_group == 0, "%s: batch_group=%d does not divide B=%d", who, *batch_group, Bn);
+    XSQ_REQUIRE(ws_bytes >= xsq_wiener_iter_workspace(nblocks, F, T, Bn, S, win_len, niter, method), "%s: workspace too small", who);
+    *resident = niter >= 2 && method != 1 && fits;
+    return XSQ_OK;
+}
+
+static int run_resident(bool masked, int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y, int Bn, int S,
+                        int win_len, int batch_group, const float* ext_max, int niter, void* ws, hipStream_t stream) {
+    WTable t;
+    int rc;
+    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
+    float* wmax = (float*)((char*)ws + iter_stats_bytes(nblocks, F, T, Bn, S, win_len));
+    XSQ_HIP(hipMemsetAsync(wmax, 0, (size_t)t.nblockwin * 4, stream));
+    { XSQ_PROF("wiener_window_max", stream);
+    hipLaunchKernelGGL(k_wiener_window_max, dim3(t.nwork), dim3(256), 0, stream, (const float2*)X, t.d_rows, t.d_work, t.d_bw_of_work,
+                       wmax, Bn, S, win_len); }
+    { XSQ_PROF("wiener_resident", stream);
+    hipLaunchKernelGGL(masked ? k_wiener_resident<true> : k_wiener_resident<false>, dim3(t.nwork), dim3(RES_THREADS), 0, stream,
+                       (const float2*)X, masks, (float2*)Y, t.d_rows, t.d_work, t.d_bw_of_work, wmax, ext_max, Bn, S, win_len, niter); }
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
+}
+
+// iterations 2 .. niter of the looped form, after iteration 1 left the estimates in Y and 1/ma^2 in the stats slots
+static int run_more_iterations(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S, int win_len,
+                               int batch_group, int niter, void* ws, hipStream_t stream) {
+    WTable t;
+    int rc;
+    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
+    float* stats = (float*)ws;
+    for (int it = 2; it <= niter; ++it) {
+        { XSQ_PROF("wiener_stats_iter", stream);
+        hipLaunchKernelGGL(k_wiener_stats_iter, dim3(t.nwork), dim3(256), 0, stream, (const float2*)Y, t.d_rows, t.d_work, stats, Bn, S,
+                           win_len); }
+        { XSQ_PROF("wiener_apply", stream);
+        hipLaunchKernelGGL(k_wiener_apply, dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, stream,
+                           (const float2*)X, (float2*)Y, t.d_rows, stats, Bn, S, win_len); }
+    }
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
+}
+
+int xsq_wiener_em_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S, int win_len,
+                       int batch_group, int niter, int method, void* ws, size_t ws_bytes, void* stream_) {
+    int rc = check_table("xsq_wiener_em_iter", nblocks, F, T, Bn, S);
+    if (rc) return rc;
+    XSQ_REQUIRE(X && Y && ws, "xsq_wiener_em_iter: null argument");
+    XSQ_REQUIRE(win_len > 0, "xsq_wiener_em_iter: win_len=%d", win_len);
+    bool resident;
+    if ((rc = check_iter("xsq_wiener_em_iter", nblocks, F, T, Bn, S, win_len, &batch_group, niter, method, ws_bytes, &resident))) return rc;
+    if (niter == 0) return XSQ_OK;                        // the initial estimate is the result (norbert :247-251)
+    if (resident)
+        return run_resident(false, nblocks, F, T, X, nullptr, Y, Bn, S, win_len, batch_group, nullptr, niter, ws, (hipStream_t)stream_);
+    if ((rc = xsq_wiener_em(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, ws, ws_bytes, stream_))) return rc;
+    return niter == 1 ? XSQ_OK : run_more_iterations(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, niter, ws, (hipStream_t)stream_);
+}
+
+int xsq_wiener_em_masked_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y, int Bn,
+                              int S, int win_len, int batch_group, const float* ext_max, int niter, int method, void* ws,
+                              size_t ws_bytes, void* stream_) {
+    int rc = check_table("xsq_wiener_em_masked_iter", nblocks, F, T, Bn, S);
+    if (rc) return rc;
+    XSQ_REQUIRE(X && masks && Y && ws, "xsq_wiener_em_masked_iter: null argument");
+    XSQ_REQUIRE(win_len > 0 && win_len % 2 == 0, "xsq_wiener_em_masked_iter: win_len=%d must be even (two frames per thread)", win_len);
+    XSQ_REQUIRE(niter != 0, "xsq_wiener_em_masked_iter: niter=0 is the mix-phase estimate mask * X, which has no EM pass "
+                            "(xsq_slicqt_inverse_masked forms it)");
+    bool resident;
+    if ((rc = check_iter("xsq_wiener_em_masked_iter", nblocks, F, T, Bn, S, win_len, &batch_group, niter, method, ws_bytes, &resident)))
+        return rc;
+    if (resident) {
+        for (int b = 0; b < nblocks; ++b)
+            XSQ_REQUIRE(((int64_t)S * T[b]) % 2 == 0, "xsq_wiener_em_masked_iter: block %d has an odd frame count S*T=%lld", b, (long long)S * T[b]);
+        return run_resident(true, nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, niter, ws, (hipStream_t)stream_);
+    }
+    if ((rc = xsq_wiener_em_masked_ext(nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, stream_))) return rc;
+    return niter == 1 ? XSQ_OK : run_more_iterations(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, niter, ws, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -221,7 +221,18 @@ def _remix_one(audio, separator, rate, device, remix):
     return dict(zip(remix[0], mixes)), time.time() - start_time
 
 
-def inference_main(argv=None):
+def parse_args(p: argparse.ArgumentParser, argv=None):
+    """``p.parse_args`` plus the checks between options.  Host only."""
+    args = p.parse_args(argv)
+    if args.niter is not None:
+        if args.niter < 0:
+            p.error(f"--niter {args.niter}: the iteration count is >= 0")
+        if args.realtime:
+            p.error("--niter counts the EM iterations of the offline model's Wiener filter; --realtime is mix-phase and has none")
+    return args
+
+
+def cli_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="xumx-sliCQ-V2 inference on MI355X (hip-rocm backend)")
     p.add_argument("--input-dir", type=str, default="/input")
     p.add_argument("--output-dir", type=str, default="/output")
@@ -235,16 +246,24 @@ def inference_main(argv=None):
     p.add_argument("--remix", action="append", default=None, metavar="NAME:SPEC",
                    help="write <NAME>.wav = sum of the stems with the gains of SPEC (target=gain,...; unnamed targets keep 1.0) "
                         "instead of the four stems, e.g. karaoke:vocals=0; up to four times")
-    args = p.parse_args(argv)
+    p.add_argument("--niter", type=int, default=None, metavar="N",
+                   help="EM iterations of the Wiener post-filter of the offline model (default 1, the reference's; 0 = mix-phase); "
+                        "not with --realtime, which has no EM")
+    return p
+
+
+def inference_main(argv=None):
+    p = cli_parser()
+    args = parse_args(p, argv)
     try:
         remix = parse_remix_specs(args.remix)
     except ValueError as e:
         p.error(str(e))
     if args.model_path:
         separator = Separator.load(model_path=args.model_path, runtime_backend="hip-rocm",
-                                   warmup=args.warmup, realtime=args.realtime, device=args.device)
+                                   warmup=args.warmup, realtime=args.realtime, device=args.device, niter=args.niter)
     else:
-        separator = seeded_separator(realtime=args.realtime, device=args.device)
+        separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter)
     out_dir = Path(args.output_dir)
     wavs = sorted(Path(args.input_dir).glob(f"*{args.ext}"))
     if not args.serial:

@@ -229,6 +229,11 @@ class Unmix(nn.Module):
         self._T = np.asarray([s[1] for s in shapes], dtype=np.int32)
         self._handles = {}      # device index -> (version, handle)
         self._ws = {}
+        # EM iterations of the Wiener post-filter of an offline model (the `niter` of the Open-Unmix family; the reference pins
+        # 1, phase.py:53-58): read per call, as ``.realtime`` of the blocks.  0 = the mix-phase estimate.
+        self.niter = 1
+        # form of niter >= 2 ("auto", "looped", "resident": phase.wiener_em_arena); anything but "auto" is an A/B switch
+        self.niter_method = "auto"
         self.precision = os.environ.get("XSQ_CDAE_PRECISION", "fp32")
         if self.precision not in _PRECISIONS:
             raise ValueError(f"XSQ_CDAE_PRECISION={self.precision!r} not in {sorted(_PRECISIONS)}")
@@ -406,7 +411,8 @@ class Unmix(nn.Module):
 
     def forward(self, Xcomplex: List[Tensor], return_masks=False, wiener_batch_group: int = 0, xin_ready: bool = False):
         """list over blocks of (B, 2, F_b, S, T_b, 2) -> list of (4, B, 2, F_b, S, T_b, 2)
-        [+ masks (4, B, 2, F_b, S, T_b)].  model.py:69-82.  ``wiener_batch_group`` (extension):
+        [+ masks (4, B, 2, F_b, S, T_b)].  model.py:69-82.  An offline model runs ``self.niter`` EM iterations
+        (default 1, the reference's; 0 = mix-phase).  ``wiener_batch_group`` (extension):
         runs of that many batch items share the Wiener window maximum (0 = the whole batch, the
         reference's behaviour); Separator uses it to stack independent chunks along the batch."""
         from .phase import wiener_em_arena, wiener_em_masked_arena
@@ -419,7 +425,11 @@ class Unmix(nn.Module):
         modes = {bool(blk.realtime) for blk in self.sliced_umx}
         if len(modes) != 1:
             raise _lib.XsqError("mixed per-block post-filters (some mix-phase, some Wiener) are not supported")
-        phasemix = modes.pop()
+        niter = int(getattr(self, "niter", 1))
+        if niter < 0:
+            raise _lib.XsqError(f"Unmix.niter must be >= 0 (got {niter})")
+        method = getattr(self, "niter_method", "auto")
+        phasemix = modes.pop() or niter == 0           # no EM iteration: the initial estimate mask * X is the result
         # Wiener-EM from the masks (default): the last layer stores the real masks only and both EM passes form the
         # initial estimate mask * X while they load -- same bits, a third less traffic.  ``wiener_masked = False`` /
         # XSQ_WIENER_MASKED=0 restores the two-step form (layer 4 writes mask * X, the EM refines it in place).
@@ -437,9 +447,9 @@ class Unmix(nn.Module):
                 h, X.data_ptr(), B, S, None if masked else Y.data_ptr(), masks.data_ptr() if masks is not None else None,
                 ws.data_ptr(), ws.numel(), _lib.stream_ptr(), int(bool(xin_ready))), "xsq_cdae_forward")
             if masked:
-                wiener_em_masked_arena(self.table, X, masks, Y, B, S, batch_group=wiener_batch_group)
+                wiener_em_masked_arena(self.table, X, masks, Y, B, S, batch_group=wiener_batch_group, niter=niter, method=method)
             elif not phasemix:
-                wiener_em_arena(self.table, X, Y, B, S, batch_group=wiener_batch_group)
+                wiener_em_arena(self.table, X, Y, B, S, batch_group=wiener_batch_group, niter=niter, method=method)
         Ylist = self.table.views(Y, (4, B, 2), S)
         if return_masks:
             return Ylist, self.table.views(masks, (4, B, 2), S, complex_=False)

@@ -39,12 +39,45 @@ def _need_gpu(t: Tensor, who: str):
         raise _lib.XsqError(f"{who} runs on a ROCm device only (got '{t.device}'); there is no CPU fallback")
 
 
+METHODS = {"auto": 0, "looped": 1, "resident": 2}      # the forms of more than one EM iteration (xsq_wiener_em_iter)
+
+
+def _niter_method(niter, method):
+    niter = int(niter)
+    if niter < 0:
+        raise _lib.XsqError(f"niter must be >= 0 (got {niter})")
+    if method not in METHODS:
+        raise ValueError(f"method {method!r} not in {sorted(METHODS)}")
+    return niter, METHODS[method]
+
+
+def resident_max_window() -> int:
+    """Longest window (frames) the window-resident EM kernel holds on chip."""
+    return int(_lib.lib.xsq_wiener_resident_max_window())
+
+
 def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
-                    batch_group: int = 0):
-    """One EM iteration in place on the estimates arena Y (8B channels) given the
-    mix arena X (2B channels).  phase.py:43-59 + norbert/__init__.py:153-260.
-    ``batch_group``: runs of that many batch items share the window maximum (0 = whole batch)."""
+                    batch_group: int = 0, niter: int = 1, method: str = "auto"):
+    """``niter`` EM iterations in place on the estimates arena Y (8B channels) given the
+    mix arena X (2B channels).  phase.py:43-59 + norbert/__init__.py:153-260 (the reference calls it with one).
+    ``batch_group``: runs of that many batch items share the window maximum (0 = whole batch).
+    ``niter`` = 0 leaves Y alone, 1 is the reference's call; ``method`` ("auto", "looped", "resident") picks the form of
+    ``niter`` >= 2 (include/xumx_slicq_hip.h, xsq_wiener_em_iter)."""
+    niter, meth = _niter_method(niter, method)
+    if niter == 0:
+        return
     F, T = _tables(table)
+    if niter != 1:
+        with torch.cuda.device(X.device):
+            nbytes = _lib.lib.xsq_wiener_iter_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len, niter, meth)
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_wiener_iter_workspace: bad arguments")
+            ws = _workspace(X.device, nbytes)
+            _lib.check(_lib.lib.xsq_wiener_em_iter(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), Y.data_ptr(),
+                                                   B, S, win_len, int(batch_group), niter, meth, ws.data_ptr(), ws.numel(),
+                                                   _lib.stream_ptr()),
+                       "xsq_wiener_em_iter")
+        return
     with torch.cuda.device(X.device):
         nbytes = _lib.lib.xsq_wiener_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len)
         if nbytes == 0:
@@ -57,11 +90,24 @@ def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win
 
 
 def wiener_em_masked_arena(table: BlockTable, X: Tensor, masks: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
-                           batch_group: int = 0):
+                           batch_group: int = 0, niter: int = 1, method: str = "auto"):
     """The same iteration fed by the sigmoid masks (real arena, 8B channels): the initial estimate mask * X
     (model.py:262-264) is formed while the two passes load, Y (8B channels, complex) is only written.
-    Same bits as ``xsq_cdae_forward(Y)`` + ``wiener_em_arena``; a third less HBM traffic."""
+    Same bits as ``xsq_cdae_forward(Y)`` + ``wiener_em_arena``; a third less HBM traffic.  ``niter`` >= 1, ``method``:
+    as ``wiener_em_arena``."""
+    niter, meth = _niter_method(niter, method)
     F, T = _tables(table)
+    if niter != 1:
+        with torch.cuda.device(X.device):
+            nbytes = _lib.lib.xsq_wiener_iter_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len, niter, meth)
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_wiener_iter_workspace: bad arguments")
+            ws = _workspace(X.device, nbytes)
+            _lib.check(_lib.lib.xsq_wiener_em_masked_iter(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), masks.data_ptr(),
+                                                          Y.data_ptr(), B, S, win_len, int(batch_group), None, niter, meth,
+                                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                       "xsq_wiener_em_masked_iter")
+        return
     with torch.cuda.device(X.device):
         nbytes = _lib.lib.xsq_wiener_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len)
         if nbytes == 0:
@@ -96,14 +142,17 @@ def blockwise_phasemix_sep(X_block: Tensor, Ymag_block: Tensor) -> Tensor:
     return Y
 
 
-def blockwise_wiener(mix_slicqt: Tensor, slicqtgrams: Tensor, wiener_win_len_param: int = 5000) -> Tensor:
-    """phase.py:18-69.  (B,2,F,S,T,2), (4,B,2,F,S,T) -> (4,B,2,F,S,T,2)."""
+def blockwise_wiener(mix_slicqt: Tensor, slicqtgrams: Tensor, wiener_win_len_param: int = 5000, niter: int = 1,
+                     method: str = "auto") -> Tensor:
+    """phase.py:18-69.  (B,2,F,S,T,2), (4,B,2,F,S,T) -> (4,B,2,F,S,T,2).  ``niter`` (extension; the reference pins 1): the
+    iteration count of norbert.wiener, 0 = the mix-phase estimate; ``method``: "auto", "looped" or "resident" for
+    ``niter`` >= 2 (``wiener_em_arena``)."""
     table, B, S = _one_block(mix_slicqt, slicqtgrams)
     X = mix_slicqt.contiguous().float()
     Y = blockwise_phasemix_sep(X, slicqtgrams)
     nb_frames = S * mix_slicqt.shape[4]
     win = int(wiener_win_len_param) if wiener_win_len_param else nb_frames
-    wiener_em_arena(table, X.view(-1), Y.view(-1), B, S, win)
+    wiener_em_arena(table, X.view(-1), Y.view(-1), B, S, win, niter=niter, method=method)
     return Y
 
 
@@ -112,9 +161,9 @@ def abs_of_real_complex(Xcomplex_real_view: Tensor) -> Tensor:
     return torch.sqrt(Xcomplex_real_view[..., 0] ** 2 + Xcomplex_real_view[..., 1] ** 2)
 
 
-def wiener(mix_slicqt: List[Tensor], slicqtgrams: List[Tensor], wiener_win_len: int = 5000):
+def wiener(mix_slicqt: List[Tensor], slicqtgrams: List[Tensor], wiener_win_len: int = 5000, niter: int = 1, method: str = "auto"):
     """phase.py:7-15."""
-    return [blockwise_wiener(m, s, wiener_win_len) for m, s in zip(mix_slicqt, slicqtgrams)]
+    return [blockwise_wiener(m, s, wiener_win_len, niter, method) for m, s in zip(mix_slicqt, slicqtgrams)]
 
 
 def phasemix_sep(X: List[Tensor], Ymag: List[Tensor]):

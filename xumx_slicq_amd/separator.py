@@ -35,8 +35,8 @@ class Separator(nn.Module):
     @classmethod
     def load(cls, chunk_size: int = 2621440, model_path: Optional[str] = None,
              runtime_backend: Optional[str] = _ACCELERATED, warmup: int = 0, realtime: bool = False,
-             device: Union[str, torch.device] = "cuda"):
-        """separator.py:50-93."""
+             device: Union[str, torch.device] = "cuda", niter: Optional[int] = None):
+        """separator.py:50-93.  ``niter`` (extension): EM iterations of the Wiener post-filter, see ``Separator.niter``."""
         if runtime_backend not in _SUPPORTED_RUNTIMES:
             raise ValueError(f"requested runtime backend {runtime_backend} not in {_SUPPORTED_RUNTIMES}")
         xumx_model, encoder, sample_rate = load_target_models(
@@ -44,6 +44,8 @@ class Separator(nn.Module):
         separator = cls(xumx_model=xumx_model, encoder=encoder, sample_rate=sample_rate,
                         runtime_backend=runtime_backend, chunk_size=chunk_size, device=device).to(device)
         separator.freeze()
+        if niter is not None:
+            separator.niter = niter
         for _ in range(warmup):
             waveform = torch.rand((1, 2, int(100 * sample_rate)), dtype=torch.float32, device=device)
             separator.forward(waveform)
@@ -72,6 +74,20 @@ class Separator(nn.Module):
         self.xumx_model.freeze()
         self.eval()
 
+    @property
+    def niter(self) -> int:
+        """EM iterations of the Wiener post-filter of an offline model: the ``niter`` of the Open-Unmix family,
+        ``iterations`` of norbert.wiener (the reference pins 1, phase.py:53-58).  Lives on the model (``Unmix.niter``), read
+        per call; 0 = the mix-phase estimate.  A realtime (mix-phase) model has no EM and ignores it."""
+        return int(getattr(self.xumx_model, "niter", 1))
+
+    @niter.setter
+    def niter(self, value: int):
+        value = int(value)
+        if value < 0:
+            raise ValueError(f"niter must be >= 0 (got {value})")
+        self.xumx_model.niter = value
+
     def _graph_key(self, audio_big: Tensor):
         """Everything a captured forward depends on besides the input values: shape and device, the chunking
         switches, the packed-parameter version of the model (captured kernels hold raw pointers into the
@@ -84,7 +100,7 @@ class Separator(nn.Module):
                 bool(getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0")),
                 bool(getattr(m, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")), self._packed_fft(),
                 bool(getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0")), int(getattr(self, "max_item_slices", 0)),
-                int(getattr(m, "winograd", 7)))
+                int(getattr(m, "winograd", 7)), self.niter, getattr(m, "niter_method", "auto"))
 
     def drop_graphs(self):
         """Forget every captured forward (they hold raw pointers into the model handle and the workspaces)."""
@@ -279,7 +295,8 @@ class Separator(nn.Module):
     # -- the native whole-call path ---------------------------------------------------------------------------
     def _native_mode(self, audio: Tensor):
         """None when this call has to take the Python chunk loop (an A/B switch is off its default, a mixed or
-        non-stereo model), else the post-filter of the native call: 0 mix-phase, 1 Wiener-EM."""
+        non-stereo model), else the post-filter of the native call: 0 mix-phase, k >= 1 Wiener-EM of k iterations
+        (``niter``; 0 on an offline model is mix-phase)."""
         if not getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0"):
             return None
         if audio.dim() != 3 or audio.shape[1] != 2 or audio.device.type != "cuda" or audio.shape[-1] < 1:
@@ -287,12 +304,13 @@ class Separator(nn.Module):
         if not (getattr(self, "batch_chunks", True) and int(getattr(self, "pass_streams", 1)) == 1
                 and getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0")
                 and getattr(self, "fuse_phasemix", os.environ.get("XSQ_FUSE_PHASEMIX", "1") != "0")
-                and getattr(self.xumx_model, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")):
+                and getattr(self.xumx_model, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")
+                and getattr(self.xumx_model, "niter_method", "auto") == "auto"):
             return None
         modes = {bool(b.realtime) for b in self.xumx_model.sliced_umx}
         if len(modes) != 1:
             return None
-        return 0 if modes.pop() else 1
+        return 0 if modes.pop() else self.niter
 
     def _native_ws(self, dev: torch.device, stream_ptr: int, which: str, nbytes: int) -> Tensor:
         """Grow-only workspace of the native path per (device, stream, main | tail).  PyTorch owns the memory."""
@@ -576,7 +594,7 @@ def load_target_models(model_path: str, runtime_backend: str = _ACCELERATED, rea
 
 
 def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed: int = 1234,
-                     device="cuda", chunk_size: int = 2621440, **cfg) -> Separator:
+                     device="cuda", chunk_size: int = 2621440, niter: Optional[int] = None, **cfg) -> Separator:
     """Separator with the seeded synthetic weights (no checkpoint exists offline).
     ``wiener`` overrides the post-filter: None follows the reference (offline -> Wiener-EM,
     realtime -> mix-phase); False on the offline stack is BASELINE config 2."""
@@ -588,4 +606,6 @@ def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed
     sep = Separator(xumx_model=xumx_model, encoder=encoder, sample_rate=sr, chunk_size=chunk_size,
                     device=device, quiet=True).to(device)
     sep.freeze()
+    if niter is not None:
+        sep.niter = niter
     return sep

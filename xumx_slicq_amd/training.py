@@ -65,6 +65,10 @@ class Trainer:
         if len(causal) != 1 or len(wiener) != 1:
             raise _lib.XsqError("all blocks must share the same first-layer type and post-filter")
         self.causal, self.wiener = causal.pop(), wiener.pop()
+        if self.wiener and int(getattr(unmix, "niter", 1)) != 1:
+            raise _lib.XsqError(f"training differentiates ONE Wiener-EM iteration (the reference trains with iterations=1, and the "
+                                f"backward kernels are the gradient of one); this model has niter = {unmix.niter}: set it to 1 "
+                                "to train and back afterwards")
         self._spec = [(k, tuple(v.shape)) for k, v in unmix.state_dict().items() if not k.endswith("num_batches_tracked")]
         params = unmix.packed_parameters()
         self.nparams = int(params.size)
