@@ -1,4 +1,4 @@
-// Mix-phase estimate and norbert Wiener-EM (one iteration) on the coefficient arena, gfx950.
+// Mix-phase estimate and norbert Wiener-EM on the coefficient arena, gfx950.
 //
 // Reference: xumx_slicq_v2/phase.py:18-69 (blockwise_wiener: windows of <= 5000 frames over the
 // flattened (slice, time) axis), :96-113 (blockwise_phasemix_sep); norbert/__init__.py:153-260
@@ -15,6 +15,16 @@
 // Three launches: k_wiener_stats (raw sums + max per row/window, fixed-order LDS tree, no atomics
 // -> bitwise reproducible), k_wiener_finalize (window max, R), k_wiener_apply (elementwise 2x2
 // solve, in place on Y).  All reads/writes are contiguous along the frame axis.
+//
+// The arithmetic is written once, in wiener_math.h: the sums of a frame, the workgroup reduction, sums -> R, Cxx^-1 and
+// y_j = v_j R_j z.  The kernels here differ in where the estimates come from and where the results go:
+//   k_wiener_stats<YFrom>    Estimates: the arena Y | Masks: mask * mix, formed on the way in | Current: Y again, in a later
+//                            iteration (no maximum; R straight from the sums with the 1/ma^2 of iteration 1)
+//   k_wiener_apply[_masked]  one / two frames per thread through wiener_point
+//   k_wiener_bwd_*           the backward of one iteration (training)
+//   k_wiener_resident        all iterations of a window on chip (wiener_iter.h)
+// and the host side has one path: check_em -> run_em (the three launches) / run_resident, then run_more_iterations.
+//
 // More iterations (niter of the Open-Unmix family; norbert/__init__.py:133-148 loops, :247-260 scales ONCE
 // around the loop): xsq_wiener_em_iter / xsq_wiener_em_masked_iter below.  niter = 1 runs exactly the three
 // launches above.  niter >= 2 runs either the looped form (iteration 1 as above, then per iteration the
@@ -29,22 +39,10 @@
 #include "../../include/xumx_slicq_hip.h"
 #include "plan.h"
 #include "prof.h"
+#include "wiener_iter.h"
+#include "wiener_math.h"
 
 namespace xsq {
-
-static const int STAT = 24;   // floats per (row, window): 4 sources x (C00, C11, Re C01, Im C01), max|x|^2, pad[3],
-                              // 4 x 1/(sum_n v + eps) (kept for the backward pass)
-
-struct WRow {          // one (block, batch item, bin) row of the arena
-    int F, T;          // block geometry
-    int b, f;          // batch item, bin
-    int nwin;          // windows of this block
-    int first_row;     // first row index of this row's block (rows of a block are consecutive)
-    int nrows;         // rows in the block (B*F)
-    int pad;
-    int64_t cum;       // sum over earlier blocks of F*T
-    int64_t stat;      // float offset of this row's window 0 in the stats buffer
-};
 
 struct WTable {
     WRow* d_rows = nullptr;
@@ -52,20 +50,11 @@ struct WTable {
     int nrows = 0, nwork = 0, nblockwin = 0;
     int* d_blockwin = nullptr; // (first_row, window) per (block, window)
     int* d_bw_of_work = nullptr;   // per (row, window) work item: index of its (block, group, window) in d_blockwin order
-    int64_t stat_floats = 0;
     int64_t max_frames = 0;
 };
 
 static std::mutex g_wmu;
 static std::map<std::vector<int>, WTable> g_wtables;
-
-__device__ inline float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ inline float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }  // a * conj(b)
-
-// complex arena index of (chan, f, frame n) for a block; nchan = packed channels of the arena
-__device__ inline int64_t cidx(const WRow& r, int nchan, int S, int chan, int64_t n) {
-    return (int64_t)nchan * S * r.cum + ((int64_t)chan * r.F + r.f) * ((int64_t)S * r.T) + n;
-}
 
 // ---- Y = mag * x/|x|  (phase.py:96-113; angle(0) = 0) --------------------------------------------
 __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, const float* __restrict__ mag,
@@ -77,12 +66,12 @@ __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, 
     if (n >= N) return;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-        const float2 x = X[cidx(r, 2 * Bn, S, r.b * 2 + c, n)];
+        const float2 x = X[aidx(r, 2 * Bn, S, r.b * 2 + c, n)];
         const float ax = sqrtf(x.x * x.x + x.y * x.y);
         const float2 u = ax > 0.f ? make_float2(x.x / ax, x.y / ax) : make_float2(1.f, 0.f);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int64_t yi = cidx(r, 8 * Bn, S, (j * Bn + r.b) * 2 + c, n);
+            const int64_t yi = aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2 + c, n);
             const float m = mag[yi];
             Y[yi] = make_float2(m * u.x, m * u.y);
         }
@@ -90,52 +79,57 @@ __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, 
 }
 
 // ---- pass 1: raw sums and max per (row, window).  One workgroup per (row, window). -----------------
+// Lane t adds frames n0 + t, n0 + t + 256, ... in order, whatever the source: the sums round identically.
+//   Estimates  y = Y[n]: 80 B per time-frequency point.
+//   Masks      y = mask * x, the products the CDAE's layer-4 epilogue would have stored (one fp32 rounding each): the layer
+//              then writes 4 bytes per coefficient instead of 8 and this pass reads 48 B.  Bitwise the two-step result.
+//   Current    y = Y[n] in iterations >= 2 of the looped form.  st[16] holds 1/ma^2 (k_wiener_finalize of iteration 1) and is
+//              left alone; st[0..15] become R, st[20..23] the denominators: the arithmetic of k_wiener_finalize.
+enum class YFrom { Estimates, Masks, Current };
+
+template <YFrom SRC>
 __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__ X, const float2* __restrict__ Y,
-                                                       const WRow* __restrict__ rows, const int* __restrict__ work,
-                                                       float* __restrict__ stats, int Bn, int S, int win_len) {
+                                                       const float* __restrict__ Mk, const WRow* __restrict__ rows,
+                                                       const int* __restrict__ work, float* __restrict__ stats, int Bn, int S,
+                                                       int win_len) {
+    constexpr bool MAX = SRC != YFrom::Current;
+    constexpr int NV = MAX ? 17 : 16;
     const int row = work[2 * blockIdx.x], w = work[2 * blockIdx.x + 1];
     const WRow r = rows[row];
-    const int64_t N = (int64_t)S * r.T;
-    const int64_t n0 = (int64_t)w * win_len;
-    const int64_t n1 = n0 + win_len < N ? n0 + win_len : N;
-    float acc[17];
+    const WWin W = window_of(r, S, w, win_len);
+    float acc[NV];
 #pragma unroll
-    for (int i = 0; i < 17; ++i) acc[i] = 0.f;
-    const float2* x0 = X + cidx(r, 2 * Bn, S, r.b * 2, 0);
-    const float2* x1 = X + cidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += 256) {
-        const float2 a = x0[n], b = x1[n];
-        acc[16] = fmaxf(acc[16], fmaxf(a.x * a.x + a.y * a.y, b.x * b.x + b.y * b.y));
+    for (int i = 0; i < NV; ++i) acc[i] = 0.f;
+    const float2* x0 = X + aidx(r, 2 * Bn, S, r.b * 2, 0);
+    const float2* x1 = X + aidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
+    const int64_t base = aidx(r, 8 * Bn, S, r.b * 2, 0);                 // target 0, channel 0 of this row
+    const int64_t cstride = (int64_t)r.F * W.N, jstride = (int64_t)Bn * 2 * cstride;
+    for (int64_t n = W.n0 + threadIdx.x; n < W.n1; n += 256) {
+        float2 a, b;
+        if constexpr (MAX) {
+            a = x0[n], b = x1[n];
+            acc[NV - 1] = fmaxf(acc[NV - 1], fmaxf(abs2(a), abs2(b)));
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float2 y0 = Y[cidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n)];
-            const float2 y1 = Y[cidx(r, 8 * Bn, S, (j * Bn + r.b) * 2 + 1, n)];
-            const float2 c01 = cmulc(y0, y1);
-            acc[4 * j + 0] += y0.x * y0.x + y0.y * y0.y;
-            acc[4 * j + 1] += y1.x * y1.x + y1.y * y1.y;
-            acc[4 * j + 2] += c01.x;
-            acc[4 * j + 3] += c01.y;
+            const int64_t i = base + j * jstride + n;
+            if constexpr (SRC == YFrom::Masks) {
+                const float ma = Mk[i], mb = Mk[i + cstride];
+                accumulate(acc, j, make_float2(ma * a.x, ma * a.y), make_float2(mb * b.x, mb * b.y));
+            } else {
+                accumulate(acc, j, Y[i], Y[i + cstride]);
+            }
         }
     }
-    // wavefront butterfly, then a fixed-order sum of the 4 wave partials
-    __shared__ float red[4][17];
-#pragma unroll
-    for (int i = 0; i < 17; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float o = __shfl_xor(v, off, 64);
-            v = (i == 16) ? fmaxf(v, o) : v + o;
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 17) {
-        const int i = threadIdx.x;
-        float v;
-        if (i == 16) v = fmaxf(fmaxf(red[0][i], red[1][i]), fmaxf(red[2][i], red[3][i]));
-        else v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-        stats[r.stat + (int64_t)w * STAT + i] = v;
+    __shared__ float red[4][NV];
+    float* st = stats + r.stat + (int64_t)w * STAT;
+    if constexpr (MAX) {
+        reduce<4>(acc, red, st);
+    } else {
+        __shared__ float tot[16];
+        reduce<4>(acc, red, tot);
+        __syncthreads();
+        if (threadIdx.x < 4) sums_to_R_slot(st, threadIdx.x, tot, st[16]);
     }
 }
 
@@ -159,19 +153,10 @@ __global__ __launch_bounds__(256) void k_wiener_finalize(const WRow* __restrict_
     const float mx2 = ext_max ? fmaxf(smax[0], ext_max[blockIdx.x]) : smax[0];
     const float ma = fmaxf(1.f, 0.1f * sqrtf(mx2));         // norbert :257
     const float inv_ma2 = 1.f / (ma * ma);
-    const float eps = FLT_EPSILON;
     for (int i = threadIdx.x; i < nrows; i += 256) {
         float* st = stats + rows[first + i].stat + (int64_t)w * STAT;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float c00 = st[4 * j] * inv_ma2, c11 = st[4 * j + 1] * inv_ma2;
-            const float den = 1.f / (0.5f * (c00 + c11) + eps);   // sum_n mean_c |y'|^2 + eps   (:491-493)
-            st[4 * j] = c00 * den;
-            st[4 * j + 1] = c11 * den;
-            st[4 * j + 2] = st[4 * j + 2] * inv_ma2 * den;
-            st[4 * j + 3] = st[4 * j + 3] * inv_ma2 * den;
-            st[20 + j] = den;
-        }
+        for (int j = 0; j < 4; ++j) sums_to_R_slot(st, j, st, inv_ma2);
         st[16] = inv_ma2;
     }
 }
@@ -185,146 +170,26 @@ __global__ __launch_bounds__(256) void k_wiener_apply(const float2* __restrict__
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     const float* st = stats + r.stat + (n / win_len) * STAT;
-    const float inv_ma2 = st[16];
-    const float2 x0 = X[cidx(r, 2 * Bn, S, r.b * 2, n)];
-    const float2 x1 = X[cidx(r, 2 * Bn, S, r.b * 2 + 1, n)];
-    float v[4];
-    float2 R01[4];
-    float R00[4], R11[4];
+    const float2 x0 = X[aidx(r, 2 * Bn, S, r.b * 2, n)];
+    const float2 x1 = X[aidx(r, 2 * Bn, S, r.b * 2 + 1, n)];
+    float2 y[4][2], o[4][2];
     int64_t yi[4];
-    const float reg = sqrtf(FLT_EPSILON);
-    float c00 = reg, c11 = reg;
-    float2 c01 = make_float2(0.f, 0.f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        yi[j] = cidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n);
-        const float2 y0 = Y[yi[j]];
-        const float2 y1 = Y[yi[j] + (int64_t)r.F * N];
-        v[j] = 0.5f * ((y0.x * y0.x + y0.y * y0.y) * inv_ma2 + (y1.x * y1.x + y1.y * y1.y) * inv_ma2);
-        R00[j] = st[4 * j]; R11[j] = st[4 * j + 1]; R01[j] = make_float2(st[4 * j + 2], st[4 * j + 3]);
-        c00 += v[j] * R00[j];
-        c11 += v[j] * R11[j];
-        c01.x += v[j] * R01[j].x;
-        c01.y += v[j] * R01[j].y;
+        yi[j] = aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n);
+        y[j][0] = Y[yi[j]];
+        y[j][1] = Y[yi[j] + (int64_t)r.F * N];
     }
-    // Cxx = [[c00, c01], [conj(c01), c11]];  analytic inverse (norbert _invert :337-346)
-    const float det = c00 * c11 - (c01.x * c01.x + c01.y * c01.y);
-    const float idet = 1.f / det;
-    const float i00 = c11 * idet, i11 = c00 * idet;
-    const float2 i01 = make_float2(-c01.x * idet, -c01.y * idet);    // -c01/det
-    const float2 i10 = make_float2(-c01.x * idet, c01.y * idet);     // -conj(c01)/det
-    // z = Cxx^-1 x
-    const float2 z0 = make_float2(i00 * x0.x + (i01.x * x1.x - i01.y * x1.y), i00 * x0.y + (i01.x * x1.y + i01.y * x1.x));
-    const float2 z1 = make_float2((i10.x * x0.x - i10.y * x0.y) + i11 * x1.x, (i10.x * x0.y + i10.y * x0.x) + i11 * x1.y);
+    wiener_point(st, x0, x1, y, o);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        // y_j = v_j R_j z ;  R_j = [[R00, R01], [conj(R01), R11]]
-        const float2 a = cmul(R01[j], z1);
-        const float2 b = cmulc(z0, R01[j]);      // conj(R01) * z0
-        Y[yi[j]] = make_float2(v[j] * (R00[j] * z0.x + a.x), v[j] * (R00[j] * z0.y + a.y));
-        Y[yi[j] + (int64_t)r.F * N] = make_float2(v[j] * (b.x + R11[j] * z1.x), v[j] * (b.y + R11[j] * z1.y));
+        Y[yi[j]] = o[j][0];
+        Y[yi[j] + (int64_t)r.F * N] = o[j][1];
     }
 }
 
-// ---- the same two passes fed by MASKS: y0 = mask * x is formed on the way in ---------------------------------
-// The CDAE's last layer then writes 4 bytes per coefficient instead of 8 (and does not read the mix), pass 1 reads
-// 48 instead of 80 bytes per time-frequency point, pass 3 reads 48 and writes 64 instead of 80 + 64.  The products
-// mask * re, mask * im are the ones the layer-4 epilogue would have stored (one fp32 rounding each), and everything
-// downstream is the same expression tree: bitwise the two-step result.  Two frames per thread (N = S*T and the
+// The same pass fed by masks: pass 3 reads 48 B and writes 64 B instead of 80 + 64.  Two frames per thread (N = S*T and the
 // window length are even on this path): 16-byte loads of the mix, 8-byte loads of the masks, 16-byte stores.
-__device__ inline int64_t ridx(const WRow& r, int nchan, int S, int chan, int64_t n) {      // real arena (masks)
-    return (int64_t)nchan * S * r.cum + ((int64_t)chan * r.F + r.f) * ((int64_t)S * r.T) + n;
-}
-
-__global__ __launch_bounds__(256) void k_wiener_stats_masked(const float2* __restrict__ X, const float* __restrict__ Mk,
-                                                              const WRow* __restrict__ rows, const int* __restrict__ work,
-                                                              float* __restrict__ stats, int Bn, int S, int win_len) {
-    const int row = work[2 * blockIdx.x], w = work[2 * blockIdx.x + 1];
-    const WRow r = rows[row];
-    const int64_t N = (int64_t)S * r.T;
-    const int64_t n0 = (int64_t)w * win_len;
-    const int64_t n1 = n0 + win_len < N ? n0 + win_len : N;
-    float acc[17];
-#pragma unroll
-    for (int i = 0; i < 17; ++i) acc[i] = 0.f;
-    const float2* x0 = X + cidx(r, 2 * Bn, S, r.b * 2, 0);
-    const float2* x1 = X + cidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
-    const float* m0 = Mk + ridx(r, 8 * Bn, S, r.b * 2, 0);            // target 0, channel 0 of this row
-    const int64_t cstride = (int64_t)r.F * N, jstride = (int64_t)Bn * 2 * cstride;
-    // The reduction keeps the two-step kernel's shape -- lane t adds frames n0 + t, n0 + t + 256, ... in order -- so the
-    // sums round identically; the pair (t, t + 256) is what one thread of THIS kernel owns per 512-frame step.
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += 256) {
-        const float2 a = x0[n], b = x1[n];
-        acc[16] = fmaxf(acc[16], fmaxf(a.x * a.x + a.y * a.y, b.x * b.x + b.y * b.y));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float ma = m0[j * jstride + n], mb = m0[j * jstride + cstride + n];
-            const float2 y0 = make_float2(ma * a.x, ma * a.y);
-            const float2 y1 = make_float2(mb * b.x, mb * b.y);
-            const float2 c01 = cmulc(y0, y1);
-            acc[4 * j + 0] += y0.x * y0.x + y0.y * y0.y;
-            acc[4 * j + 1] += y1.x * y1.x + y1.y * y1.y;
-            acc[4 * j + 2] += c01.x;
-            acc[4 * j + 3] += c01.y;
-        }
-    }
-    __shared__ float red[4][17];
-#pragma unroll
-    for (int i = 0; i < 17; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float o = __shfl_xor(v, off, 64);
-            v = (i == 16) ? fmaxf(v, o) : v + o;
-        }
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 17) {
-        const int i = threadIdx.x;
-        float v;
-        if (i == 16) v = fmaxf(fmaxf(red[0][i], red[1][i]), fmaxf(red[2][i], red[3][i]));
-        else v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-        stats[r.stat + (int64_t)w * STAT + i] = v;
-    }
-}
-
-// one time-frequency point of pass 3 (shared by both apply kernels: same expression tree, same bits)
-__device__ inline void wiener_point(const float* __restrict__ st, float2 x0, float2 x1, const float2 (&y)[4][2],
-                                    float2 (&o)[4][2]) {
-    const float inv_ma2 = st[16];
-    float v[4];
-    float2 R01[4];
-    float R00[4], R11[4];
-    const float reg = sqrtf(FLT_EPSILON);
-    float c00 = reg, c11 = reg;
-    float2 c01 = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float2 y0 = y[j][0], y1 = y[j][1];
-        v[j] = 0.5f * ((y0.x * y0.x + y0.y * y0.y) * inv_ma2 + (y1.x * y1.x + y1.y * y1.y) * inv_ma2);
-        R00[j] = st[4 * j]; R11[j] = st[4 * j + 1]; R01[j] = make_float2(st[4 * j + 2], st[4 * j + 3]);
-        c00 += v[j] * R00[j];
-        c11 += v[j] * R11[j];
-        c01.x += v[j] * R01[j].x;
-        c01.y += v[j] * R01[j].y;
-    }
-    const float det = c00 * c11 - (c01.x * c01.x + c01.y * c01.y);
-    const float idet = 1.f / det;
-    const float i00 = c11 * idet, i11 = c00 * idet;
-    const float2 i01 = make_float2(-c01.x * idet, -c01.y * idet);
-    const float2 i10 = make_float2(-c01.x * idet, c01.y * idet);
-    const float2 z0 = make_float2(i00 * x0.x + (i01.x * x1.x - i01.y * x1.y), i00 * x0.y + (i01.x * x1.y + i01.y * x1.x));
-    const float2 z1 = make_float2((i10.x * x0.x - i10.y * x0.y) + i11 * x1.x, (i10.x * x0.y + i10.y * x0.x) + i11 * x1.y);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float2 a = cmul(R01[j], z1);
-        const float2 b = cmulc(z0, R01[j]);
-        o[j][0] = make_float2(v[j] * (R00[j] * z0.x + a.x), v[j] * (R00[j] * z0.y + a.y));
-        o[j][1] = make_float2(v[j] * (b.x + R11[j] * z1.x), v[j] * (b.y + R11[j] * z1.y));
-    }
-}
-
 __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __restrict__ X, const float* __restrict__ Mk,
                                                               float2* __restrict__ Y, const WRow* __restrict__ rows,
                                                               const float* __restrict__ stats, int Bn, int S, int win_len) {
@@ -333,10 +198,10 @@ __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __res
     const int64_t n = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);       // frames n, n + 1 (same window: both even)
     if (n >= N) return;
     const float* st = stats + r.stat + (n / win_len) * STAT;
-    const float4 xa = *reinterpret_cast<const float4*>(X + cidx(r, 2 * Bn, S, r.b * 2, n));
-    const float4 xb = *reinterpret_cast<const float4*>(X + cidx(r, 2 * Bn, S, r.b * 2 + 1, n));
+    const float4 xa = *reinterpret_cast<const float4*>(X + aidx(r, 2 * Bn, S, r.b * 2, n));
+    const float4 xb = *reinterpret_cast<const float4*>(X + aidx(r, 2 * Bn, S, r.b * 2 + 1, n));
     const int64_t cstride = (int64_t)r.F * N, jstride = (int64_t)Bn * 2 * cstride;
-    const float* m0 = Mk + ridx(r, 8 * Bn, S, r.b * 2, n);
+    const float* m0 = Mk + aidx(r, 8 * Bn, S, r.b * 2, n);
     float2 ma[4], mb[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -356,7 +221,7 @@ __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __res
         y[j][1] = make_float2(mb[j].y * xb.z, mb[j].y * xb.w);
     }
     wiener_point(st, make_float2(xa.z, xa.w), make_float2(xb.z, xb.w), y, o1);
-    float2* y0p = Y + cidx(r, 8 * Bn, S, r.b * 2, n);
+    float2* y0p = Y + aidx(r, 8 * Bn, S, r.b * 2, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         *reinterpret_cast<float4*>(y0p + j * jstride) = make_float4(o0[j][0].x, o0[j][0].y, o1[j][0].x, o1[j][0].y);
@@ -378,39 +243,30 @@ struct WPoint {
     float2 w0, w1;
 };
 
+
 __device__ inline void wiener_bwd_point(const float* __restrict__ st, float2 x0, float2 x1, const float2 (&y)[4][2],
                                         const float2 (&g)[4][2], WPoint& P) {
     const float inv_ma2 = st[16];
-    const float reg = sqrtf(FLT_EPSILON);
-    float c00 = reg, c11 = reg;
-    float2 c01 = make_float2(0.f, 0.f);
-    float R00[4], R11[4];
-    float2 R01[4];
+    WR R;
+    load_R(st, R);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        P.v[j] = 0.5f * ((y[j][0].x * y[j][0].x + y[j][0].y * y[j][0].y) * inv_ma2 +
-                         (y[j][1].x * y[j][1].x + y[j][1].y * y[j][1].y) * inv_ma2);
-        R00[j] = st[4 * j]; R11[j] = st[4 * j + 1]; R01[j] = make_float2(st[4 * j + 2], st[4 * j + 3]);
-        c00 += P.v[j] * R00[j];
-        c11 += P.v[j] * R11[j];
-        c01.x += P.v[j] * R01[j].x;
-        c01.y += P.v[j] * R01[j].y;
-    }
-    const float idet = 1.f / (c00 * c11 - (c01.x * c01.x + c01.y * c01.y));
-    const float i00 = c11 * idet, i11 = c00 * idet;
-    const float2 i01 = make_float2(-c01.x * idet, -c01.y * idet);
-    auto solve = [&](float2 a0, float2 a1, float2& o0, float2& o1) {      // Cxx^-1 a
-        const float2 t = cmul(i01, a1), s = cmulc(a0, i01);               // i10 = conj(i01)
-        o0 = make_float2(i00 * a0.x + t.x, i00 * a0.y + t.y);
-        o1 = make_float2(s.x + i11 * a1.x, s.y + i11 * a1.y);
+    for (int j = 0; j < 4; ++j) P.v[j] = power(y[j][0], y[j][1], inv_ma2);
+    const WInv I = invert_cxx(R, P.v);
+    // Cxx^-1 a with i10 written as conj(i01): the same values as solve() of the forward pass with one multiply fewer; kept
+    // so that the backward kernels' instructions stay what they were
+    auto solve = [&](float2 a0, float2 a1, float2& o0, float2& o1) {
+        const float2 t = cmul(I.i01, a1), s = cmulc(a0, I.i01);
+        o0 = make_float2(I.i00 * a0.x + t.x, I.i00 * a0.y + t.y);
+        o1 = make_float2(s.x + I.i11 * a1.x, s.y + I.i11 * a1.y);
     };
     solve(x0, x1, P.w0, P.w1);
     float2 q0 = make_float2(0.f, 0.f), q1 = q0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {       // R_j gO_j
-        const float2 a = cmul(R01[j], g[j][1]), b = cmulc(g[j][0], R01[j]);
-        q0.x += P.v[j] * (R00[j] * g[j][0].x + a.x); q0.y += P.v[j] * (R00[j] * g[j][0].y + a.y);
-        q1.x += P.v[j] * (b.x + R11[j] * g[j][1].x); q1.y += P.v[j] * (b.y + R11[j] * g[j][1].y);
+    for (int j = 0; j < 4; ++j) {       // v_j R_j gO_j
+        float2 a, b;
+        source(R, j, P.v[j], g[j][0], g[j][1], a, b);
+        q0.x += a.x; q0.y += a.y;
+        q1.x += b.x; q1.y += b.y;
     }
     float2 p0, p1;
     solve(q0, q1, p0, p1);
@@ -418,9 +274,8 @@ __device__ inline void wiener_bwd_point(const float* __restrict__ st, float2 x0,
     for (int j = 0; j < 4; ++j) {
         P.u[j][0] = make_float2(g[j][0].x - p0.x, g[j][0].y - p0.y);
         P.u[j][1] = make_float2(g[j][1].x - p1.x, g[j][1].y - p1.y);
-        const float2 a = cmul(R01[j], P.w1), b = cmulc(P.w0, R01[j]);
-        const float2 rw0 = make_float2(R00[j] * P.w0.x + a.x, R00[j] * P.w0.y + a.y);
-        const float2 rw1 = make_float2(b.x + R11[j] * P.w1.x, b.y + R11[j] * P.w1.y);
+        float2 rw0, rw1;
+        mul_R(R, j, P.w0, P.w1, rw0, rw1);
         P.gv[j] = (P.u[j][0].x * rw0.x + P.u[j][0].y * rw0.y) + (P.u[j][1].x * rw1.x + P.u[j][1].y * rw1.y);
     }
 }
@@ -430,11 +285,11 @@ __device__ inline void wiener_load_point(const float2* __restrict__ X, const flo
                                          const float2* __restrict__ G, const WRow& r, int Bn, int S, int64_t n,
                                          float2& x0, float2& x1, float2 (&y)[4][2], float2 (&g)[4][2], int64_t (&yi)[4]) {
     const int64_t N = (int64_t)S * r.T;
-    x0 = X[cidx(r, 2 * Bn, S, r.b * 2, n)];
-    x1 = X[cidx(r, 2 * Bn, S, r.b * 2 + 1, n)];
+    x0 = X[aidx(r, 2 * Bn, S, r.b * 2, n)];
+    x1 = X[aidx(r, 2 * Bn, S, r.b * 2 + 1, n)];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        yi[j] = cidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n);
+        yi[j] = aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n);
         if (Mk) {
             const float ma = Mk[yi[j]], mb = Mk[yi[j] + (int64_t)r.F * N];      // real arena: same index, one float each
             y[j][0] = make_float2(ma * x0.x, ma * x0.y); y[j][1] = make_float2(mb * x1.x, mb * x1.y);
@@ -452,14 +307,12 @@ __global__ __launch_bounds__(256) void k_wiener_bwd_stats(const float2* __restri
                                                            float* __restrict__ bstats, int Bn, int S, int win_len) {
     const int row = work[2 * blockIdx.x], w = work[2 * blockIdx.x + 1];
     const WRow r = rows[row];
-    const int64_t N = (int64_t)S * r.T;
-    const int64_t n0 = (int64_t)w * win_len;
-    const int64_t n1 = n0 + win_len < N ? n0 + win_len : N;
+    const WWin W = window_of(r, S, w, win_len);
     const float* st = stats + r.stat + (int64_t)w * STAT;
     float acc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += 256) {
+    for (int64_t n = W.n0 + threadIdx.x; n < W.n1; n += 256) {
         float2 x0, x1, y[4][2], g[4][2];
         int64_t yi[4];
         wiener_load_point(X, Y0, Mk, G, r, Bn, S, n, x0, x1, y, g, yi);
@@ -475,18 +328,7 @@ __global__ __launch_bounds__(256) void k_wiener_bwd_stats(const float2* __restri
         }
     }
     __shared__ float red[4][16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        const int i = threadIdx.x;
-        bstats[r.stat + (int64_t)w * STAT + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    }
+    reduce<4>(acc, red, bstats + r.stat + (int64_t)w * STAT);
 }
 
 // K_j -> H_j, one thread per (row, window)
@@ -559,22 +401,15 @@ __global__ __launch_bounds__(256) void k_wiener_window_max(const float2* __restr
                                                             float* __restrict__ ext_max, int Bn, int S, int win_len) {
     const int row = work[2 * blockIdx.x], w = work[2 * blockIdx.x + 1];
     const WRow r = rows[row];
-    const int64_t N = (int64_t)S * r.T;
-    const int64_t n0 = (int64_t)w * win_len;
-    const int64_t n1 = n0 + win_len < N ? n0 + win_len : N;
-    const float2* x0 = X + cidx(r, 2 * Bn, S, r.b * 2, 0);
-    const float2* x1 = X + cidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
+    const WWin W = window_of(r, S, w, win_len);
+    const float2* x0 = X + aidx(r, 2 * Bn, S, r.b * 2, 0);
+    const float2* x1 = X + aidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
     float m = 0.f;
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += 256) {
-        const float2 a = x0[n], b = x1[n];
-        m = fmaxf(m, fmaxf(a.x * a.x + a.y * a.y, b.x * b.x + b.y * b.y));      // the expression of the statistics pass: same bits
-    }
+    for (int64_t n = W.n0 + threadIdx.x; n < W.n1; n += 256) m = fmaxf(m, fmaxf(abs2(x0[n]), abs2(x1[n])));   // as k_wiener_stats
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(ext_max) + bw_of_work[blockIdx.x], __builtin_bit_cast(unsigned, m));
 }
-
-#include "wiener_iter.h"      // niter > 1: k_wiener_stats_iter (looped form), k_wiener_resident (window-resident form)
 
 // ------------------------------------------------------------------------------------------------
 static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int group, WTable* out) {
@@ -600,10 +435,9 @@ static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, i
             for (int f = 0; f < F[k]; ++f) {
                 for (int w = 0; w < nwin; ++w) bw_of_work.push_back(bw0 + (b / group) * nwin + w);
                 WRow r;
-                r.F = F[k]; r.T = T[k]; r.b = b; r.f = f; r.nwin = nwin;
-                // rows sharing one window maximum: the `group` consecutive batch items of this row's group
-                r.first_row = first + (b / group) * group * F[k];
-                r.nrows = group * F[k]; r.pad = 0; r.cum = cum; r.stat = stat;
+                r.F = F[k]; r.T = T[k]; r.b = b; r.f = f;
+                r.nrows = group * F[k];      // rows sharing one window maximum: the `group` consecutive batch items of this row's group
+                r.cum = cum; r.stat = stat;
                 for (int w = 0; w < nwin; ++w) { work.push_back((int)rows.size()); work.push_back(w); }
                 rows.push_back(r);
                 stat += (int64_t)nwin * STAT;
@@ -614,7 +448,7 @@ static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, i
     }
     WTable t;
     t.nrows = (int)rows.size(); t.nwork = (int)work.size() / 2; t.nblockwin = (int)blockwin.size() / 2;
-    t.stat_floats = stat; t.max_frames = maxN;
+    t.max_frames = maxN;
     int rc = upload(t.d_rows, rows);
     if (!rc) rc = upload(t.d_work, work);
     if (!rc) rc = upload(t.d_blockwin, blockwin);
@@ -663,6 +497,120 @@ int wiener_em_backward(int nblocks, const int32_t* F, const int32_t* T, const fl
     return XSQ_OK;
 }
 
+// ---- forward: one path for every entry point ---------------------------------------------------------------------------
+struct EmCall {                     // the arguments of a forward entry point
+    int nblocks;
+    const int32_t *F, *T;
+    const float* X;
+    const float* masks;             // the masked form (two frames per thread); nullptr: Y holds the initial estimates
+    float* Y;
+    int Bn, S, win_len, batch_group;
+    const float* ext_max;
+    void* ws;
+    size_t ws_bytes;
+    hipStream_t stream;
+};
+
+// the longest window a call runs: win_len, or the longest row when that is shorter
+static int64_t longest_window(int nblocks, const int32_t* T, int S, int win_len) {
+    int64_t maxN = 0;
+    for (int k = 0; k < nblocks; ++k) maxN = std::max<int64_t>(maxN, (int64_t)S * T[k]);
+    return std::min<int64_t>(win_len, maxN);
+}
+
+// workspace of the iteration entry points: the statistics of xsq_wiener_workspace | max |x|^2 per (block, group, window) of
+// the resident form
+static size_t iter_stats_bytes(const EmCall& c) { return al256(xsq_wiener_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len)); }
+
+// The argument checks of every forward entry point; no HIP call.  `masked`: the entry point takes masks; `iter`: it takes
+// niter / method and the larger workspace.  Defaults batch_group; *resident: the form the call takes (niter >= 2).
+static int check_em(const char* who, EmCall& c, bool masked, bool iter, int niter, int method, bool* resident) {
+    if (int rc = check_table(who, c.nblocks, c.F, c.T, c.Bn, c.S)) return rc;
+    XSQ_REQUIRE(c.X && c.Y && c.ws && (c.masks || !masked), "%s: null argument", who);
+    if (masked) XSQ_REQUIRE(c.win_len > 0 && c.win_len % 2 == 0, "%s: win_len=%d must be even (two frames per thread)", who, c.win_len);
+    XSQ_REQUIRE(c.win_len > 0, "%s: win_len=%d", who, c.win_len);
+    XSQ_REQUIRE(niter != 0 || !masked, "%s: niter=0 is the mix-phase estimate mask * X, which has no EM pass "
+                                       "(xsq_slicqt_inverse_masked forms it)", who);
+    XSQ_REQUIRE(niter >= 0, "%s: niter=%d", who, niter);
+    XSQ_REQUIRE(method >= 0 && method <= 2, "%s: method=%d (0 auto, 1 looped, 2 resident)", who, method);
+    const int64_t longest = longest_window(c.nblocks, c.T, c.S, c.win_len);
+    const bool fits = longest <= RES_MAX_WINDOW;
+    XSQ_REQUIRE(method != 2 || fits, "%s: the resident form holds windows of at most %d frames (this call's longest has %lld)", who,
+                RES_MAX_WINDOW, (long long)longest);
+    if (c.batch_group <= 0) c.batch_group = c.Bn;
+    XSQ_REQUIRE(c.Bn % c.batch_group == 0, "%s: batch_group=%d does not divide B=%d", who, c.batch_group, c.Bn);
+    const size_t need = iter ? xsq_wiener_iter_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, niter, method)
+                             : xsq_wiener_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len);
+    XSQ_REQUIRE(c.ws_bytes >= need, "%s: workspace too small", who);
+    for (int b = 0; masked && b < c.nblocks; ++b)
+        XSQ_REQUIRE(((int64_t)c.S * c.T[b]) % 2 == 0, "%s: block %d has an odd frame count S*T=%lld", who, b, (long long)c.S * c.T[b]);
+    *resident = niter >= 2 && method != 1 && fits;
+    return XSQ_OK;
+}
+
+static void launch_window_max(const WTable& t, const float* X, float* ext_max, int Bn, int S, int win_len, hipStream_t stream) {
+    XSQ_PROF("wiener_window_max", stream);
+    hipLaunchKernelGGL(k_wiener_window_max, dim3(t.nwork), dim3(256), 0, stream, (const float2*)X, t.d_rows, t.d_work, t.d_bw_of_work,
+                       ext_max, Bn, S, win_len);
+}
+
+// in place on Y; with masks (iteration 1 of the masked form) Y is only written
+static void launch_apply(const WTable& t, const EmCall& c, const float* masks) {
+    XSQ_PROF("wiener_apply", c.stream);
+    if (masks)
+        hipLaunchKernelGGL(k_wiener_apply_masked, dim3((unsigned)((t.max_frames / 2 + 255) / 256), t.nrows), dim3(256), 0, c.stream,
+                           (const float2*)c.X, masks, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+    else
+        hipLaunchKernelGGL(k_wiener_apply, dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, c.stream,
+                           (const float2*)c.X, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+}
+
+template <YFrom SRC>
+static void launch_stats(const WTable& t, const EmCall& c) {
+    XSQ_PROF(SRC == YFrom::Current ? "wiener_stats_iter" : "wiener_stats", c.stream);
+    hipLaunchKernelGGL(k_wiener_stats<SRC>, dim3(t.nwork), dim3(256), 0, c.stream, (const float2*)c.X, (const float2*)c.Y, c.masks, t.d_rows,
+                       t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
+}
+
+// niter >= 1 iterations of the looped form: the three launches of iteration 1, then statistics + apply per further one (the
+// estimates are in Y and 1/ma^2 in the stats slots by then)
+static int run_em(const EmCall& c, int niter) {
+    WTable t;
+    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t)) return rc;
+    if (c.masks) launch_stats<YFrom::Masks>(t, c);
+    else launch_stats<YFrom::Estimates>(t, c);
+    { XSQ_PROF("wiener_finalize", c.stream);
+    hipLaunchKernelGGL(k_wiener_finalize, dim3(t.nblockwin), dim3(256), 0, c.stream, t.d_rows, t.d_blockwin, (float*)c.ws, c.ext_max); }
+    launch_apply(t, c, c.masks);
+    for (int it = 2; it <= niter; ++it) {
+        launch_stats<YFrom::Current>(t, c);
+        launch_apply(t, c, nullptr);
+    }
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
+}
+
+static int run_resident(const EmCall& c, int niter) {
+    WTable t;
+    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t)) return rc;
+    float* wmax = (float*)((char*)c.ws + iter_stats_bytes(c));
+    XSQ_HIP(hipMemsetAsync(wmax, 0, (size_t)t.nblockwin * 4, c.stream));
+    launch_window_max(t, c.X, wmax, c.Bn, c.S, c.win_len, c.stream);
+    { XSQ_PROF("wiener_resident", c.stream);
+    hipLaunchKernelGGL(c.masks ? k_wiener_resident<true> : k_wiener_resident<false>, dim3(t.nwork), dim3(RES_THREADS), 0, c.stream,
+                       (const float2*)c.X, c.masks, (float2*)c.Y, t.d_rows, t.d_work, t.d_bw_of_work, wmax, c.ext_max, c.Bn, c.S, c.win_len,
+                       niter); }
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
+}
+
+static int em(const char* who, EmCall c, bool masked, bool iter, int niter, int method) {
+    bool resident;
+    if (int rc = check_em(who, c, masked, iter, niter, method, &resident)) return rc;
+    if (niter == 0) return XSQ_OK;                        // the initial estimate is the result (norbert :247-251)
+    return resident ? run_resident(c, niter) : run_em(c, niter);
+}
+
 }  // namespace xsq
 
 using namespace xsq;
@@ -690,36 +638,6 @@ size_t xsq_wiener_workspace(int nblocks, const int32_t* F, const int32_t* T, int
     return (size_t)stat * 4 + 256;
 }
 
-int xsq_wiener_em(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S,
-                  int win_len, int batch_group, void* ws, size_t ws_bytes, void* stream_) {
-    int rc = check_table("xsq_wiener_em", nblocks, F, T, Bn, S);
-    if (rc) return rc;
-    XSQ_REQUIRE(X && Y && ws, "xsq_wiener_em: null argument");
-    XSQ_REQUIRE(win_len > 0, "xsq_wiener_em: win_len=%d", win_len);
-    if (batch_group <= 0) batch_group = Bn;
-    XSQ_REQUIRE(Bn % batch_group == 0, "xsq_wiener_em: batch_group=%d does not divide B=%d", batch_group, Bn);
-    XSQ_REQUIRE(ws_bytes >= xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len), "xsq_wiener_em: workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    WTable t;
-    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
-    float* stats = (float*)ws;
-    { XSQ_PROF("wiener_stats", stream);
-    hipLaunchKernelGGL(k_wiener_stats, dim3(t.nwork), dim3(256), 0, stream, (const float2*)X, (const float2*)Y,
-                       t.d_rows, t.d_work, stats, Bn, S, win_len); }
-    { XSQ_PROF("wiener_finalize", stream);
-    hipLaunchKernelGGL(k_wiener_finalize, dim3(t.nblockwin), dim3(256), 0, stream, t.d_rows, t.d_blockwin, stats); }
-    { XSQ_PROF("wiener_apply", stream);
-    hipLaunchKernelGGL(k_wiener_apply, dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, stream,
-                       (const float2*)X, (float2*)Y, t.d_rows, stats, Bn, S, win_len); }
-    XSQ_HIP(hipGetLastError());
-    return XSQ_OK;
-}
-
-int xsq_wiener_em_masked(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y,
-                         int Bn, int S, int win_len, int batch_group, void* ws, size_t ws_bytes, void* stream_) {
-    return xsq_wiener_em_masked_ext(nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, nullptr, ws, ws_bytes, stream_);
-}
-
 int64_t xsq_wiener_num_windows(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int batch_group) {
     if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0) return 0;
     if (batch_group <= 0) batch_group = Bn;
@@ -727,6 +645,13 @@ int64_t xsq_wiener_num_windows(int nblocks, const int32_t* F, const int32_t* T, 
     int64_t n = 0;
     for (int k = 0; k < nblocks; ++k) n += (int64_t)(Bn / batch_group) * (((int64_t)S * T[k] + win_len - 1) / win_len);
     return n;
+}
+
+int xsq_wiener_resident_max_window(void) { return RES_MAX_WINDOW; }
+
+size_t xsq_wiener_iter_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int niter, int method) {
+    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0 || niter < 0 || method < 0 || method > 2) return 0;
+    return al256(xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len)) + (size_t)xsq_wiener_num_windows(nblocks, F, T, Bn, S, win_len, 1) * 4 + 256;
 }
 
 int xsq_wiener_window_max(int nblocks, const int32_t* F, const int32_t* T, const float* X, int Bn, int S, int win_len,
@@ -738,147 +663,42 @@ int xsq_wiener_window_max(int nblocks, const int32_t* F, const int32_t* T, const
     XSQ_REQUIRE(Bn % batch_group == 0, "xsq_wiener_window_max: batch_group=%d does not divide B=%d", batch_group, Bn);
     WTable t;
     if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
-    XSQ_PROF("wiener_window_max", (hipStream_t)stream_);
-    hipLaunchKernelGGL(k_wiener_window_max, dim3(t.nwork), dim3(256), 0, (hipStream_t)stream_, (const float2*)X, t.d_rows, t.d_work,
-                       t.d_bw_of_work, ext_max, Bn, S, win_len);
+    launch_window_max(t, X, ext_max, Bn, S, win_len, (hipStream_t)stream_);
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
+}
+
+// One iteration is the looped form at niter = 1 (method 1); the iteration entry points pass theirs on.
+int xsq_wiener_em(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S,
+                  int win_len, int batch_group, void* ws, size_t ws_bytes, void* stream_) {
+    return em("xsq_wiener_em", {nblocks, F, T, X, nullptr, Y, Bn, S, win_len, batch_group, nullptr, ws, ws_bytes, (hipStream_t)stream_},
+              false, false, 1, 1);
+}
+
+int xsq_wiener_em_masked(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y,
+                         int Bn, int S, int win_len, int batch_group, void* ws, size_t ws_bytes, void* stream_) {
+    return xsq_wiener_em_masked_ext(nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, nullptr, ws, ws_bytes, stream_);
 }
 
 int xsq_wiener_em_masked_ext(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y,
                              int Bn, int S, int win_len, int batch_group, const float* ext_max, void* ws, size_t ws_bytes,
                              void* stream_) {
-    int rc = check_table("xsq_wiener_em_masked", nblocks, F, T, Bn, S);
-    if (rc) return rc;
-    XSQ_REQUIRE(X && masks && Y && ws, "xsq_wiener_em_masked: null argument");
-    XSQ_REQUIRE(win_len > 0 && win_len % 2 == 0, "xsq_wiener_em_masked: win_len=%d must be even (two frames per thread)", win_len);
-    for (int b = 0; b < nblocks; ++b)
-        XSQ_REQUIRE(((int64_t)S * T[b]) % 2 == 0, "xsq_wiener_em_masked: block %d has an odd frame count S*T=%lld", b, (long long)S * T[b]);
-    if (batch_group <= 0) batch_group = Bn;
-    XSQ_REQUIRE(Bn % batch_group == 0, "xsq_wiener_em_masked: batch_group=%d does not divide B=%d", batch_group, Bn);
-    XSQ_REQUIRE(ws_bytes >= xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len), "xsq_wiener_em_masked: workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    WTable t;
-    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
-    float* stats = (float*)ws;
-    { XSQ_PROF("wiener_stats", stream);
-    hipLaunchKernelGGL(k_wiener_stats_masked, dim3(t.nwork), dim3(256), 0, stream, (const float2*)X, masks,
-                       t.d_rows, t.d_work, stats, Bn, S, win_len); }
-    { XSQ_PROF("wiener_finalize", stream);
-    hipLaunchKernelGGL(k_wiener_finalize, dim3(t.nblockwin), dim3(256), 0, stream, t.d_rows, t.d_blockwin, stats, ext_max); }
-    { XSQ_PROF("wiener_apply", stream);
-    hipLaunchKernelGGL(k_wiener_apply_masked, dim3((unsigned)((t.max_frames / 2 + 255) / 256), t.nrows), dim3(256), 0, stream,
-                       (const float2*)X, masks, (float2*)Y, t.d_rows, stats, Bn, S, win_len); }
-    XSQ_HIP(hipGetLastError());
-    return XSQ_OK;
+    return em("xsq_wiener_em_masked", {nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, (hipStream_t)stream_},
+              true, false, 1, 1);
 }
-
 
 // ---- niter iterations (norbert/__init__.py:133-148, 247-260) -----------------------------------------------------------
-int xsq_wiener_resident_max_window(void) { return RES_MAX_WINDOW; }
-
-// the longest window a call runs: win_len, or the longest row when that is shorter
-static int64_t longest_window(int nblocks, const int32_t* T, int S, int win_len) {
-    int64_t maxN = 0;
-    for (int k = 0; k < nblocks; ++k) maxN = std::max<int64_t>(maxN, (int64_t)S * T[k]);
-    return std::min<int64_t>(win_len, maxN);
-}
-
-// workspace: the statistics of xsq_wiener_workspace | max |x|^2 per (block, group, window) of the resident form
-static size_t iter_stats_bytes(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len) {
-    return (xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len) + 255) / 256 * 256;
-}
-
-size_t xsq_wiener_iter_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int niter, int method) {
-    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0 || niter < 0 || method < 0 || method > 2) return 0;
-    return iter_stats_bytes(nblocks, F, T, Bn, S, win_len) + (size_t)xsq_wiener_num_windows(nblocks, F, T, Bn, S, win_len, 1) * 4 + 256;
-}
-
-// shared argument checks of the two entry points; no HIP call.  *resident: the form the call takes (niter >= 2).
-static int check_iter(const char* who, int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int* batch_group,
-                      int niter, int method, size_t ws_bytes, bool* resident) {
-    XSQ_REQUIRE(niter >= 0, "%s: niter=%d", who, niter);
-    XSQ_REQUIRE(method >= 0 && method <= 2, "%s: method=%d (0 auto, 1 looped, 2 resident)", who, method);
-    const bool fits = longest_window(nblocks, T, S, win_len) <= RES_MAX_WINDOW;
-    XSQ_REQUIRE(method != 2 || fits, "%s: the resident form holds windows of at most %d frames (this call's longest has %lld)", who,
-                RES_MAX_WINDOW, (long long)longest_window(nblocks, T, S, win_len));
-    if (*batch_group <= 0) *batch_group = Bn;
-    XSQ_REQUIRE(Bn % *batch_group == 0, "%s: batch_group=%d does not divide B=%d", who, *batch_group, Bn);
-    XSQ_REQUIRE(ws_bytes >= xsq_wiener_iter_workspace(nblocks, F, T, Bn, S, win_len, niter, method), "%s: workspace too small", who);
-    *resident = niter >= 2 && method != 1 && fits;
-    return XSQ_OK;
-}
-
-static int run_resident(bool masked, int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y, int Bn, int S,
-                        int win_len, int batch_group, const float* ext_max, int niter, void* ws, hipStream_t stream) {
-    WTable t;
-    int rc;
-    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
-    float* wmax = (float*)((char*)ws + iter_stats_bytes(nblocks, F, T, Bn, S, win_len));
-    XSQ_HIP(hipMemsetAsync(wmax, 0, (size_t)t.nblockwin * 4, stream));
-    { XSQ_PROF("wiener_window_max", stream);
-    hipLaunchKernelGGL(k_wiener_window_max, dim3(t.nwork), dim3(256), 0, stream, (const float2*)X, t.d_rows, t.d_work, t.d_bw_of_work,
-                       wmax, Bn, S, win_len); }
-    { XSQ_PROF("wiener_resident", stream);
-    hipLaunchKernelGGL(masked ? k_wiener_resident<true> : k_wiener_resident<false>, dim3(t.nwork), dim3(RES_THREADS), 0, stream,
-                       (const float2*)X, masks, (float2*)Y, t.d_rows, t.d_work, t.d_bw_of_work, wmax, ext_max, Bn, S, win_len, niter); }
-    XSQ_HIP(hipGetLastError());
-    return XSQ_OK;
-}
-
-// iterations 2 .. niter of the looped form, after iteration 1 left the estimates in Y and 1/ma^2 in the stats slots
-static int run_more_iterations(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S, int win_len,
-                               int batch_group, int niter, void* ws, hipStream_t stream) {
-    WTable t;
-    int rc;
-    if ((rc = get_wtable(nblocks, F, T, Bn, S, win_len, batch_group, &t))) return rc;
-    float* stats = (float*)ws;
-    for (int it = 2; it <= niter; ++it) {
-        { XSQ_PROF("wiener_stats_iter", stream);
-        hipLaunchKernelGGL(k_wiener_stats_iter, dim3(t.nwork), dim3(256), 0, stream, (const float2*)Y, t.d_rows, t.d_work, stats, Bn, S,
-                           win_len); }
-        { XSQ_PROF("wiener_apply", stream);
-        hipLaunchKernelGGL(k_wiener_apply, dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, stream,
-                           (const float2*)X, (float2*)Y, t.d_rows, stats, Bn, S, win_len); }
-    }
-    XSQ_HIP(hipGetLastError());
-    return XSQ_OK;
-}
-
 int xsq_wiener_em_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S, int win_len,
                        int batch_group, int niter, int method, void* ws, size_t ws_bytes, void* stream_) {
-    int rc = check_table("xsq_wiener_em_iter", nblocks, F, T, Bn, S);
-    if (rc) return rc;
-    XSQ_REQUIRE(X && Y && ws, "xsq_wiener_em_iter: null argument");
-    XSQ_REQUIRE(win_len > 0, "xsq_wiener_em_iter: win_len=%d", win_len);
-    bool resident;
-    if ((rc = check_iter("xsq_wiener_em_iter", nblocks, F, T, Bn, S, win_len, &batch_group, niter, method, ws_bytes, &resident))) return rc;
-    if (niter == 0) return XSQ_OK;                        // the initial estimate is the result (norbert :247-251)
-    if (resident)
-        return run_resident(false, nblocks, F, T, X, nullptr, Y, Bn, S, win_len, batch_group, nullptr, niter, ws, (hipStream_t)stream_);
-    if ((rc = xsq_wiener_em(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, ws, ws_bytes, stream_))) return rc;
-    return niter == 1 ? XSQ_OK : run_more_iterations(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, niter, ws, (hipStream_t)stream_);
+    return em("xsq_wiener_em_iter", {nblocks, F, T, X, nullptr, Y, Bn, S, win_len, batch_group, nullptr, ws, ws_bytes, (hipStream_t)stream_},
+              false, true, niter, method);
 }
 
 int xsq_wiener_em_masked_iter(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y, int Bn,
                               int S, int win_len, int batch_group, const float* ext_max, int niter, int method, void* ws,
                               size_t ws_bytes, void* stream_) {
-    int rc = check_table("xsq_wiener_em_masked_iter", nblocks, F, T, Bn, S);
-    if (rc) return rc;
-    XSQ_REQUIRE(X && masks && Y && ws, "xsq_wiener_em_masked_iter: null argument");
-    XSQ_REQUIRE(win_len > 0 && win_len % 2 == 0, "xsq_wiener_em_masked_iter: win_len=%d must be even (two frames per thread)", win_len);
-    XSQ_REQUIRE(niter != 0, "xsq_wiener_em_masked_iter: niter=0 is the mix-phase estimate mask * X, which has no EM pass "
-                            "(xsq_slicqt_inverse_masked forms it)");
-    bool resident;
-    if ((rc = check_iter("xsq_wiener_em_masked_iter", nblocks, F, T, Bn, S, win_len, &batch_group, niter, method, ws_bytes, &resident)))
-        return rc;
-    if (resident) {
-        for (int b = 0; b < nblocks; ++b)
-            XSQ_REQUIRE(((int64_t)S * T[b]) % 2 == 0, "xsq_wiener_em_masked_iter: block %d has an odd frame count S*T=%lld", b, (long long)S * T[b]);
-        return run_resident(true, nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, niter, ws, (hipStream_t)stream_);
-    }
-    if ((rc = xsq_wiener_em_masked_ext(nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, stream_))) return rc;
-    return niter == 1 ? XSQ_OK : run_more_iterations(nblocks, F, T, X, Y, Bn, S, win_len, batch_group, niter, ws, (hipStream_t)stream_);
+    return em("xsq_wiener_em_masked_iter", {nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, (hipStream_t)stream_},
+              true, true, niter, method);
 }
 
 }  // extern "C"

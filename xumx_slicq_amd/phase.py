@@ -56,6 +56,27 @@ def resident_max_window() -> int:
     return int(_lib.lib.xsq_wiener_resident_max_window())
 
 
+def _em(table: BlockTable, X: Tensor, masks, Y: Tensor, B: int, S: int, win_len: int, batch_group: int, niter: int, meth: int):
+    """Workspace query, workspace and call of the entry point that (``masks is None``, ``niter``) select: one iteration is
+    xsq_wiener_em / xsq_wiener_em_masked, any other count the ``_iter`` form of the same."""
+    F, T = _tables(table)
+    geometry = (len(table), F.ctypes.data, T.ctypes.data)
+    name, arenas = "xsq_wiener_em", (X.data_ptr(), Y.data_ptr())
+    if masks is not None:
+        name, arenas = "xsq_wiener_em_masked", (X.data_ptr(), masks.data_ptr(), Y.data_ptr())
+    query, count = "xsq_wiener_workspace", ()
+    if niter != 1:
+        name, query, count = name + "_iter", "xsq_wiener_iter_workspace", (niter, meth)
+    ext_max = (None,) if count and masks is not None else ()          # xsq_wiener_em_masked_iter takes a table; none here
+    with torch.cuda.device(X.device):
+        nbytes = getattr(_lib.lib, query)(*geometry, B, S, win_len, *count)
+        if nbytes == 0:
+            raise _lib.XsqError(f"{query}: bad arguments")
+        ws = _workspace(X.device, nbytes)
+        _lib.check(getattr(_lib.lib, name)(*geometry, *arenas, B, S, win_len, int(batch_group), *ext_max, *count,
+                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+
+
 def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
                     batch_group: int = 0, niter: int = 1, method: str = "auto"):
     """``niter`` EM iterations in place on the estimates arena Y (8B channels) given the
@@ -64,29 +85,8 @@ def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win
     ``niter`` = 0 leaves Y alone, 1 is the reference's call; ``method`` ("auto", "looped", "resident") picks the form of
     ``niter`` >= 2 (include/xumx_slicq_hip.h, xsq_wiener_em_iter)."""
     niter, meth = _niter_method(niter, method)
-    if niter == 0:
-        return
-    F, T = _tables(table)
-    if niter != 1:
-        with torch.cuda.device(X.device):
-            nbytes = _lib.lib.xsq_wiener_iter_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len, niter, meth)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_wiener_iter_workspace: bad arguments")
-            ws = _workspace(X.device, nbytes)
-            _lib.check(_lib.lib.xsq_wiener_em_iter(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), Y.data_ptr(),
-                                                   B, S, win_len, int(batch_group), niter, meth, ws.data_ptr(), ws.numel(),
-                                                   _lib.stream_ptr()),
-                       "xsq_wiener_em_iter")
-        return
-    with torch.cuda.device(X.device):
-        nbytes = _lib.lib.xsq_wiener_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len)
-        if nbytes == 0:
-            raise _lib.XsqError("xsq_wiener_workspace: bad arguments")
-        ws = _workspace(X.device, nbytes)
-        _lib.check(_lib.lib.xsq_wiener_em(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), Y.data_ptr(),
-                                          B, S, win_len, int(batch_group), ws.data_ptr(), ws.numel(),
-                                          _lib.stream_ptr()),
-                   "xsq_wiener_em")
+    if niter:
+        _em(table, X, None, Y, B, S, win_len, batch_group, niter, meth)
 
 
 def wiener_em_masked_arena(table: BlockTable, X: Tensor, masks: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
@@ -96,27 +96,7 @@ def wiener_em_masked_arena(table: BlockTable, X: Tensor, masks: Tensor, Y: Tenso
     Same bits as ``xsq_cdae_forward(Y)`` + ``wiener_em_arena``; a third less HBM traffic.  ``niter`` >= 1, ``method``:
     as ``wiener_em_arena``."""
     niter, meth = _niter_method(niter, method)
-    F, T = _tables(table)
-    if niter != 1:
-        with torch.cuda.device(X.device):
-            nbytes = _lib.lib.xsq_wiener_iter_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len, niter, meth)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_wiener_iter_workspace: bad arguments")
-            ws = _workspace(X.device, nbytes)
-            _lib.check(_lib.lib.xsq_wiener_em_masked_iter(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), masks.data_ptr(),
-                                                          Y.data_ptr(), B, S, win_len, int(batch_group), None, niter, meth,
-                                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                       "xsq_wiener_em_masked_iter")
-        return
-    with torch.cuda.device(X.device):
-        nbytes = _lib.lib.xsq_wiener_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S, win_len)
-        if nbytes == 0:
-            raise _lib.XsqError("xsq_wiener_workspace: bad arguments")
-        ws = _workspace(X.device, nbytes)
-        _lib.check(_lib.lib.xsq_wiener_em_masked(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), masks.data_ptr(),
-                                                 Y.data_ptr(), B, S, win_len, int(batch_group), ws.data_ptr(), ws.numel(),
-                                                 _lib.stream_ptr()),
-                   "xsq_wiener_em_masked")
+    _em(table, X, masks, Y, B, S, win_len, batch_group, niter, meth)
 
 
 def _one_block(mix_slicqt: Tensor, slicqtgrams: Tensor):
