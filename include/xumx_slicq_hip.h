@@ -235,6 +235,9 @@ int xsq_model_whitening(xsq_model* model, const float** mean, const float** scal
  * xsq_phasemix replaces blockwise_phasemix_sep (phase.py:96-113, with _atan2 :72-93):
  *   Y[j,b,c] = mag[j,b,c] * X[b,c] / |X[b,c]|   (angle(0) := 0); does not modify X
  *   (the reference's _atan2 adds 1 to re(X) where X == 0).
+ *   The unit phase is exact to fp32 rounding for EVERY finite non-zero X: where re^2 + im^2 is not a normal
+ *   fp32 number (|X| below about 1.1e-19 or above 1.8e19) X is divided by max(|re|, |im|) before it is
+ *   normalised; elsewhere the plain form, bit for bit what earlier versions returned.
  *   X  complex arena, 2*B channels;  mag  REAL arena, 8*B channels (4, B, 2, ...);
  *   Y  complex arena, 8*B channels.
  *
@@ -356,7 +359,14 @@ int xsq_wiener_em_masked_iter(int nblocks, const int32_t* F, const int32_t* T, c
  *   pred, target  complex arenas, 8*B channels (4 targets, B, 2, ...)
  *   masks         real arena, 8*B channels, or NULL
  *   out           DEVICE double[2*nblocks]: per block (complex-MSE mean over the 14 combinations,
- *                 mask-sum mean); the criteria average these over the blocks.                  */
+ *                 mask-sum mean); the criteria average these over the blocks.
+ * Any block table: the arenas are walked 16 bytes at a time where every block's real sub-arena
+ * (2*B*F_b*S*T_b floats per target) is a multiple of four floats -- every table of a sliCQT plan -- and
+ * the masks of EVERY block of the table 8 bytes at a time otherwise (B*F_b*S*T_b odd for some block),
+ * so that every access is inside its own sub-arena and aligned to its width (an even block's mask
+ * term may then differ in the last bits from what it gives in an all-even table).  The arenas themselves must be 16-byte aligned.
+ * XSQ_ERR_ARG (before any device call) on a null pointer, B or S <= 0 or a workspace below
+ * xsq_loss_workspace (0 on bad arguments).                                                      */
 size_t xsq_loss_workspace(int nblocks, const int32_t* F, const int32_t* T, int B, int S);
 int xsq_loss_forward(int nblocks, const int32_t* F, const int32_t* T, const float* pred,
                      const float* target, const float* masks, int B, int S, double* out,

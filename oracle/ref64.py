@@ -263,3 +263,42 @@ def bn_running(old_mean, old_var, batch_mean, batch_var_biased, count: int, mome
     om, ov, bm, bv = (t.to(F64) for t in (old_mean, old_var, batch_mean, batch_var_biased))
     unbiased = bv * (count / (count - 1.0)) if count > 1 else bv
     return (1.0 - momentum) * om + momentum * bm, (1.0 - momentum) * ov + momentum * unbiased
+
+
+# --------------------------------------------------------------------------
+# loss terms per block, dataset statistics per bin
+# --------------------------------------------------------------------------
+def block_losses(pred: Sequence[torch.Tensor], target: Sequence[torch.Tensor], masks=None, dtype: torch.dtype = F64) -> np.ndarray:
+    """Lists over blocks of (4, B, 2, F_b, S, T_b, 2) estimates and targets, and of (4, B, 2, F_b, S, T_b) masks (or None: the
+    second column is 0) -> (nblocks, 2) float64: per block ``oracle.loss.complex_mse`` and ``oracle.loss.mask_sum`` of that block
+    alone, which is the term the two criteria average over the blocks.  The two functions follow the dtype of their operands:
+    float32 is the fp32 oracle's arithmetic, float64 the reference."""
+    from . import loss as oloss
+    out = np.zeros((len(pred), 2), dtype=np.float64)
+    for b, (p, t) in enumerate(zip(pred, target)):
+        out[b, 0] = float(oloss.complex_mse([p.to(dtype)], [t.to(dtype)]))
+        if masks is not None:
+            out[b, 1] = float(oloss.mask_sum([masks[b].to(dtype)]))
+    return out
+
+
+def magnitude_sums(X_list: Sequence[torch.Tensor], dtype: torch.dtype = F64) -> List[np.ndarray]:
+    """List over blocks of (C, F_b, S, T_b, 2) coefficients of ONE track (leading dimensions of one are dropped) -> per block
+    (F_b, 2) float64: sum and sum of squares over the S * T_b frames of the channel-mean magnitude, what
+    ``oracle.statistics.get_statistics`` accumulates per track.  float32: magnitude (``oslicqt.complex_norm``) and channel mean in
+    fp32, the sums in float64, as the oracle has them; float64: all of it in float64."""
+    out = []
+    for X in X_list:
+        C, Fb, S, T, _ = X.shape[-5:]
+        mag = oslicqt.complex_norm(X.to(dtype).reshape(C, Fb, S * T, 2).contiguous())
+        m = mag.mean(0).to(F64)
+        out.append(torch.stack((m.sum(1), (m * m).sum(1)), dim=1).numpy())
+    return out
+
+
+def statistics_from_sums(sums: Sequence[np.ndarray], frames: Sequence[float]):
+    """The host formula of ``oracle.statistics.get_statistics`` on per-block (F_b, 2) sums merged over the tracks and the frame
+    count of each block: (means, stds), population std floored at 1e-4 of the block's largest."""
+    means = [s[:, 0] / n for s, n in zip(sums, frames)]
+    stds = [np.sqrt(np.maximum(s[:, 1] / n - mu * mu, 0.0)) for s, n, mu in zip(sums, frames, means)]
+    return means, [np.maximum(s, 1e-4 * np.max(s)) for s in stds]

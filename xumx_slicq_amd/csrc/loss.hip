@@ -30,11 +30,22 @@ struct LossWork {     // one workgroup: `count` float4 quads of one block's per-
 // BWD: the same pass also writes the loss gradients (training step, training.py:107): d/dpred_j = (8 e_j + 6 sum_k e_k)
 // / (14 n_b nblocks) into gY and the mask-sum gradient 2 (sum_j m_j - 1) / (n'_b nblocks) into gM (the same value for
 // the four targets) -- the operands are in registers already, a second read of pred / target / masks is saved.
-template <bool BWD>
+//
+// HALVES: a table with a block whose real sub-arena (nreal = 2 B F S T floats, always even) is no multiple of four.  The float4
+// walk of the mask arena would then run two floats past the end of every target (into the next target, the next block or past
+// the arena) and every odd target would start 8-byte aligned only.  EVERY block of such a table (the even ones too: the arm is
+// chosen per table) reads its masks as the two float2 halves of the quad, each guarded by nreal: every access is inside its own
+// sub-arena and aligned to its width; the fp64 sum then takes two two-term fp32 sums per quad instead of one four-term sum, so an
+// even block's mask term may differ in the last bits from what it gives in an all-even table.  The complex arenas are unaffected
+// (4 B F S T floats per target).  Tables whose every nreal is a multiple of four -- all plan tables -- keep the float4 code and
+// its bits.  Forward only: the training step accepts even T_b alone (xsq_train_create), so its tables never need the arm, and
+// loss_forward_backward refuses the gradients for a table that would.
+template <bool BWD, bool HALVES>
 __global__ __launch_bounds__(256) void k_loss_partial(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                        const float* __restrict__ masks,
                                                        const LossWork* __restrict__ work, double* __restrict__ partial,
                                                        float* __restrict__ gY, float* __restrict__ gM, int nblocks) {
+    static_assert(!(BWD && HALVES), "the float2 mask walk has no gradient arm");
     const LossWork w = work[blockIdx.x];
     double mse = 0.0, msk = 0.0;
     const float cb = BWD ? 1.f / (14.f * (float)(2 * w.nreal) * (float)nblocks) : 0.f;
@@ -61,7 +72,21 @@ __global__ __launch_bounds__(256) void k_loss_partial(const float* __restrict__ 
                     make_float4((8.f * e[j].x + 6.f * s1x) * cb, (8.f * e[j].y + 6.f * s1y) * cb,
                                 (8.f * e[j].z + 6.f * s1z) * cb, (8.f * e[j].w + 6.f * s1w) * cb);
         }
-        if (masks && i < w.nreal) {       // the real arena is half as long: quads [0, nreal/4) of this block
+        if constexpr (HALVES) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int64_t k = i + 2 * h;
+                if (!masks || k >= w.nreal) break;
+                float2 m = *reinterpret_cast<const float2*>(masks + w.base_r + k);
+#pragma unroll
+                for (int j = 1; j < 4; ++j) {
+                    const float2 mj = *reinterpret_cast<const float2*>(masks + w.base_r + j * w.tstride_r + k);
+                    m.x += mj.x; m.y += mj.y;
+                }
+                m.x -= 1.f; m.y -= 1.f;
+                msk += (double)(m.x * m.x + m.y * m.y);
+            }
+        } else if (masks && i < w.nreal) {       // the real arena is half as long: quads [0, nreal/4) of this block
             float4 m = *reinterpret_cast<const float4*>(masks + w.base_r + i);
             float4 sm = make_float4(-1.f + m.x, -1.f + m.y, -1.f + m.z, -1.f + m.w);      // the gradient's own summation order
 #pragma unroll
@@ -111,7 +136,7 @@ using namespace xsq;
 // work tables of one (device, block table, B, S): built once on first use -- a synchronous upload, so a shape has to be warmed up
 // before it is captured in a graph -- and resident for the life of the process (a few KB per shape; the step must not wait
 // for the host in mid-flight)
-struct LossTables { LossWork* d_work = nullptr; double* d_inv = nullptr; int* d_first = nullptr; int nwork = 0; };
+struct LossTables { LossWork* d_work = nullptr; double* d_inv = nullptr; int* d_first = nullptr; int nwork = 0; bool mask2 = false; };
 static std::mutex g_loss_mu;
 static std::map<std::vector<int>, LossTables> g_loss_tables;
 
@@ -145,6 +170,7 @@ static int loss_tables(int nblocks, const int32_t* F, const int32_t* T, int Bn, 
     first[nblocks] = (int)work.size();
     LossTables t;
     t.nwork = (int)work.size();
+    for (const LossWork& w : work) t.mask2 |= w.nreal % 4 != 0;      // (the kernel's HALVES arm)
     int rc = upload(t.d_work, work);
     if (!rc) rc = upload(t.d_inv, inv);
     if (!rc) rc = upload(t.d_first, first);
@@ -164,11 +190,14 @@ int loss_forward_backward(int nblocks, const int32_t* F, const int32_t* T, const
     LossTables t;
     if (int rc = loss_tables(nblocks, F, T, Bn, S, &t)) return rc;
     double* d_partial = (double*)ws;
+    const bool bwd = gY && gM && masks;
+    // (defensive: the only caller that passes gY / gM is the training step, whose tables have even T_b -- xsq_train_create --
+    // and so never set mask2; nothing in the suite can reach this line)
+    XSQ_REQUIRE(!(bwd && t.mask2), "loss gradients: a block with odd B*F*S*T (the float2 mask walk is forward only)");
     { XSQ_PROF("loss_partial", stream);
-      if (gY && gM && masks)
-          hipLaunchKernelGGL(k_loss_partial<true>, dim3((unsigned)t.nwork), dim3(256), 0, stream, pred, target, masks, t.d_work, d_partial, gY, gM, nblocks);
-      else
-          hipLaunchKernelGGL(k_loss_partial<false>, dim3((unsigned)t.nwork), dim3(256), 0, stream, pred, target, masks, t.d_work, d_partial, nullptr, nullptr, nblocks); }
+      auto kernel = bwd ? k_loss_partial<true, false> : (t.mask2 ? k_loss_partial<false, true> : k_loss_partial<false, false>);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)t.nwork), dim3(256), 0, stream, pred, target, masks, t.d_work, d_partial,
+                         bwd ? gY : nullptr, bwd ? gM : nullptr, nblocks); }
     hipLaunchKernelGGL(k_loss_combine, dim3((nblocks + 63) / 64), dim3(64), 0, stream, d_partial, t.d_first, t.d_inv, out, nblocks);
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;

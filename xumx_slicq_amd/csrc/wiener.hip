@@ -57,6 +57,22 @@ static std::mutex g_wmu;
 static std::map<std::vector<int>, WTable> g_wtables;
 
 // ---- Y = mag * x/|x|  (phase.py:96-113; angle(0) = 0) --------------------------------------------
+// x/|x| for every finite x.  re^2 + im^2 is a normal fp32 number for |x| in about (1.1e-19, 1.8e19): there the plain form
+// is used (and its bits kept).  Below, the sum of squares is subnormal or 0 (the phase would be lost: x = (1e-30, 1e-30) gave
+// (1, 0)), above it is inf (the output was 0): x is first divided by max(|re|, |im|), which puts the modulus in [1, sqrt 2].
+__device__ __forceinline__ float2 unit_phase(float2 x) {
+    const float a2 = x.x * x.x + x.y * x.y;
+    if (a2 >= FLT_MIN && a2 <= FLT_MAX) {
+        const float ax = sqrtf(a2);
+        return make_float2(x.x / ax, x.y / ax);
+    }
+    const float s = fmaxf(fabsf(x.x), fabsf(x.y));
+    if (!(s > 0.f)) return make_float2(1.f, 0.f);            // angle(0) = 0
+    const float re = x.x / s, im = x.y / s;
+    const float ax = sqrtf(re * re + im * im);
+    return make_float2(re / ax, im / ax);
+}
+
 __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, const float* __restrict__ mag,
                                                    float2* __restrict__ Y, const WRow* __restrict__ rows, int Bn,
                                                    int S) {
@@ -67,8 +83,7 @@ __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, 
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const float2 x = X[aidx(r, 2 * Bn, S, r.b * 2 + c, n)];
-        const float ax = sqrtf(x.x * x.x + x.y * x.y);
-        const float2 u = ax > 0.f ? make_float2(x.x / ax, x.y / ax) : make_float2(1.f, 0.f);
+        const float2 u = unit_phase(x);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int64_t yi = aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2 + c, n);

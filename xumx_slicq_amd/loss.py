@@ -27,8 +27,9 @@ def _per_block_losses(pred: Sequence[Tensor], target: Sequence[Tensor], masks: O
     B = lead[1]
     M = None
     if masks is not None:
-        M = torch.cat([m.to(torch.float32).reshape(-1) for m in masks]) if not _is_run(masks) else \
-            torch.as_strided(masks[0], (table.numel(8 * B, S, complex_=False),), (1,))
+        total = table.numel(8 * B, S, complex_=False)
+        M = torch.cat([m.to(torch.float32).reshape(-1) for m in masks]) if not _is_run(masks, total) else \
+            torch.as_strided(masks[0], (total,), (1,))
     F, T = _tables(table)
     with torch.cuda.device(P.device):
         out = torch.empty(len(table), 2, dtype=torch.float64, device=P.device)
@@ -40,13 +41,16 @@ def _per_block_losses(pred: Sequence[Tensor], target: Sequence[Tensor], masks: O
     return out
 
 
-def _is_run(ts: Sequence[Tensor]) -> bool:
+def _is_run(ts: Sequence[Tensor], total: int) -> bool:
+    """Views laid out back to back in ONE allocation of at least ``total`` floats (tensors of their own that merely sit next to
+    each other in the allocator's pool are no run: a view cannot span two storages)."""
     ptr = ts[0].data_ptr()
     for t in ts:
         if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() != ptr:
             return False
         ptr += t.numel() * 4
-    return True
+    st = ts[0].untyped_storage()
+    return st.nbytes() - (ts[0].data_ptr() - st.data_ptr()) >= total * 4
 
 
 class ComplexMSELossCriterion:
