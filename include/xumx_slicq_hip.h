@@ -496,6 +496,45 @@ int xsq_separator_schedule(int L, int64_t coefs_per_slice, int nb_samples, int64
  * kernels allow (7168); a smaller value forces the batch split on small shapes.  <= 0 restores the default.        */
 int xsq_demixer_set_max_rows(xsq_demixer* d, int max_item_slices);
 
+/* ---- overlapped, cross-faded segments: separate_sources of cadenza/enhance.py:35-99 behind ONE entry point ----------
+ * The Cadenza caller of the reference does not use the hard concat of Separator.forward: it walks the track in segments
+ * that overlap, fades each linearly in and out (torchaudio Fade) and adds them into the result.  The segment rule, in
+ * integers: segment k = 0, 1, ... starts at (k == 0 ? 0 : k * chunk_len - ov), exists while start < N - ov and ends at
+ * min((k + 1) * chunk_len, N); it fades in over its first ov samples unless k == 0 and out over its last ov samples when
+ * segment k + 1 exists.  w_in[i] = i / (ov - 1), w_out[i] = 1 - i / (ov - 1) (ov == 1: 0 and 1; ov == 0: no fades).
+ * Two departures from the reference text: a segment without a successor does not fade out, and the first
+ * hop is chunk_len - ov in integers.
+ *
+ * xsq_segment_schedule: the rule as pure host arithmetic (no device needed): segs[4 i ..] = (start, samples, fade_in,
+ *   fade_out) of segment i.  Returns the number of segments (may exceed max_segs: call again; 0 when N <= ov), negative
+ *   on error (N < 1, chunk_len < 1, ov < 0).
+ * xsq_crossfade_place: the blend of ONE pass of k equal-length segments.  scratch holds their un-faded stems as rows of n
+ *   samples, packed channel (target, segment * nb + b, c) at scratch + row_offsets[...] (DEVICE int64[8 k nb], the pass's
+ *   out_rows); segment j covers samples [start + j * stride, + n) of dst (4, nb, 2, N), n - stride == ov <= stride for
+ *   k > 1.  Every sample of [start, start + (k - 1) * stride + n) is written once, nothing outside it:
+ *     fl(fl(w_out * a) + fl(w_in * b)) where two segments of the pass meet, the plain value where the weight is 1;
+ *     fade_in_first:  the first ov samples become dst + fl(w_in * b) -- the launch of the previous pass, earlier on the
+ *                     same stream, stored fl(w_out * a) there (its fade_out_last) -- the same bits as the line above;
+ *     fade_out_last:  the last ov samples are stored as fl(w_out * b).
+ *   No atomics, no zero fill, 64-bit offsets into dst; a launch covers < 2^31 samples per row.
+ * xsq_separator_forward_segments: audio (nb, 2, N) -> out (4, nb, 2, N), out[.., start_k + i] = sum_k w_k[i] *
+ *   xsq_separator_forward(segment k)[.., i].  Segments of equal length (the first, the middle ones, the last) are
+ *   stacked into passes of at most min(max_stack * slices of a full chunk, the demixer's cap) item-slices -- a 10 s
+ *   segment has 56 slices against a full chunk's 292 -- read in place through x_rows at stride chunk_len, their stems
+ *   written to scratch inside the workspace and blended into `out` by one xsq_crossfade_place launch per pass.  All passes
+ *   run in segment order on `stream`.  Every (segment, sample batch) is its own Wiener item (group = nb).  `wiener` as in
+ *   xsq_separator_forward.  XSQ_ERR_ARG for chunk_len + ov > chunk_size, ov >= chunk_len, ov < 0, chunk_len < 1, N <= ov
+ *   and a batch whose single segment exceeds one pass (nb * slices above the cap).  Plans are cached per call shape with
+ *   those of xsq_separator_forward.  workspace: xsq_separator_segments_workspace bytes.                                  */
+int xsq_segment_schedule(int64_t N, int64_t chunk_len, int64_t ov, int64_t* segs, int max_segs);
+int xsq_crossfade_place(const float* scratch, const int64_t* row_offsets, float* dst, int nb, int64_t N, int64_t start,
+                        int64_t stride, int64_t n, int k, int ov, int fade_in_first, int fade_out_last, void* stream);
+int xsq_separator_segments_workspace(xsq_demixer* d, const xsq_model* model, int nb, int64_t N, int64_t chunk_size,
+                                     int64_t chunk_len, int64_t ov, int max_stack, int wiener, size_t* bytes);
+int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* model, const float* audio, int nb, int64_t N,
+                                   int64_t chunk_size, int64_t chunk_len, int64_t ov, int max_stack, int wiener, float* out,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- per-kernel timing (bench.py roofline) ------------------------------------------
  * When enabled, every kernel launch of the library is bracketed by hipEvents recorded on
  * its own launch stream.  xsq_profile_read synchronises the outstanding events and

@@ -2,6 +2,7 @@
 Wiener-EM -> isliCQT) behind the reference's Separator / Unmix / NSGT_SL /
 INSGT_SL module API.  The arithmetic lives in ``csrc/`` (hand-written HIP for
 gfx950 behind a C ABI, ``include/xumx_slicq_hip.h``); this package holds the
-host-side plan builder and the ``nn.Module`` mirrors of the reference surface.
+host-side plan builder and the ``nn.Module`` mirrors of the reference surface
+(``separator``, ``inference``, ``cadenza.separate_sources`` for overlapped, cross-faded segments).
 """
 __version__ = "0.1.0"

@@ -103,6 +103,10 @@ _SIGS = {
     "xsq_separator_forward": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "xsq_separator_forward_indirect": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "xsq_separator_remix": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int]),
+    "xsq_segment_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int]),
+    "xsq_crossfade_place": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "xsq_separator_segments_workspace": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "xsq_separator_forward_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     "xsq_comm_load": (C.c_int, [C.c_char_p]),
     "xsq_comm_version": (C.c_int, []),
     "xsq_comm_unique_id": (C.c_int, [_vp]),

@@ -37,6 +37,10 @@ struct PassPlan {
     int set_first = 0, set_count = 1;
     int64_t* d_xrows = nullptr;      // [2B] input row offsets
     int64_t* d_orows = nullptr;      // [8B] output row offsets
+    // a pass of overlapped segments (xsq_separator_forward_segments): d_orows point into the scratch arena and one
+    // xsq_crossfade_place launch blends the seg_k segments at seg_start + j * seg_stride into the result
+    int64_t seg_start = 0, seg_stride = 0;
+    int seg_k = 0, fade_in = 0, fade_out = 0;
 };
 
 struct ForwardPlan {
@@ -48,6 +52,7 @@ struct ForwardPlan {
     uint64_t last_use = 0;           // LRU stamp (xsq_demixer::clock)
     size_t main_bytes = 0, tail_bytes = 0;
     size_t ext_floats = 0;           // window-maximum tables of the split sets (zeroed at the start of every call)
+    size_t scratch_bytes = 0;        // overlapped segments: the un-faded stems of the largest pass (head of the workspace)
 };
 
 }  // namespace
@@ -225,6 +230,28 @@ static void build_schedule(int L, int nb, int64_t N, int64_t cs, int max_stack, 
         for (SchedPass& p : *out) p.tail = 0;
 }
 
+// Room for one more call shape: when the cache is full the least recently used shape goes.  Its tables may still be read
+// by kernels in flight (any stream): wait for the device once -- this happens once per kMaxPlans NEW shapes, never in a
+// steady loop over known shapes.  Shapes a HIP graph has captured are never victims (a replay reads the tables without
+// coming through here: ADVICE round 5); when every cached shape is pinned the cache simply grows.
+static int evict_for_new_plan(xsq_demixer* d) {
+    if (d->plans.size() < xsq_demixer::kMaxPlans) return XSQ_OK;
+    auto victim = d->plans.end();
+    for (auto p = d->plans.begin(); p != d->plans.end(); ++p)
+        if (!p->second.pinned && (victim == d->plans.end() || p->second.last_use < victim->second.last_use)) victim = p;
+    if (victim != d->plans.end()) {
+        XSQ_HIP(hipDeviceSynchronize());
+        (void)hipFree(victim->second.d_tables);
+        (void)hipHostFree(victim->second.h_tables);
+        d->plans.erase(victim);
+    }
+    return XSQ_OK;
+}
+
+static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<int64_t>& key, ForwardPlan& fp,
+                        const std::vector<std::vector<int64_t>>& xr, const std::vector<std::vector<int64_t>>& orw, int wiener,
+                        ForwardPlan** out);
+
 // The schedule with its device tables and workspace sizes.
 static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
                             ForwardPlan** out) {
@@ -232,21 +259,7 @@ static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
     const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal};
     auto it = d->plans.find(key);
     if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
-    if (d->plans.size() >= xsq_demixer::kMaxPlans) {
-        // evict the least recently used shape.  Its tables may still be read by kernels in flight (any stream): wait for the
-        // device once -- this happens once per kMaxPlans NEW shapes, never in a steady loop over known shapes.  Shapes a HIP
-        // graph has captured are never victims (a replay reads the tables without coming through here: ADVICE round 5);
-        // when every cached shape is pinned the cache simply grows.
-        auto victim = d->plans.end();
-        for (auto p = d->plans.begin(); p != d->plans.end(); ++p)
-            if (!p->second.pinned && (victim == d->plans.end() || p->second.last_use < victim->second.last_use)) victim = p;
-        if (victim != d->plans.end()) {
-            XSQ_HIP(hipDeviceSynchronize());
-            (void)hipFree(victim->second.d_tables);
-            (void)hipHostFree(victim->second.h_tables);
-            d->plans.erase(victim);
-        }
-    }
+    if (int rc = evict_for_new_plan(d)) return rc;
     const int64_t min_samples = P->L / 2 + 1;                      // separator.py:162
     const int cap = d->max_item_slices > 0 ? d->max_item_slices : default_max_item_slices(P);
     ForwardPlan fp;
@@ -279,6 +292,13 @@ static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
             for (int q = 0; q < sched[i].set_count; ++q) fp.passes[i + q].ext_off = off;
         }
     }
+    return publish_plan(d, Mo, key, fp, xr, orw, wiener, out);
+}
+
+// Device tables and workspace sizes of a new plan; the plan enters the cache once its tables are on the device.
+static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<int64_t>& key, ForwardPlan& fp,
+                        const std::vector<std::vector<int64_t>>& xr, const std::vector<std::vector<int64_t>>& orw, int wiener,
+                        ForwardPlan** out) {
     size_t total = 0;
     for (auto& p : fp.passes) total += (size_t)10 * p.B;
     XSQ_HIP(hipMalloc(&fp.d_tables, std::max<size_t>(total, 1) * sizeof(int64_t)));
@@ -316,6 +336,80 @@ static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
     }
     auto ins = d->plans.emplace(key, fp);
     *out = &ins.first->second;
+    return XSQ_OK;
+}
+
+
+// ---- overlapped segments (separate_sources, cadenza/enhance.py:35-99): the segment rule of include/xumx_slicq_hip.h in
+// integers, pure host arithmetic (tests/test_overlap_cpu.py drives it through xsq_segment_schedule).
+struct Segment { int64_t start, n; int fade_in, fade_out; };
+
+static void build_segments(int64_t N, int64_t cl, int64_t ov, std::vector<Segment>* out) {
+    auto start_of = [&](int64_t k) { return k == 0 ? (int64_t)0 : k * cl - ov; };
+    for (int64_t k = 0; start_of(k) < N - ov; ++k) {
+        const bool next = start_of(k + 1) < N - ov;
+        out->push_back(Segment{start_of(k), std::min((k + 1) * cl, N) - start_of(k), k == 0 ? 0 : (int)ov, next ? (int)ov : 0});
+    }
+}
+
+// Passes of equal-length segments one chunk_len apart (the first segment, the middle ones, the last: with ov == 0 the
+// first belongs to the middle ones), each of at most `budget` item-slices; every segment carries the whole batch.
+static int get_segment_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int64_t cl, int64_t ov, int max_stack,
+                            int wiener, ForwardPlan** out) {
+    xsq_plan* P = d->plan;
+    // (nine words: never the seven of an xsq_separator_forward shape)
+    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal, cl, ov};
+    auto it = d->plans.find(key);
+    if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
+    const int h = P->L / 4;
+    const int64_t min_samples = P->L / 2 + 1;
+    const int64_t hard = default_max_item_slices(P);
+    const int64_t cap = d->max_item_slices > 0 ? d->max_item_slices : hard;
+    // what bounds a stacked pass of full chunks today: max_stack items of a full chunk's slices, and the cap
+    const int64_t S_full = ((std::max(cs, min_samples) + h - 1) / h + 1) / 2 + 1;
+    const int64_t budget = std::min<int64_t>(cap, (max_stack > hard / S_full) ? hard : max_stack * S_full);
+    std::vector<Segment> segs;
+    build_segments(N, cl, ov, &segs);
+    ForwardPlan fp;
+    std::vector<std::vector<int64_t>> xr, orw;
+    for (size_t s0 = 0; s0 < segs.size();) {
+        const int64_t n = segs[s0].n, n_pad = std::max(n, min_samples);
+        const int64_t S = slices_of(n_pad, h);
+        XSQ_REQUIRE((int64_t)nb * S <= hard, "xsq_separator_forward_segments: nb=%d samples of %lld slices exceed one pass (%lld item-slices): "
+                    "split the batch", nb, (long long)S, (long long)hard);
+        const int64_t per_pass = std::max<int64_t>(1, budget / ((int64_t)nb * S));
+        size_t s1 = s0 + 1;
+        while (s1 < segs.size() && (int64_t)(s1 - s0) < per_pass && segs[s1].n == n && segs[s1].start - segs[s1 - 1].start == cl) ++s1;
+        PassPlan p;
+        p.seg_k = (int)(s1 - s0); p.seg_start = segs[s0].start; p.seg_stride = cl;
+        p.fade_in = segs[s0].fade_in ? 1 : 0; p.fade_out = segs[s1 - 1].fade_out ? 1 : 0;
+        p.n = n; p.n_pad = n_pad; p.B = p.seg_k * nb; p.group = nb;
+        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)8 * p.B);
+        for (int j = 0; j < p.seg_k; ++j)
+            for (int b = 0; b < nb; ++b)
+                for (int c = 0; c < 2; ++c) {
+                    const int item = j * nb + b;
+                    xrow[(size_t)item * 2 + c] = ((int64_t)b * 2 + c) * N + segs[s0 + j].start;
+                    for (int t = 0; t < 4; ++t) orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * p.B + item) * 2 + c) * n;
+                }
+        fp.scratch_bytes = std::max(fp.scratch_bytes, al256((size_t)8 * p.B * n * sizeof(float)));
+        xr.push_back(xrow); orw.push_back(orow);
+        fp.passes.push_back(p);
+        s0 = s1;
+    }
+    if (int rc = evict_for_new_plan(d)) return rc;
+    return publish_plan(d, Mo, key, fp, xr, orw, wiener, out);
+}
+
+static int check_segments(const char* who, int nb, int64_t N, int64_t cs, int64_t cl, int64_t ov, int max_stack, int wiener) {
+    XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "%s: nb=%d N=%lld chunk_size=%lld max_stack=%d", who, nb, (long long)N, (long long)cs, max_stack);
+    XSQ_REQUIRE(wiener >= 0, "%s: wiener=%d iterations", who, wiener);
+    XSQ_REQUIRE(cl >= 1, "%s: chunk_len=%lld samples per segment (>= 1)", who, (long long)cl);
+    XSQ_REQUIRE(ov >= 0, "%s: ov=%lld overlapping samples (>= 0)", who, (long long)ov);
+    XSQ_REQUIRE(ov < cl, "%s: ov=%lld >= chunk_len=%lld: segments two apart would overlap", who, (long long)ov, (long long)cl);
+    XSQ_REQUIRE(cl <= cs && ov <= cs - cl, "%s: a segment of chunk_len + ov = %lld + %lld samples is longer than chunk_size=%lld", who, (long long)cl,
+                (long long)ov, (long long)cs);
+    XSQ_REQUIRE(N > ov, "%s: N=%lld samples are not more than ov=%lld: no segment exists", who, (long long)N, (long long)ov);
     return XSQ_OK;
 }
 
@@ -492,6 +586,58 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
     }
     if (rc) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return rc; }
     return join();
+}
+
+int xsq_segment_schedule(int64_t N, int64_t chunk_len, int64_t ov, int64_t* segs, int max_segs) {
+    XSQ_REQUIRE(N >= 1 && chunk_len >= 1 && ov >= 0 && (segs || max_segs <= 0), "xsq_segment_schedule: N=%lld chunk_len=%lld ov=%lld", (long long)N,
+                (long long)chunk_len, (long long)ov);
+    XSQ_REQUIRE(N / chunk_len < (1 << 30), "xsq_segment_schedule: N=%lld in segments of %lld", (long long)N, (long long)chunk_len);
+    std::vector<Segment> sg;
+    build_segments(N, chunk_len, ov, &sg);
+    for (size_t i = 0; i < sg.size() && (int64_t)i < max_segs; ++i) {
+        int64_t* o = segs + 4 * i;
+        o[0] = sg[i].start; o[1] = sg[i].n; o[2] = sg[i].fade_in; o[3] = sg[i].fade_out;
+    }
+    return (int)sg.size();
+}
+
+int xsq_separator_segments_workspace(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int64_t cl, int64_t ov, int max_stack,
+                                     int wiener, size_t* bytes) {
+    XSQ_REQUIRE(d && Mo && bytes, "xsq_separator_segments_workspace: null argument");
+    if (int rc = check_segments("xsq_separator_segments_workspace", nb, N, cs, cl, ov, max_stack, wiener)) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    ForwardPlan* fp;
+    if (int rc = get_segment_plan(d, Mo, nb, N, cs, cl, ov, max_stack, wiener, &fp)) return rc;
+    *bytes = fp->scratch_bytes + fp->main_bytes;
+    return XSQ_OK;
+}
+
+int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int64_t cl, int64_t ov,
+                                   int max_stack, int wiener, float* out, void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(d && Mo && audio && out && ws, "xsq_separator_forward_segments: null argument");
+    if (int rc = check_segments("xsq_separator_forward_segments", nb, N, cs, cl, ov, max_stack, wiener)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    ForwardPlan* fp;
+    {
+        std::lock_guard<std::mutex> lk(d->mu);
+        if (int rc = get_segment_plan(d, Mo, nb, N, cs, cl, ov, max_stack, wiener, &fp)) return rc;
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) fp->pinned = true;
+    }
+    XSQ_REQUIRE(ws_bytes >= fp->scratch_bytes + fp->main_bytes, "xsq_separator_forward_segments: workspace too small (%zu needed, %zu given)",
+                fp->scratch_bytes + fp->main_bytes, ws_bytes);
+    // scratch (the un-faded stems of one pass) | workspace of the pass.  In segment order on ONE stream: the head of a
+    // pass's first segment is added onto what the launch of the previous pass stored.
+    float* scratch = (float*)ws;
+    char* pws = (char*)ws + fp->scratch_bytes;
+    for (const PassPlan& p : fp->passes) {
+        if (int rc = run_pass(d, Mo, audio, nullptr, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, scratch, p.d_orows, pws,
+                              ws_bytes - fp->scratch_bytes, stream))
+            return rc;
+        if (int rc = xsq_crossfade_place(scratch, p.d_orows, out, nb, N, p.seg_start, p.seg_stride, p.n, p.seg_k, (int)ov, p.fade_in, p.fade_out, stream))
+            return rc;
+    }
+    return XSQ_OK;
 }
 
 int xsq_separator_remix(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack, int wiener,

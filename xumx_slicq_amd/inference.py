@@ -100,7 +100,7 @@ _POOLS: dict = {}        # process-wide pinned staging pools of demix_directory
 
 
 def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, writers: int = 4, depth: int = 3, quiet=False,
-                    remix=None):
+                    remix=None, overlapped=None):
     """The CLI's loop (inference.py:118-146) as a pipeline over the tracks: decode -> pinned host buffer (reader threads) |
     H2D on a copy stream | resampling to the model's rate on the GPU where the file's rate differs (preprocess_audio,
     data.py:148-156) | ``separator(audio)`` | channel interleave on the GPU (the wav payload layout, so the host never
@@ -108,7 +108,11 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
     threads.  At ~5 ms of GPU time per 240 s track the loop is bound by PCIe and file I/O; the stages of consecutive
     tracks overlap.  Stems are written at ``separator.sample_rate`` (inference.py:135-142).  ``remix`` = (names, (R, 4)
     gains) from ``parse_remix_specs``: ``separator.remix`` runs instead and writes <NAME>.wav per mix in place of the four
-    stems.  Returns [(name, audio seconds, separator milliseconds by HIP events)] in input order."""
+    stems.  ``overlapped`` = (segment seconds, overlap fraction): ``separator.forward_overlapped`` runs instead of
+    ``separator(audio)`` (not together with ``remix``).  Returns [(name, audio seconds, separator milliseconds by HIP
+    events)] in input order."""
+    if remix is not None and overlapped is not None:
+        raise ValueError("an overlapped remix is not built: remix or overlapped, not both")
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -178,7 +182,10 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
                 x = Resample(rate, model_rate, resampling_method="sinc_interpolation")(x)
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record(main)
-            est = separator(x) if remix is None else separator.remix(x, remix[1])      # (4 | R, 1, 2, N')
+            if overlapped is not None:
+                est = separator.forward_overlapped(x, *overlapped)
+            else:
+                est = separator(x) if remix is None else separator.remix(x, remix[1])      # (4 | R, 1, 2, N')
             t1.record(main)
             inter = est[:, 0].transpose(1, 2).contiguous()           # (4, N', 2): the wav payload of each target
             ready = torch.cuda.Event()
@@ -221,6 +228,25 @@ def _remix_one(audio, separator, rate, device, remix):
     return dict(zip(remix[0], mixes)), time.time() - start_time
 
 
+def _overlapped_one(audio, separator, rate, device, overlapped):
+    """``separate`` with ``separator.forward_overlapped``: ({target: (nb_samples, 2, T)}, seconds)."""
+    if device:
+        audio = audio.to(device)
+    audio = xaudio.preprocess_audio(audio, rate, separator.sample_rate)
+    torch.cuda.synchronize(audio.device)
+    start_time = time.time()
+    estimates = separator.forward_overlapped(audio, *overlapped)
+    torch.cuda.synchronize(audio.device)
+    return separator.to_dict(estimates), time.time() - start_time
+
+
+def overlapped_option(args):
+    """(segment, overlap) when --segment or --overlap was given (the other takes its default), else None."""
+    if args.segment is None and args.overlap is None:
+        return None
+    return (10.0 if args.segment is None else args.segment, 0.1 if args.overlap is None else args.overlap)
+
+
 def parse_args(p: argparse.ArgumentParser, argv=None):
     """``p.parse_args`` plus the checks between options.  Host only."""
     args = p.parse_args(argv)
@@ -229,6 +255,13 @@ def parse_args(p: argparse.ArgumentParser, argv=None):
             p.error(f"--niter {args.niter}: the iteration count is >= 0")
         if args.realtime:
             p.error("--niter counts the EM iterations of the offline model's Wiener filter; --realtime is mix-phase and has none")
+    if args.segment is not None or args.overlap is not None:
+        if args.remix:
+            p.error("--segment / --overlap write the four stems from overlapped, cross-faded segments; an overlapped --remix is not built")
+        if args.segment is not None and not (0 < args.segment < float("inf")):
+            p.error(f"--segment {args.segment}: a positive number of seconds")
+        if args.overlap is not None and not 0 <= args.overlap < 1:
+            p.error(f"--overlap {args.overlap}: a fraction of a second in [0, 1)")
     return args
 
 
@@ -249,6 +282,12 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--niter", type=int, default=None, metavar="N",
                    help="EM iterations of the Wiener post-filter of the offline model (default 1, the reference's; 0 = mix-phase); "
                         "not with --realtime, which has no EM")
+    p.add_argument("--segment", type=float, default=None, metavar="SECONDS",
+                   help="demix in overlapped, cross-faded segments of this hop (Separator.forward_overlapped, default 10.0 once "
+                        "--segment or --overlap is given) instead of hard-joined chunks; not with --remix")
+    p.add_argument("--overlap", type=float, default=None, metavar="FRACTION",
+                   help="overlap of consecutive segments as a fraction of a second, in [0, 1) (default 0.1 once --segment or "
+                        "--overlap is given); not with --remix")
     return p
 
 
@@ -264,11 +303,17 @@ def inference_main(argv=None):
                                    warmup=args.warmup, realtime=args.realtime, device=args.device, niter=args.niter)
     else:
         separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter)
+    overlapped = overlapped_option(args)
+    if overlapped is not None:
+        try:
+            separator._segment_lengths(*overlapped)
+        except ValueError as e:
+            p.error(str(e))
     out_dir = Path(args.output_dir)
     wavs = sorted(Path(args.input_dir).glob(f"*{args.ext}"))
     if not args.serial:
         t0 = time.time()
-        done = demix_directory(separator, wavs, out_dir, device=args.device, remix=remix)
+        done = demix_directory(separator, wavs, out_dir, device=args.device, remix=remix, overlapped=overlapped)
         wall = time.time() - t0
         if done:
             print(f"xumx-sliCQ-V2 inference time: {sum(d[2] for d in done) / len(done) / 1e3:.4f} s/track over {len(done)} track(s); "
@@ -277,7 +322,9 @@ def inference_main(argv=None):
     tot, n = 0.0, 0
     for wav in wavs:
         sig, rate = xaudio.load_audio(str(wav))
-        if remix is None:
+        if overlapped is not None:
+            estimates, dt = _overlapped_one(sig, separator, rate, args.device, overlapped)
+        elif remix is None:
             estimates, dt = separate(sig, separator, rate=rate, device=args.device)
         else:
             estimates, dt = _remix_one(sig, separator, rate, args.device, remix)

@@ -482,6 +482,64 @@ class Separator(nn.Module):
             return torch.einsum("rt,tbcn->rbcn", G.to(device=est.device, dtype=est.dtype), est)
         return self._forward_native(audio_big, wiener, gains=G)
 
+    def _segment_lengths(self, segment: float, overlap: float, sample_rate=None):
+        """(chunk_len, ov) of ``forward_overlapped`` in samples; ValueError for what the segment rule cannot use."""
+        if sample_rate is None:
+            sample_rate = self.__dict__.get("_sr")
+            if sample_rate is None:                       # (the buffer lives on the device: read it once)
+                sample_rate = self.__dict__["_sr"] = float(self.sample_rate)
+        return segment_lengths(sample_rate, segment, overlap, self.chunk_size)
+
+    @torch.no_grad()
+    def forward_overlapped(self, audio_big: Tensor, segment: float = 10.0, overlap: float = 0.1) -> Tensor:
+        """(nb_samples, 2, N) fp32 on a ROCm device -> (4, nb_samples, 2, N): ``forward`` over segments that overlap and are
+        cross-faded, ``separate_sources`` of the reference's Cadenza caller (cadenza/enhance.py:35-99) instead of the hard
+        concat of separator.py:231.  ``segment`` seconds per hop, ``overlap`` in [0, 1) of a second: with
+        chunk_len = int(sr * segment * (1 + overlap)) and ov = int(overlap * sr), segment k starts at k * chunk_len - ov
+        (0 for k = 0), ends at (k + 1) * chunk_len and fades linearly (torchaudio ``Fade``) over the ov samples it shares
+        with each neighbour; ``segments`` lists them.  Two departures from the reference: a segment without
+        a successor does not fade out, and the first hop is taken in integers.
+        By default ONE native call (xsq_separator_forward_segments: equal-length segments stacked into passes, read in
+        place, blended by one xsq_crossfade_place launch per pass).  When ``_native_mode`` is None (an A/B switch off its
+        default, a mixed model) the definition is computed: ``forward`` per segment, faded and added with torch."""
+        if not isinstance(audio_big, Tensor) or audio_big.dim() != 3:
+            raise ValueError("forward_overlapped needs (nb_samples, 2, N) audio (as forward)")
+        chunk_len, ov = self._segment_lengths(segment, overlap)
+        if audio_big.shape[-1] <= ov:
+            raise ValueError(f"a track of {audio_big.shape[-1]} samples is not longer than the overlap of {ov}: no segment exists")
+        wiener = self._native_mode(audio_big)
+        if wiener is None:
+            return overlapped_loop(self.forward, audio_big, chunk_len, ov)
+        from . import _lib
+        import ctypes as C
+        if audio_big.dtype != torch.float32 or not audio_big.is_contiguous():
+            audio_big = audio_big.contiguous().float()
+        nb, N, dev = audio_big.shape[0], audio_big.shape[-1], audio_big.device
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self._packed_fft()
+        with torch.cuda.device(dev):
+            model = self.xumx_model._model(dev)
+            d = self.nsgt.nsgt.nsgt.demixer(dev)
+            main = torch.cuda.current_stream(dev)
+            cs = int(min(self.chunk_size, 1 << 62))
+            max_stack = int(getattr(self, "max_stack", 8))
+            cap = int(getattr(self, "max_item_slices", 0))
+            key = ("segments", nb, N, cs, chunk_len, ov, max_stack, wiener, self.xumx_model._version(), dev.index, cap)
+            _lib.check(_lib.lib.xsq_demixer_set_max_rows(d, cap), "xsq_demixer_set_max_rows")      # (sticky, part of the plan key)
+            nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
+            if nbytes is None:
+                b = C.c_size_t()
+                _lib.check(_lib.lib.xsq_separator_segments_workspace(d, model, nb, N, cs, chunk_len, ov, max_stack, wiener, C.byref(b)),
+                           "xsq_separator_segments_workspace")
+                nbytes = self._nsizes[key] = b.value
+            ws = self._native_ws(dev, main.cuda_stream, "main", nbytes)
+            out = torch.empty(4, nb, 2, N, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib.xsq_separator_forward_segments(d, model, audio_big.data_ptr(), nb, N, cs, chunk_len, ov, max_stack, wiener,
+                                                               out.data_ptr(), ws.data_ptr(), ws.numel(), main.cuda_stream),
+                       "xsq_separator_forward_segments")
+        return out
+
     @torch.no_grad()
     def forward_aggregate(self, audio_big: Tensor, aggregate_dict: dict) -> dict:
         """``to_dict(forward(audio), aggregate_dict)`` (separator.py:235-259) through ``remix`` with 0/1 gain rows: one
@@ -502,6 +560,66 @@ class Separator(nn.Module):
                     new_estimates[key] = new_estimates[key] + estimates_dict[target]
             estimates_dict = new_estimates
         return estimates_dict
+
+
+def segment_lengths(sample_rate, segment: float, overlap: float, chunk_size: Optional[int] = None):
+    """(chunk_len, ov) in samples of the overlapped segments (cadenza/enhance.py:75-78, the overlap in integers).
+    ValueError for segment <= 0, overlap outside [0, 1), ov >= chunk_len and a segment longer than ``chunk_size``."""
+    segment, overlap = float(segment), float(overlap)
+    if not segment > 0 or segment == float("inf"):
+        raise ValueError(f"segment must be a positive number of seconds (got {segment})")
+    if not 0.0 <= overlap < 1.0:
+        raise ValueError(f"overlap must be in [0, 1) (got {overlap})")
+    chunk_len = int(sample_rate * segment * (1 + overlap))
+    ov = int(overlap * sample_rate)
+    if chunk_len < 1 or ov >= chunk_len:
+        raise ValueError(f"segment = {segment} s gives {chunk_len} samples per hop against an overlap of {ov}: too short")
+    if chunk_size is not None and chunk_len + ov > chunk_size:
+        raise ValueError(f"a segment of {chunk_len} + {ov} samples is longer than chunk_size = {chunk_size}")
+    return chunk_len, ov
+
+
+def segments(N: int, chunk_len: int, ov: int):
+    """[(start, samples, fade_in, fade_out)] of the overlapped segments of an N-sample track (xsq_segment_schedule: host
+    arithmetic, the one statement of the rule that the native call, the fallback loop and the tests share)."""
+    import numpy as np
+    from . import _lib
+    buf = np.zeros((max(1, N // max(1, chunk_len) + 2), 4), dtype=np.int64)
+    n = _lib.lib.xsq_segment_schedule(int(N), int(chunk_len), int(ov), buf.ctypes.data, len(buf))
+    if n < 0 or n > len(buf):
+        raise ValueError(f"xsq_segment_schedule({N}, {chunk_len}, {ov}): {_lib.last_error() if n < 0 else n}")
+    return [tuple(r) for r in buf[:n].tolist()]
+
+
+def fade_weights(ov: int, device=None):
+    """(w_in, w_out) of torchaudio's linear Fade over ov >= 1 samples, fp32: i / (ov - 1) and (ov - 1 - i) / (ov - 1), one
+    rounding each (the quotients the crossfade kernel forms); ov == 1: [0] and [1]."""
+    if ov == 1:
+        return torch.zeros(1, device=device), torch.ones(1, device=device)
+    i = torch.arange(ov, dtype=torch.float32)
+    return (i / float(ov - 1)).to(device), (i.flip(0) / float(ov - 1)).to(device)
+
+
+def overlapped_loop(forward, audio: Tensor, chunk_len: int, ov: int) -> Tensor:
+    """The definition of ``Separator.forward_overlapped``: ``forward`` (any callable (nb, ch, n) -> (4, nb, ch, n)) per
+    segment, each faded and added into the result in segment order.  The tail of a segment is stored as w_out * a and the
+    head of the next added as w_in * b: products and sum rounded one by one, as the native call does."""
+    nb, ch, N = audio.shape
+    segs = segments(N, chunk_len, ov)
+    if not segs:
+        raise ValueError(f"a track of {N} samples is not longer than the overlap of {ov}: no segment exists")
+    out = None
+    for start, n, fi, fo in segs:
+        est = forward(audio[..., start:start + n])
+        if out is None:
+            out = torch.empty((*est.shape[:-1], N), dtype=est.dtype, device=est.device)
+            w_in, w_out = fade_weights(ov, est.device) if ov else (None, None)
+        if fi:
+            out[..., start:start + fi] += w_in * est[..., :fi]
+        out[..., start + fi:start + n - fo] = est[..., fi:n - fo]
+        if fo:
+            out[..., start + n - fo:start + n] = w_out * est[..., n - fo:]
+    return out
 
 
 def _gain_row(d: dict) -> list:
