@@ -354,6 +354,43 @@ int xsq_wiener_em_masked_iter(int nblocks, const int32_t* F, const int32_t* T, c
                               float* Y, int B, int S, int win_len, int batch_group, const float* ext_max, int niter,
                               int method, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the other two post-filter options of the Open-Unmix family: softmask and the residual source ------------------------
+ * norbert.wiener(v, x, niter, use_softmask=softmask) on v = contrib.residual_model(v, x, alpha=1) when residual is set
+ * (norbert/__init__.py:247-248, :263-309; norbert/contrib.py:11-77), per window as above.  flags:
+ *   XSQ_WIENER_SOFTMASK  the initial estimates are the ratio mask  y_j = x v_j / (eps + sum_j v_j)  per channel instead of the
+ *                        mixture phase on v_j (sum over all sources, the residual included)
+ *   XSQ_WIENER_RESIDUAL  a fifth source  v_4 = relu(max(|x|, eps) - sum_{j<4} v_j)  per channel: what the four targets do not
+ *                        explain.  The estimates' arena then has 10*B channels (5, B, 2, ...), residual last, and the
+ *                        statistics slot 32 floats (20 sums, max|x|^2, pad[3], 5 denominators, pad[3]); the masks' / magnitudes'
+ *                        arena keeps 8*B.  The residual is formed from the mix and the four masks as a frame is loaded.
+ * eps = FLT_EPSILON everywhere.  flags = 0 is the call without options, launch for launch.
+ *   xsq_wiener_start              the J initial estimates from MAGNITUDES v (real arena, 8*B channels) into Y (2*J*B channels):
+ *                                 what xsq_phasemix is without options; flags != 0
+ *   xsq_wiener_em_options         niter iterations in place on Y (2*J*B channels) holding those starts (only the source count
+ *                                 of flags matters here); niter = 0 leaves Y alone
+ *   xsq_wiener_em_masked_options  the same fed by the MASKS (v_j = m_j |x|): Y is written only; niter = 0 with flags != 0 writes
+ *                                 the starts (one elementwise launch); win_len and every S*T_b even
+ *   workspace: xsq_wiener_options_workspace bytes for every niter (0 on error).  method as xsq_wiener_em_iter; the resident
+ *   form holds windows of at most xsq_wiener_resident_max_window_sources(J) frames, J = 4 or 5 (0 for any other J).     */
+#define XSQ_WIENER_SOFTMASK 1
+#define XSQ_WIENER_RESIDUAL 2
+int xsq_wiener_resident_max_window_sources(int nsources);
+size_t xsq_wiener_options_workspace(int nblocks, const int32_t* F, const int32_t* T, int B, int S, int win_len, int niter,
+                                    int method, int flags);
+int xsq_wiener_start(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* mag, float* Y, int B, int S,
+                     int flags, void* stream);
+int xsq_wiener_em_options(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int B, int S, int win_len,
+                          int batch_group, int niter, int method, int flags, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int xsq_wiener_em_masked_options(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y,
+                                 int B, int S, int win_len, int batch_group, const float* ext_max, int niter, int method,
+                                 int flags, void* workspace, size_t workspace_bytes, void* stream);
+/* The option set of the whole call (xsq_demix_pass, xsq_separator_*): state of the model handle, read per call.  With
+ * residual set xsq_separator_forward / _indirect / _forward_segments write FIVE stems, out = (5, nb, 2, N), and size their
+ * workspaces for it; xsq_separator_remix and xsq_demix_pass refuse (XSQ_ERR_ARG).  A mix-phase call (wiener = 0) with an
+ * option set runs the elementwise start in place of the fused mask * X.                                              */
+int xsq_model_set_wiener_options(xsq_model* model, int softmask, int residual);
+
 /* ---- loss forward (validation half of training.loop, training.py:34-112 with train=False) -------
  * Replaces ComplexMSELossCriterion (loss.py:37-76) and MaskSumLossCriterion (loss.py:79-96).
  *   pred, target  complex arenas, 8*B channels (4 targets, B, 2, ...)
@@ -529,6 +566,10 @@ int xsq_demixer_set_max_rows(xsq_demixer* d, int max_item_slices);
 int xsq_segment_schedule(int64_t N, int64_t chunk_len, int64_t ov, int64_t* segs, int max_segs);
 int xsq_crossfade_place(const float* scratch, const int64_t* row_offsets, float* dst, int nb, int64_t N, int64_t start,
                         int64_t stride, int64_t n, int k, int ov, int fade_in_first, int fade_out_last, void* stream);
+/* the same for nsources = 4 or 5 stems (the residual of xsq_model_set_wiener_options): rows (source, segment * nb + b, c) */
+int xsq_crossfade_place_sources(const float* scratch, const int64_t* row_offsets, float* dst, int nsources, int nb, int64_t N,
+                                int64_t start, int64_t stride, int64_t n, int k, int ov, int fade_in_first, int fade_out_last,
+                                void* stream);
 int xsq_separator_segments_workspace(xsq_demixer* d, const xsq_model* model, int nb, int64_t N, int64_t chunk_size,
                                      int64_t chunk_len, int64_t ov, int max_stack, int wiener, size_t* bytes);
 int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* model, const float* audio, int nb, int64_t N,

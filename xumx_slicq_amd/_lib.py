@@ -125,6 +125,16 @@ _SIGS = {
     "xsq_wiener_em_iter": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "xsq_wiener_em_masked_iter": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp,
                                             C.c_size_t, _vp]),
+    "xsq_wiener_resident_max_window_sources": (C.c_int, [C.c_int]),
+    "xsq_wiener_options_workspace": (C.c_size_t, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xsq_wiener_start": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "xsq_wiener_em_options": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
+                                        _vp]),
+    "xsq_wiener_em_masked_options": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                               _vp, C.c_size_t, _vp]),
+    "xsq_model_set_wiener_options": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "xsq_crossfade_place_sources": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

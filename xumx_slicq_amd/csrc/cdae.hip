@@ -1006,6 +1006,12 @@ extern "C" int xsq_debug_w4_stamps(unsigned long long* out, int reset) {     // 
 }
 #endif
 
+int xsq_model_set_wiener_options(xsq_model* Mo, int softmask, int residual) {
+    XSQ_REQUIRE(Mo, "xsq_model_set_wiener_options: null model");
+    Mo->wiener_flags = (softmask ? XSQ_WIENER_SOFTMASK : 0) | (residual ? XSQ_WIENER_RESIDUAL : 0);
+    return XSQ_OK;
+}
+
 int xsq_model_set_winograd(xsq_model* Mo, int on) {
     XSQ_REQUIRE(Mo && on >= 0 && on <= 15, "xsq_model_set_winograd: null model or mask %d (1 = layers 2 / 3 Winograd F(2, 4), 2 / 4 = layer 1 / 4 F(2, 2), 8 = F(4, 4) for long rows)", on);
     XSQ_REQUIRE(!(on & 8) || Mo->wino4, "xsq_model_set_winograd: bit 8 (F(4, 4)) needs a model created with XSQ_WINO4=1 in the environment");

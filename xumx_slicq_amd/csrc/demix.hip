@@ -21,10 +21,13 @@ namespace {
 
 // what the 32-bit float offsets of the band kernels allow for the 8-channel estimate arena of one pass:
 // 2 * (8 B) * S * sumFT < 2^31 (slicqt.hip: inverse_impl) -> B * S <= 7168 for the Bark-262 plan (sumFT = 18640)
-static int default_max_item_slices(const xsq_plan* P) {
-    const int64_t lim = ((1ll << 31) - 1) / (16 * std::max<int64_t>(P->sumFT, P->nbins));
-    return (int)std::min<int64_t>(lim, 65535 / 8);          // and BC * S <= 65535 rows per launch
+// (J sources: 2J channels per sample; 4 without the residual of xsq_model_set_wiener_options)
+static int default_max_item_slices(const xsq_plan* P, int J = 4) {
+    const int64_t lim = ((1ll << 31) - 1) / (4 * J * std::max<int64_t>(P->sumFT, P->nbins));
+    return (int)std::min<int64_t>(lim, 65535 / (2 * J));    // and BC * S <= 65535 rows per launch
 }
+
+static inline int sources_of(const xsq_model* Mo) { return (Mo->wiener_flags & XSQ_WIENER_RESIDUAL) ? 5 : 4; }
 
 struct PassPlan {
     int64_t n = 0, n_pad = 0;        // samples per item that exist / that the slice count is taken from
@@ -36,7 +39,7 @@ struct PassPlan {
     int64_t ext_off = -1;
     int set_first = 0, set_count = 1;
     int64_t* d_xrows = nullptr;      // [2B] input row offsets
-    int64_t* d_orows = nullptr;      // [8B] output row offsets
+    int64_t* d_orows = nullptr;      // [2JB] output row offsets (J = 4 sources, 5 with the residual)
     // a pass of overlapped segments (xsq_separator_forward_segments): d_orows point into the scratch arena and one
     // xsq_crossfade_place launch blends the seg_k segments at seg_start + j * seg_stride into the result
     int64_t seg_start = 0, seg_stride = 0;
@@ -85,16 +88,18 @@ static int pass_layout(xsq_demixer* d, const xsq_model* Mo, int B, int64_t n_pad
     XSQ_REQUIRE(S >= 3, "xsq_demix_pass: %lld samples give %d slices; the conv stack needs 3 (pad to sllen/2 + 1)", (long long)n_pad, S);
     XSQ_REQUIRE(Mo->sumFT == P->sumFT && Mo->nblocks == P->nblocks, "xsq_demix_pass: the model's block table is not the plan's");
     const size_t coefs = (size_t)S * P->sumFT;
+    const int flags = Mo->wiener_flags, J = sources_of(Mo);
     size_t o = 0;
     L->X = o;     o += al256((size_t)2 * B * coefs * 8);
     L->masks = o; o += al256((size_t)8 * B * coefs * 4);
-    L->Y = o;     if (wiener) o += al256((size_t)8 * B * coefs * 8);
+    L->Y = o;     if (wiener || flags) o += al256((size_t)2 * J * B * coefs * 8);
     L->fwd_bytes = xsq_slicqt_forward_workspace(P, 2 * B, n_pad);
     L->cdae_bytes = xsq_cdae_workspace(Mo, B, S);
-    L->inv_bytes = xsq_slicqt_inverse_workspace(P, 8 * B, S);
-    L->wien_bytes = wiener >= 2 ? xsq_wiener_iter_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000, wiener, 0)
+    L->inv_bytes = xsq_slicqt_inverse_workspace(P, 2 * J * B, S);
+    L->wien_bytes = flags ? xsq_wiener_options_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000, wiener, 0, flags)
+                  : wiener >= 2 ? xsq_wiener_iter_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000, wiener, 0)
                   : wiener ? xsq_wiener_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, 5000) : 0;
-    if (!L->fwd_bytes || !L->cdae_bytes || !L->inv_bytes || (wiener && !L->wien_bytes)) {
+    if (!L->fwd_bytes || !L->cdae_bytes || !L->inv_bytes || ((wiener || flags) && !L->wien_bytes)) {
         const std::string why = xsq_last_error();
         set_error("xsq_demix_pass: B=%d, %lld samples: a stage's workspace query failed (%s)", B, (long long)n_pad, why.c_str());
         return XSQ_ERR_ARG;
@@ -147,6 +152,16 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
     if ((rc = xsq_slicqt_forward_rows_indirect(P, x, x_slot, x_rows, 2 * B, n, n_pad, X, xin, mean, scale, split, w + L.fwd, L.fwd_bytes, stream)))
         return rc;
     if ((rc = xsq_cdae_forward_xin(Mo, X, B, S, nullptr, masks, w + L.cdae, L.cdae_bytes, stream, 1))) return rc;
+    const int flags = Mo->wiener_flags, J = sources_of(Mo);
+    if (flags) {
+        // an option set (softmask, residual): J sources from the masks, whatever the iteration count; none writes the starts
+        XSQ_REQUIRE(!gains || J == 4, "xsq_separator_remix: the residual has no gain column; remix the four targets without it");
+        if ((rc = xsq_wiener_em_masked_options(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max, wiener, 0, flags,
+                                               w + L.wien, L.wien_bytes, stream)))
+            return rc;
+        if (!gains) return xsq_slicqt_inverse_rows(P, Y, 2 * J * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
+        return run_remix(P, nullptr, nullptr, Y, gains, R, B, S, n, out, out_rows, w + L.inv, L.total - L.inv, stream);
+    }
     if (!wiener && !gains)
         return xsq_slicqt_inverse_masked(P, masks, X, 8 * B, 2 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
     // `wiener` counts the EM iterations: one runs the three launches it always ran, more take the form xsq_wiener_em_masked_iter
@@ -256,12 +271,13 @@ static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<i
 static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
                             ForwardPlan** out) {
     xsq_plan* P = d->plan;
-    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal};
+    const int J = sources_of(Mo);
+    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal | ((int64_t)Mo->wiener_flags << 8)};
     auto it = d->plans.find(key);
     if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
     if (int rc = evict_for_new_plan(d)) return rc;
     const int64_t min_samples = P->L / 2 + 1;                      // separator.py:162
-    const int cap = d->max_item_slices > 0 ? d->max_item_slices : default_max_item_slices(P);
+    const int cap = d->max_item_slices > 0 ? std::min(d->max_item_slices, default_max_item_slices(P, J)) : default_max_item_slices(P, J);
     ForwardPlan fp;
     std::vector<SchedPass> sched;
     build_schedule(P->L, nb, N, cs, max_stack, wiener ? 1 : 0, cap, &sched);
@@ -270,13 +286,13 @@ static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
         PassPlan p;
         p.n = sp.n; p.n_pad = std::max(sp.n, min_samples); p.B = sp.k * sp.nbb; p.group = sp.nbb; p.tail = sp.tail;
         p.set_first = sp.set_first; p.set_count = sp.set_count;
-        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)8 * p.B);
+        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)2 * J * p.B);
         for (int j2 = 0; j2 < sp.k; ++j2)
             for (int b = 0; b < sp.nbb; ++b)
                 for (int c = 0; c < 2; ++c) {
                     const int item = j2 * sp.nbb + b;
                     xrow[(size_t)item * 2 + c] = ((int64_t)(sp.b0 + b) * 2 + c) * N + sp.start + j2 * cs;
-                    for (int t = 0; t < 4; ++t)
+                    for (int t = 0; t < J; ++t)
                         orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * nb + sp.b0 + b) * 2 + c) * N + sp.start + j2 * cs;
                 }
         xr.push_back(xrow); orw.push_back(orow);
@@ -300,7 +316,7 @@ static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<i
                         const std::vector<std::vector<int64_t>>& xr, const std::vector<std::vector<int64_t>>& orw, int wiener,
                         ForwardPlan** out) {
     size_t total = 0;
-    for (auto& p : fp.passes) total += (size_t)10 * p.B;
+    for (size_t i = 0; i < fp.passes.size(); ++i) total += xr[i].size() + orw[i].size();
     XSQ_HIP(hipMalloc(&fp.d_tables, std::max<size_t>(total, 1) * sizeof(int64_t)));
     if (hipHostMalloc(&fp.h_tables, std::max<size_t>(total, 1) * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) {
         (void)hipFree(fp.d_tables);
@@ -358,13 +374,14 @@ static int get_segment_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
                             int wiener, ForwardPlan** out) {
     xsq_plan* P = d->plan;
     // (nine words: never the seven of an xsq_separator_forward shape)
-    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal, cl, ov};
+    const int J = sources_of(Mo);
+    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal | ((int64_t)Mo->wiener_flags << 8), cl, ov};
     auto it = d->plans.find(key);
     if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
     const int h = P->L / 4;
     const int64_t min_samples = P->L / 2 + 1;
-    const int64_t hard = default_max_item_slices(P);
-    const int64_t cap = d->max_item_slices > 0 ? d->max_item_slices : hard;
+    const int64_t hard = default_max_item_slices(P, J);
+    const int64_t cap = d->max_item_slices > 0 ? std::min<int64_t>(d->max_item_slices, hard) : hard;
     // what bounds a stacked pass of full chunks today: max_stack items of a full chunk's slices, and the cap
     const int64_t S_full = ((std::max(cs, min_samples) + h - 1) / h + 1) / 2 + 1;
     const int64_t budget = std::min<int64_t>(cap, (max_stack > hard / S_full) ? hard : max_stack * S_full);
@@ -384,15 +401,15 @@ static int get_segment_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
         p.seg_k = (int)(s1 - s0); p.seg_start = segs[s0].start; p.seg_stride = cl;
         p.fade_in = segs[s0].fade_in ? 1 : 0; p.fade_out = segs[s1 - 1].fade_out ? 1 : 0;
         p.n = n; p.n_pad = n_pad; p.B = p.seg_k * nb; p.group = nb;
-        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)8 * p.B);
+        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)2 * J * p.B);
         for (int j = 0; j < p.seg_k; ++j)
             for (int b = 0; b < nb; ++b)
                 for (int c = 0; c < 2; ++c) {
                     const int item = j * nb + b;
                     xrow[(size_t)item * 2 + c] = ((int64_t)b * 2 + c) * N + segs[s0 + j].start;
-                    for (int t = 0; t < 4; ++t) orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * p.B + item) * 2 + c) * n;
+                    for (int t = 0; t < J; ++t) orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * p.B + item) * 2 + c) * n;
                 }
-        fp.scratch_bytes = std::max(fp.scratch_bytes, al256((size_t)8 * p.B * n * sizeof(float)));
+        fp.scratch_bytes = std::max(fp.scratch_bytes, al256((size_t)2 * J * p.B * n * sizeof(float)));
         xr.push_back(xrow); orw.push_back(orow);
         fp.passes.push_back(p);
         s0 = s1;
@@ -482,6 +499,8 @@ int xsq_demix_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const int64_t*
     if (group <= 0) group = B;
     XSQ_REQUIRE(B % group == 0, "xsq_demix_pass: group=%d does not divide B=%d", group, B);
     XSQ_REQUIRE(wiener >= 0, "xsq_demix_pass: wiener=%d iterations", wiener);
+    XSQ_REQUIRE(!(Mo->wiener_flags & XSQ_WIENER_RESIDUAL), "xsq_demix_pass: out_rows name four stems per item; the residual option "
+                "(xsq_model_set_wiener_options) writes five: use xsq_separator_forward");
     return run_pass(d, Mo, x, nullptr, x_rows, B, n, n_pad, group, wiener, out, out_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -634,7 +653,8 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* Mo, const float* a
         if (int rc = run_pass(d, Mo, audio, nullptr, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, scratch, p.d_orows, pws,
                               ws_bytes - fp->scratch_bytes, stream))
             return rc;
-        if (int rc = xsq_crossfade_place(scratch, p.d_orows, out, nb, N, p.seg_start, p.seg_stride, p.n, p.seg_k, (int)ov, p.fade_in, p.fade_out, stream))
+        if (int rc = xsq_crossfade_place_sources(scratch, p.d_orows, out, sources_of(Mo), nb, N, p.seg_start, p.seg_stride, p.n, p.seg_k, (int)ov,
+                                                 p.fade_in, p.fade_out, stream))
             return rc;
     }
     return XSQ_OK;
@@ -646,6 +666,8 @@ int xsq_separator_remix(xsq_demixer* d, xsq_model* Mo, const float* audio, int n
     XSQ_REQUIRE(audio && gains, "xsq_separator_remix: null argument");
     XSQ_REQUIRE(R >= 1 && R <= 4, "xsq_separator_remix: R=%d mixes (1..4)", R);
     for (int i = 0; i < 4 * R; ++i) XSQ_REQUIRE(std::isfinite(gains[i]), "xsq_separator_remix: gain [%d][%d] is not finite", i / 4, i % 4);
+    XSQ_REQUIRE(Mo && !(Mo->wiener_flags & XSQ_WIENER_RESIDUAL), "xsq_separator_remix: the residual option has no gain column; remix the "
+                "four targets without it");
     return separator_forward_impl(d, Mo, audio, nullptr, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws, tail_ws_bytes,
                                   stream_, tail_stream_, gains, R);
 }

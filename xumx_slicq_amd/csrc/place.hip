@@ -68,8 +68,8 @@ __global__ __launch_bounds__(PLACE_THREADS) void k_place_rows(const float* __res
 // stream -- stored fl(w_out * a) there: fl(w_in * b) is added onto it.  No contraction, so both routes give the same bits.
 struct CrossfadeArgs {
     const float* src;
-    const int64_t* rows;      // [8 * k * nb] scratch row offsets, (target, segment * nb + b, c)
-    float* dst;               // (4, nb, 2, N)
+    const int64_t* rows;      // [2J * k * nb] scratch row offsets, (target, segment * nb + b, c)
+    float* dst;               // (J, nb, 2, N)
     int64_t N, start;
     int nb, k, ov, fade_in_first, fade_out_last;
     unsigned stride, n, range;      // range = (k - 1) * stride + n < 2^31
@@ -140,8 +140,15 @@ extern "C" int xsq_place_rows(const float* src, float* dst, const int64_t* table
 
 extern "C" int xsq_crossfade_place(const float* scratch, const int64_t* row_offsets, float* dst, int nb, int64_t N, int64_t start,
                                    int64_t stride, int64_t n, int k, int ov, int fade_in_first, int fade_out_last, void* stream) {
+    return xsq_crossfade_place_sources(scratch, row_offsets, dst, 4, nb, N, start, stride, n, k, ov, fade_in_first, fade_out_last, stream);
+}
+
+extern "C" int xsq_crossfade_place_sources(const float* scratch, const int64_t* row_offsets, float* dst, int nsources, int nb, int64_t N,
+                                           int64_t start, int64_t stride, int64_t n, int k, int ov, int fade_in_first, int fade_out_last,
+                                           void* stream) {
     XSQ_REQUIRE(scratch && row_offsets && dst, "xsq_crossfade_place: null pointer");
-    XSQ_REQUIRE(nb >= 1 && 8 * (int64_t)nb <= 65535 && N >= 1 && start >= 0 && n >= 1 && k >= 1,
+    XSQ_REQUIRE(nsources == 4 || nsources == 5, "xsq_crossfade_place: %d sources (4, or 5 with the residual)", nsources);
+    XSQ_REQUIRE(nb >= 1 && 2 * nsources * (int64_t)nb <= 65535 && N >= 1 && start >= 0 && n >= 1 && k >= 1,
                 "xsq_crossfade_place: nb=%d N=%lld start=%lld n=%lld k=%d", nb, (long long)N, (long long)start, (long long)n, k);
     XSQ_REQUIRE(ov >= 0 && ov < (1 << 24) && ov <= n, "xsq_crossfade_place: ov=%d (0 .. min(n, 2^24 - 1))", ov);
     if (k == 1) stride = n;
@@ -159,7 +166,7 @@ extern "C" int xsq_crossfade_place(const float* scratch, const int64_t* row_offs
     hipStream_t st = (hipStream_t)stream;
     const int64_t gx = (range + 3 + 4 * PLACE_THREADS - 1) / (4 * PLACE_THREADS);       // + 3: the destination's lead-in
     XSQ_PROF("crossfade_place", st);
-    hipLaunchKernelGGL(k_crossfade_place, dim3((unsigned)gx, (unsigned)(8 * nb)), dim3(PLACE_THREADS), 0, st, A);
+    hipLaunchKernelGGL(k_crossfade_place, dim3((unsigned)gx, (unsigned)(2 * nsources * nb)), dim3(PLACE_THREADS), 0, st, A);
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
 }

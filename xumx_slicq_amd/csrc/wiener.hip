@@ -32,8 +32,16 @@
 // window-resident form (one workgroup per (row, window) keeps the window's frames in registers over all
 // iterations: one read, one write; windows of at most xsq_wiener_resident_max_window() frames) --
 // wiener_iter.h.  `method` chooses: 0 = resident when the window fits, 1 = looped, 2 = resident.
+//
+// Option sets (softmask, residual; norbert/__init__.py:247-248, :263-309 and norbert/contrib.py:11-77): the source count J (4, or 5
+// with the residual last) and the kind of start are template parameters of every kernel here and of the arithmetic in
+// wiener_math.h (start_channel: the J initial estimates of a channel from the mix and the four masks or magnitudes, formed as a
+// frame is loaded).  The estimates' arena then has 2JB channels and the statistics slot Slot<J>::N floats; the masks' arena keeps
+// 8B.  k_wiener_start writes the starts alone (niter = 0, and xsq_wiener_start for callers that hold magnitudes).  The entry points
+// without options run the <4, MixPhase> instantiations: the code and the launches they always ran.  xsq_wiener_*_options below.
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/xumx_slicq_hip.h"
@@ -57,22 +65,7 @@ static std::mutex g_wmu;
 static std::map<std::vector<int>, WTable> g_wtables;
 
 // ---- Y = mag * x/|x|  (phase.py:96-113; angle(0) = 0) --------------------------------------------
-// x/|x| for every finite x.  re^2 + im^2 is a normal fp32 number for |x| in about (1.1e-19, 1.8e19): there the plain form
-// is used (and its bits kept).  Below, the sum of squares is subnormal or 0 (the phase would be lost: x = (1e-30, 1e-30) gave
-// (1, 0)), above it is inf (the output was 0): x is first divided by max(|re|, |im|), which puts the modulus in [1, sqrt 2].
-__device__ __forceinline__ float2 unit_phase(float2 x) {
-    const float a2 = x.x * x.x + x.y * x.y;
-    if (a2 >= FLT_MIN && a2 <= FLT_MAX) {
-        const float ax = sqrtf(a2);
-        return make_float2(x.x / ax, x.y / ax);
-    }
-    const float s = fmaxf(fabsf(x.x), fabsf(x.y));
-    if (!(s > 0.f)) return make_float2(1.f, 0.f);            // angle(0) = 0
-    const float re = x.x / s, im = x.y / s;
-    const float ax = sqrtf(re * re + im * im);
-    return make_float2(re / ax, im / ax);
-}
-
+// (unit_phase: wiener_math.h)
 __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, const float* __restrict__ mag,
                                                    float2* __restrict__ Y, const WRow* __restrict__ rows, int Bn,
                                                    int S) {
@@ -93,6 +86,28 @@ __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, 
     }
 }
 
+// ---- the J initial estimates under an option set (softmask, residual), into the estimates' arena of 2JB channels: the result of
+// niter = 0 and what the forms fed by estimates start from.  a: the masks (MASKS) or the magnitudes, real arena of 8B channels.
+template <int J, Start ST, bool MASKS>
+__global__ __launch_bounds__(256) void k_wiener_start(const float2* __restrict__ X, const float* __restrict__ a,
+                                                       float2* __restrict__ Y, const WRow* __restrict__ rows, int Bn, int S) {
+    const WRow r = rows[blockIdx.y];
+    const int64_t N = (int64_t)S * r.T;
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float2 x = X[aidx(r, 2 * Bn, S, r.b * 2 + c, n)];
+        float m[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[j] = a[aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2 + c, n)];
+        float2 y[J];
+        start_channel<J, ST, MASKS>(x, m, y);
+#pragma unroll
+        for (int j = 0; j < J; ++j) Y[aidx(r, 2 * J * Bn, S, (j * Bn + r.b) * 2 + c, n)] = y[j];
+    }
+}
+
 // ---- pass 1: raw sums and max per (row, window).  One workgroup per (row, window). -----------------
 // Lane t adds frames n0 + t, n0 + t + 256, ... in order, whatever the source: the sums round identically.
 //   Estimates  y = Y[n]: 80 B per time-frequency point.
@@ -100,15 +115,17 @@ __global__ __launch_bounds__(256) void k_phasemix(const float2* __restrict__ X, 
 //              then writes 4 bytes per coefficient instead of 8 and this pass reads 48 B.  Bitwise the two-step result.
 //   Current    y = Y[n] in iterations >= 2 of the looped form.  st[16] holds 1/ma^2 (k_wiener_finalize of iteration 1) and is
 //              left alone; st[0..15] become R, st[20..23] the denominators: the arithmetic of k_wiener_finalize.
+// J sources (Slot<J>: the slot above is J = 4) and, from masks, the kind of start (start_channel: the residual and the softmask
+// are formed on the way in; J = 4 from the mixture phase is the line above).
 enum class YFrom { Estimates, Masks, Current };
 
-template <YFrom SRC>
+template <YFrom SRC, int J, Start ST>
 __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__ X, const float2* __restrict__ Y,
                                                        const float* __restrict__ Mk, const WRow* __restrict__ rows,
                                                        const int* __restrict__ work, float* __restrict__ stats, int Bn, int S,
                                                        int win_len) {
     constexpr bool MAX = SRC != YFrom::Current;
-    constexpr int NV = MAX ? 17 : 16;
+    constexpr int NV = MAX ? 4 * J + 1 : 4 * J;
     const int row = work[2 * blockIdx.x], w = work[2 * blockIdx.x + 1];
     const WRow r = rows[row];
     const WWin W = window_of(r, S, w, win_len);
@@ -117,7 +134,8 @@ __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__
     for (int i = 0; i < NV; ++i) acc[i] = 0.f;
     const float2* x0 = X + aidx(r, 2 * Bn, S, r.b * 2, 0);
     const float2* x1 = X + aidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
-    const int64_t base = aidx(r, 8 * Bn, S, r.b * 2, 0);                 // target 0, channel 0 of this row
+    // target 0, channel 0 of this row: in the masks' arena (8B channels) or the estimates' (2JB); the same index at J = 4
+    const int64_t base = aidx(r, SRC == YFrom::Masks ? 8 * Bn : 2 * J * Bn, S, r.b * 2, 0);
     const int64_t cstride = (int64_t)r.F * W.N, jstride = (int64_t)Bn * 2 * cstride;
     for (int64_t n = W.n0 + threadIdx.x; n < W.n1; n += 256) {
         float2 a, b;
@@ -125,40 +143,52 @@ __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__
             a = x0[n], b = x1[n];
             acc[NV - 1] = fmaxf(acc[NV - 1], fmaxf(abs2(a), abs2(b)));
         }
+        if constexpr (SRC == YFrom::Masks && (J != 4 || ST != Start::MixPhase)) {
+            float m0[4], m1[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t i = base + j * jstride + n;
-            if constexpr (SRC == YFrom::Masks) {
-                const float ma = Mk[i], mb = Mk[i + cstride];
-                accumulate(acc, j, make_float2(ma * a.x, ma * a.y), make_float2(mb * b.x, mb * b.y));
-            } else {
-                accumulate(acc, j, Y[i], Y[i + cstride]);
+            for (int j = 0; j < 4; ++j) { m0[j] = Mk[base + j * jstride + n]; m1[j] = Mk[base + j * jstride + cstride + n]; }
+            float2 y0[J], y1[J];
+            start_channel<J, ST, true>(a, m0, y0);
+            start_channel<J, ST, true>(b, m1, y1);
+#pragma unroll
+            for (int j = 0; j < J; ++j) accumulate(acc, j, y0[j], y1[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const int64_t i = base + j * jstride + n;
+                if constexpr (SRC == YFrom::Masks) {
+                    const float ma = Mk[i], mb = Mk[i + cstride];
+                    accumulate(acc, j, make_float2(ma * a.x, ma * a.y), make_float2(mb * b.x, mb * b.y));
+                } else {
+                    accumulate(acc, j, Y[i], Y[i + cstride]);
+                }
             }
         }
     }
     __shared__ float red[4][NV];
-    float* st = stats + r.stat + (int64_t)w * STAT;
+    float* st = stats + r.stat + (int64_t)w * Slot<J>::N;
     if constexpr (MAX) {
         reduce<4>(acc, red, st);
     } else {
-        __shared__ float tot[16];
+        __shared__ float tot[4 * J];
         reduce<4>(acc, red, tot);
         __syncthreads();
-        if (threadIdx.x < 4) sums_to_R_slot(st, threadIdx.x, tot, st[16]);
+        if (threadIdx.x < J) sums_to_R_slot<J>(st, threadIdx.x, tot, st[Slot<J>::MAX]);
     }
 }
 
 // ---- pass 2: window max over all rows of the block, then R per row.  One workgroup per (block, window).
 // ext_max (optional): max |x|^2 per (block, group, window) in blockwin order, taken over MORE batch items than this call holds
 // (a batch split into several passes, demix.hip): the window maximum of norbert :257 spans the whole batch.
+template <int J>
 __global__ __launch_bounds__(256) void k_wiener_finalize(const WRow* __restrict__ rows,
                                                           const int* __restrict__ blockwin,
-                                                          float* __restrict__ stats, const float* __restrict__ ext_max = nullptr) {
+                                                          float* __restrict__ stats, const float* __restrict__ ext_max) {
     const int first = blockwin[2 * blockIdx.x], w = blockwin[2 * blockIdx.x + 1];
     const int nrows = rows[first].nrows;
     __shared__ float smax[256];
     float m = 0.f;
-    for (int i = threadIdx.x; i < nrows; i += 256) m = fmaxf(m, stats[rows[first + i].stat + (int64_t)w * STAT + 16]);
+    for (int i = threadIdx.x; i < nrows; i += 256) m = fmaxf(m, stats[rows[first + i].stat + (int64_t)w * Slot<J>::N + Slot<J>::MAX]);
     smax[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -169,14 +199,15 @@ __global__ __launch_bounds__(256) void k_wiener_finalize(const WRow* __restrict_
     const float ma = fmaxf(1.f, 0.1f * sqrtf(mx2));         // norbert :257
     const float inv_ma2 = 1.f / (ma * ma);
     for (int i = threadIdx.x; i < nrows; i += 256) {
-        float* st = stats + rows[first + i].stat + (int64_t)w * STAT;
+        float* st = stats + rows[first + i].stat + (int64_t)w * Slot<J>::N;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sums_to_R_slot(st, j, st, inv_ma2);
-        st[16] = inv_ma2;
+        for (int j = 0; j < J; ++j) sums_to_R_slot<J>(st, j, st, inv_ma2);
+        st[Slot<J>::MAX] = inv_ma2;
     }
 }
 
 // ---- pass 3: per time-frequency point 2x2 solve and filter, in place on Y ---------------------------
+template <int J>
 __global__ __launch_bounds__(256) void k_wiener_apply(const float2* __restrict__ X, float2* __restrict__ Y,
                                                        const WRow* __restrict__ rows, const float* __restrict__ stats,
                                                        int Bn, int S, int win_len) {
@@ -184,27 +215,42 @@ __global__ __launch_bounds__(256) void k_wiener_apply(const float2* __restrict__
     const int64_t N = (int64_t)S * r.T;
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    const float* st = stats + r.stat + (n / win_len) * STAT;
+    const float* st = stats + r.stat + (n / win_len) * Slot<J>::N;
     const float2 x0 = X[aidx(r, 2 * Bn, S, r.b * 2, n)];
     const float2 x1 = X[aidx(r, 2 * Bn, S, r.b * 2 + 1, n)];
-    float2 y[4][2], o[4][2];
-    int64_t yi[4];
+    float2 y[J][2], o[J][2];
+    int64_t yi[J];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        yi[j] = aidx(r, 8 * Bn, S, (j * Bn + r.b) * 2, n);
+    for (int j = 0; j < J; ++j) {
+        yi[j] = aidx(r, 2 * J * Bn, S, (j * Bn + r.b) * 2, n);
         y[j][0] = Y[yi[j]];
         y[j][1] = Y[yi[j] + (int64_t)r.F * N];
     }
-    wiener_point(st, x0, x1, y, o);
+    wiener_point<J>(st, x0, x1, y, o);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < J; ++j) {
         Y[yi[j]] = o[j][0];
         Y[yi[j] + (int64_t)r.F * N] = o[j][1];
     }
 }
 
+// the starts of frame n (second = false) or n + 1 of the two-frame loads of k_wiener_apply_masked
+template <int J, Start ST>
+__device__ inline void point_start(float2 x0, float2 x1, const float2 (&ma)[4], const float2 (&mb)[4], bool second, float2 (&y)[J][2]) {
+    float m0[4], m1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { m0[j] = second ? ma[j].y : ma[j].x; m1[j] = second ? mb[j].y : mb[j].x; }
+    float2 y0[J], y1[J];
+    start_channel<J, ST, true>(x0, m0, y0);
+    start_channel<J, ST, true>(x1, m1, y1);
+#pragma unroll
+    for (int j = 0; j < J; ++j) { y[j][0] = y0[j]; y[j][1] = y1[j]; }
+}
+
 // The same pass fed by masks: pass 3 reads 48 B and writes 64 B instead of 80 + 64.  Two frames per thread (N = S*T and the
-// window length are even on this path): 16-byte loads of the mix, 8-byte loads of the masks, 16-byte stores.
+// window length are even on this path): 16-byte loads of the mix, 8-byte loads of the masks, 16-byte stores.  J sources from the
+// start ST (start_channel); the masks' arena has 8B channels, the estimates' 2JB.
+template <int J, Start ST>
 __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __restrict__ X, const float* __restrict__ Mk,
                                                               float2* __restrict__ Y, const WRow* __restrict__ rows,
                                                               const float* __restrict__ stats, int Bn, int S, int win_len) {
@@ -212,7 +258,7 @@ __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __res
     const int64_t N = (int64_t)S * r.T;
     const int64_t n = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);       // frames n, n + 1 (same window: both even)
     if (n >= N) return;
-    const float* st = stats + r.stat + (n / win_len) * STAT;
+    const float* st = stats + r.stat + (n / win_len) * Slot<J>::N;
     const float4 xa = *reinterpret_cast<const float4*>(X + aidx(r, 2 * Bn, S, r.b * 2, n));
     const float4 xb = *reinterpret_cast<const float4*>(X + aidx(r, 2 * Bn, S, r.b * 2 + 1, n));
     const int64_t cstride = (int64_t)r.F * N, jstride = (int64_t)Bn * 2 * cstride;
@@ -223,22 +269,30 @@ __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __res
         ma[j] = *reinterpret_cast<const float2*>(m0 + j * jstride);
         mb[j] = *reinterpret_cast<const float2*>(m0 + j * jstride + cstride);
     }
-    float2 y[4][2], o0[4][2], o1[4][2];
+    float2 y[J][2], o0[J][2], o1[J][2];
+    if constexpr (J == 4 && ST == Start::MixPhase) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        y[j][0] = make_float2(ma[j].x * xa.x, ma[j].x * xa.y);
-        y[j][1] = make_float2(mb[j].x * xb.x, mb[j].x * xb.y);
+        for (int j = 0; j < 4; ++j) {
+            y[j][0] = make_float2(ma[j].x * xa.x, ma[j].x * xa.y);
+            y[j][1] = make_float2(mb[j].x * xb.x, mb[j].x * xb.y);
+        }
+    } else {
+        point_start<J, ST>(make_float2(xa.x, xa.y), make_float2(xb.x, xb.y), ma, mb, false, y);
     }
-    wiener_point(st, make_float2(xa.x, xa.y), make_float2(xb.x, xb.y), y, o0);
+    wiener_point<J>(st, make_float2(xa.x, xa.y), make_float2(xb.x, xb.y), y, o0);
+    if constexpr (J == 4 && ST == Start::MixPhase) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        y[j][0] = make_float2(ma[j].y * xa.z, ma[j].y * xa.w);
-        y[j][1] = make_float2(mb[j].y * xb.z, mb[j].y * xb.w);
+        for (int j = 0; j < 4; ++j) {
+            y[j][0] = make_float2(ma[j].y * xa.z, ma[j].y * xa.w);
+            y[j][1] = make_float2(mb[j].y * xb.z, mb[j].y * xb.w);
+        }
+    } else {
+        point_start<J, ST>(make_float2(xa.z, xa.w), make_float2(xb.z, xb.w), ma, mb, true, y);
     }
-    wiener_point(st, make_float2(xa.z, xa.w), make_float2(xb.z, xb.w), y, o1);
-    float2* y0p = Y + aidx(r, 8 * Bn, S, r.b * 2, n);
+    wiener_point<J>(st, make_float2(xa.z, xa.w), make_float2(xb.z, xb.w), y, o1);
+    float2* y0p = Y + aidx(r, 2 * J * Bn, S, r.b * 2, n);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < J; ++j) {
         *reinterpret_cast<float4*>(y0p + j * jstride) = make_float4(o0[j][0].x, o0[j][0].y, o1[j][0].x, o1[j][0].y);
         *reinterpret_cast<float4*>(y0p + j * jstride + cstride) = make_float4(o0[j][1].x, o0[j][1].y, o1[j][1].x, o1[j][1].y);
     }
@@ -262,7 +316,7 @@ struct WPoint {
 __device__ inline void wiener_bwd_point(const float* __restrict__ st, float2 x0, float2 x1, const float2 (&y)[4][2],
                                         const float2 (&g)[4][2], WPoint& P) {
     const float inv_ma2 = st[16];
-    WR R;
+    WR<4> R;
     load_R(st, R);
 #pragma unroll
     for (int j = 0; j < 4; ++j) P.v[j] = power(y[j][0], y[j][1], inv_ma2);
@@ -427,12 +481,13 @@ __global__ __launch_bounds__(256) void k_wiener_window_max(const float2* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
-static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int group, WTable* out) {
+// slot: floats per (row, window) of the statistics (Slot<J>::N)
+static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int group, WTable* out, int slot = STAT) {
     std::vector<int> key;
     int dev = 0;
     XSQ_HIP(hipGetDevice(&dev));                 // the tables live in one device's memory: keyed by it
     key.push_back(dev);
-    key.push_back(nblocks); key.push_back(Bn); key.push_back(S); key.push_back(win_len); key.push_back(group);
+    key.push_back(nblocks); key.push_back(Bn); key.push_back(S); key.push_back(win_len); key.push_back(group); key.push_back(slot);
     for (int b = 0; b < nblocks; ++b) { key.push_back(F[b]); key.push_back(T[b]); }
     std::lock_guard<std::mutex> lk(g_wmu);
     auto it = g_wtables.find(key);
@@ -455,7 +510,7 @@ static int get_wtable(int nblocks, const int32_t* F, const int32_t* T, int Bn, i
                 r.cum = cum; r.stat = stat;
                 for (int w = 0; w < nwin; ++w) { work.push_back((int)rows.size()); work.push_back(w); }
                 rows.push_back(r);
-                stat += (int64_t)nwin * STAT;
+                stat += (int64_t)nwin * slot;
             }
         for (int gI = 0; gI < Bn / group; ++gI)
             for (int w = 0; w < nwin; ++w) { blockwin.push_back(first + gI * group * F[k]); blockwin.push_back(w); }
@@ -524,7 +579,29 @@ struct EmCall {                     // the arguments of a forward entry point
     void* ws;
     size_t ws_bytes;
     hipStream_t stream;
+    int flags = 0;                  // XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL: J = 5 sources with the latter
 };
+
+static inline int sources_of(int flags) { return (flags & XSQ_WIENER_RESIDUAL) ? 5 : 4; }
+static inline int slot_of(int J) { return J == 5 ? Slot<5>::N : Slot<4>::N; }
+static inline int res_window_of(int J) { return J == 5 ? res_max_window<5> : res_max_window<4>; }
+
+// f(integral_constant<int, J>, integral_constant<Start, ST>) for the call's option set; ST is the mixture phase where the
+// estimates are given (the start is theirs)
+template <bool MASKED, class Fn>
+static void with_options(int flags, Fn&& f) {
+    using Mix = std::integral_constant<Start, Start::MixPhase>;
+    using Soft = std::integral_constant<Start, Start::Softmask>;
+    using J4 = std::integral_constant<int, 4>;
+    using J5 = std::integral_constant<int, 5>;
+    if constexpr (MASKED) {
+        if (flags & XSQ_WIENER_SOFTMASK) {
+            if (sources_of(flags) == 5) f(J5{}, Soft{}); else f(J4{}, Soft{});
+            return;
+        }
+    }
+    if (sources_of(flags) == 5) f(J5{}, Mix{}); else f(J4{}, Mix{});
+}
 
 // the longest window a call runs: win_len, or the longest row when that is shorter
 static int64_t longest_window(int nblocks, const int32_t* T, int S, int win_len) {
@@ -533,29 +610,41 @@ static int64_t longest_window(int nblocks, const int32_t* T, int S, int win_len)
     return std::min<int64_t>(win_len, maxN);
 }
 
-// workspace of the iteration entry points: the statistics of xsq_wiener_workspace | max |x|^2 per (block, group, window) of
-// the resident form
-static size_t iter_stats_bytes(const EmCall& c) { return al256(xsq_wiener_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len)); }
+// statistics of J sources: one slot per (row, window)
+static size_t stats_bytes(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int J) {
+    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0) return 0;
+    int64_t stat = 0;
+    for (int k = 0; k < nblocks; ++k)
+        stat += (int64_t)Bn * F[k] * (((int64_t)S * T[k] + win_len - 1) / win_len) * slot_of(J);
+    return (size_t)stat * 4 + 256;
+}
+
+// workspace of the iteration entry points: the statistics | max |x|^2 per (block, group, window) of the resident form
+static size_t iter_stats_bytes(const EmCall& c) { return al256(stats_bytes(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, sources_of(c.flags))); }
+static size_t iter_bytes(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int J) {
+    return al256(stats_bytes(nblocks, F, T, Bn, S, win_len, J)) + (size_t)xsq_wiener_num_windows(nblocks, F, T, Bn, S, win_len, 1) * 4 + 256;
+}
 
 // The argument checks of every forward entry point; no HIP call.  `masked`: the entry point takes masks; `iter`: it takes
 // niter / method and the larger workspace.  Defaults batch_group; *resident: the form the call takes (niter >= 2).
 static int check_em(const char* who, EmCall& c, bool masked, bool iter, int niter, int method, bool* resident) {
     if (int rc = check_table(who, c.nblocks, c.F, c.T, c.Bn, c.S)) return rc;
     XSQ_REQUIRE(c.X && c.Y && c.ws && (c.masks || !masked), "%s: null argument", who);
+    XSQ_REQUIRE((c.flags & ~(XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)) == 0, "%s: flags=%d (XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)", who, c.flags);
+    const int J = sources_of(c.flags);
     if (masked) XSQ_REQUIRE(c.win_len > 0 && c.win_len % 2 == 0, "%s: win_len=%d must be even (two frames per thread)", who, c.win_len);
     XSQ_REQUIRE(c.win_len > 0, "%s: win_len=%d", who, c.win_len);
-    XSQ_REQUIRE(niter != 0 || !masked, "%s: niter=0 is the mix-phase estimate mask * X, which has no EM pass "
-                                       "(xsq_slicqt_inverse_masked forms it)", who);
+    XSQ_REQUIRE(niter != 0 || !masked || c.flags, "%s: niter=0 is the mix-phase estimate mask * X, which has no EM pass "
+                                                  "(xsq_slicqt_inverse_masked forms it)", who);
     XSQ_REQUIRE(niter >= 0, "%s: niter=%d", who, niter);
     XSQ_REQUIRE(method >= 0 && method <= 2, "%s: method=%d (0 auto, 1 looped, 2 resident)", who, method);
     const int64_t longest = longest_window(c.nblocks, c.T, c.S, c.win_len);
-    const bool fits = longest <= RES_MAX_WINDOW;
+    const bool fits = longest <= res_window_of(J);
     XSQ_REQUIRE(method != 2 || fits, "%s: the resident form holds windows of at most %d frames (this call's longest has %lld)", who,
-                RES_MAX_WINDOW, (long long)longest);
+                res_window_of(J), (long long)longest);
     if (c.batch_group <= 0) c.batch_group = c.Bn;
     XSQ_REQUIRE(c.Bn % c.batch_group == 0, "%s: batch_group=%d does not divide B=%d", who, c.batch_group, c.Bn);
-    const size_t need = iter ? xsq_wiener_iter_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, niter, method)
-                             : xsq_wiener_workspace(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len);
+    const size_t need = iter ? iter_bytes(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, J) : stats_bytes(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, J);
     XSQ_REQUIRE(c.ws_bytes >= need, "%s: workspace too small", who);
     for (int b = 0; masked && b < c.nblocks; ++b)
         XSQ_REQUIRE(((int64_t)c.S * c.T[b]) % 2 == 0, "%s: block %d has an odd frame count S*T=%lld", who, b, (long long)c.S * c.T[b]);
@@ -573,29 +662,57 @@ static void launch_window_max(const WTable& t, const float* X, float* ext_max, i
 static void launch_apply(const WTable& t, const EmCall& c, const float* masks) {
     XSQ_PROF("wiener_apply", c.stream);
     if (masks)
-        hipLaunchKernelGGL(k_wiener_apply_masked, dim3((unsigned)((t.max_frames / 2 + 255) / 256), t.nrows), dim3(256), 0, c.stream,
-                           (const float2*)c.X, masks, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+        with_options<true>(c.flags, [&](auto j, auto st) {
+            hipLaunchKernelGGL((k_wiener_apply_masked<decltype(j)::value, decltype(st)::value>), dim3((unsigned)((t.max_frames / 2 + 255) / 256), t.nrows),
+                               dim3(256), 0, c.stream, (const float2*)c.X, masks, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+        });
     else
-        hipLaunchKernelGGL(k_wiener_apply, dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, c.stream,
-                           (const float2*)c.X, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+        with_options<false>(c.flags, [&](auto j, auto) {
+            hipLaunchKernelGGL((k_wiener_apply<decltype(j)::value>), dim3((unsigned)((t.max_frames + 255) / 256), t.nrows), dim3(256), 0, c.stream,
+                               (const float2*)c.X, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+        });
 }
 
 template <YFrom SRC>
 static void launch_stats(const WTable& t, const EmCall& c) {
     XSQ_PROF(SRC == YFrom::Current ? "wiener_stats_iter" : "wiener_stats", c.stream);
-    hipLaunchKernelGGL(k_wiener_stats<SRC>, dim3(t.nwork), dim3(256), 0, c.stream, (const float2*)c.X, (const float2*)c.Y, c.masks, t.d_rows,
-                       t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
+    with_options<SRC == YFrom::Masks>(c.flags, [&](auto j, auto st) {
+        hipLaunchKernelGGL((k_wiener_stats<SRC, decltype(j)::value, decltype(st)::value>), dim3(t.nwork), dim3(256), 0, c.stream,
+                           (const float2*)c.X, (const float2*)c.Y, c.masks, t.d_rows, t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
+    });
+}
+
+// the J starts of an option set into Y (2JB channels), from the masks or from magnitudes (a: real arena of 8B channels)
+static int launch_start(const WTable& t, const float* X, const float* a, bool from_masks, float* Y, int Bn, int S, int flags, hipStream_t stream) {
+    XSQ_PROF("wiener_start", stream);
+    const dim3 grid((unsigned)((t.max_frames + 255) / 256), t.nrows);
+    using Mix = std::integral_constant<Start, Start::MixPhase>;
+    using Soft = std::integral_constant<Start, Start::Softmask>;
+    auto go = [&](auto j, auto st) {
+        constexpr int J = decltype(j)::value;
+        constexpr Start ST = decltype(st)::value;
+        if (from_masks) hipLaunchKernelGGL((k_wiener_start<J, ST, true>), grid, dim3(256), 0, stream, (const float2*)X, a, (float2*)Y, t.d_rows, Bn, S);
+        else hipLaunchKernelGGL((k_wiener_start<J, ST, false>), grid, dim3(256), 0, stream, (const float2*)X, a, (float2*)Y, t.d_rows, Bn, S);
+    };
+    const bool soft = flags & XSQ_WIENER_SOFTMASK;
+    if (sources_of(flags) == 5) { if (soft) go(std::integral_constant<int, 5>{}, Soft{}); else go(std::integral_constant<int, 5>{}, Mix{}); }
+    else if (soft) go(std::integral_constant<int, 4>{}, Soft{});
+    else { set_error("xsq_wiener_start: no option set (xsq_phasemix / mask * X is that start)"); return XSQ_ERR_ARG; }
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
 }
 
 // niter >= 1 iterations of the looped form: the three launches of iteration 1, then statistics + apply per further one (the
 // estimates are in Y and 1/ma^2 in the stats slots by then)
 static int run_em(const EmCall& c, int niter) {
     WTable t;
-    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t)) return rc;
+    const int J = sources_of(c.flags);
+    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t, slot_of(J))) return rc;
     if (c.masks) launch_stats<YFrom::Masks>(t, c);
     else launch_stats<YFrom::Estimates>(t, c);
     { XSQ_PROF("wiener_finalize", c.stream);
-    hipLaunchKernelGGL(k_wiener_finalize, dim3(t.nblockwin), dim3(256), 0, c.stream, t.d_rows, t.d_blockwin, (float*)c.ws, c.ext_max); }
+    hipLaunchKernelGGL((J == 5 ? k_wiener_finalize<5> : k_wiener_finalize<4>), dim3(t.nblockwin), dim3(256), 0, c.stream, t.d_rows, t.d_blockwin,
+                       (float*)c.ws, c.ext_max); }
     launch_apply(t, c, c.masks);
     for (int it = 2; it <= niter; ++it) {
         launch_stats<YFrom::Current>(t, c);
@@ -607,14 +724,18 @@ static int run_em(const EmCall& c, int niter) {
 
 static int run_resident(const EmCall& c, int niter) {
     WTable t;
-    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t)) return rc;
+    if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t, slot_of(sources_of(c.flags)))) return rc;
     float* wmax = (float*)((char*)c.ws + iter_stats_bytes(c));
     XSQ_HIP(hipMemsetAsync(wmax, 0, (size_t)t.nblockwin * 4, c.stream));
     launch_window_max(t, c.X, wmax, c.Bn, c.S, c.win_len, c.stream);
     { XSQ_PROF("wiener_resident", c.stream);
-    hipLaunchKernelGGL(c.masks ? k_wiener_resident<true> : k_wiener_resident<false>, dim3(t.nwork), dim3(RES_THREADS), 0, c.stream,
-                       (const float2*)c.X, c.masks, (float2*)c.Y, t.d_rows, t.d_work, t.d_bw_of_work, wmax, c.ext_max, c.Bn, c.S, c.win_len,
-                       niter); }
+    auto go = [&](auto masked, auto j, auto st) {
+        hipLaunchKernelGGL((k_wiener_resident<decltype(masked)::value, decltype(j)::value, decltype(st)::value>), dim3(t.nwork), dim3(RES_THREADS), 0,
+                           c.stream, (const float2*)c.X, c.masks, (float2*)c.Y, t.d_rows, t.d_work, t.d_bw_of_work, wmax, c.ext_max, c.Bn, c.S,
+                           c.win_len, niter);
+    };
+    if (c.masks) with_options<true>(c.flags, [&](auto j, auto st) { go(std::true_type{}, j, st); });
+    else with_options<false>(c.flags, [&](auto j, auto st) { go(std::false_type{}, j, st); }); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
 }
@@ -622,7 +743,12 @@ static int run_resident(const EmCall& c, int niter) {
 static int em(const char* who, EmCall c, bool masked, bool iter, int niter, int method) {
     bool resident;
     if (int rc = check_em(who, c, masked, iter, niter, method, &resident)) return rc;
-    if (niter == 0) return XSQ_OK;                        // the initial estimate is the result (norbert :247-251)
+    if (niter == 0) {                                     // the initial estimate is the result (norbert :247-251)
+        if (!masked || !c.flags) return XSQ_OK;
+        WTable t;
+        if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t, slot_of(sources_of(c.flags)))) return rc;
+        return launch_start(t, c.X, c.masks, true, c.Y, c.Bn, c.S, c.flags, c.stream);
+    }
     return resident ? run_resident(c, niter) : run_em(c, niter);
 }
 
@@ -646,11 +772,7 @@ int xsq_phasemix(int nblocks, const int32_t* F, const int32_t* T, const float* X
 }
 
 size_t xsq_wiener_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len) {
-    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0) return 0;
-    int64_t stat = 0;
-    for (int k = 0; k < nblocks; ++k)
-        stat += (int64_t)Bn * F[k] * (((int64_t)S * T[k] + win_len - 1) / win_len) * STAT;
-    return (size_t)stat * 4 + 256;
+    return stats_bytes(nblocks, F, T, Bn, S, win_len, 4);
 }
 
 int64_t xsq_wiener_num_windows(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int batch_group) {
@@ -662,11 +784,49 @@ int64_t xsq_wiener_num_windows(int nblocks, const int32_t* F, const int32_t* T, 
     return n;
 }
 
-int xsq_wiener_resident_max_window(void) { return RES_MAX_WINDOW; }
+int xsq_wiener_resident_max_window(void) { return res_max_window<4>; }
+
+int xsq_wiener_resident_max_window_sources(int nsources) { return nsources == 4 || nsources == 5 ? res_window_of(nsources) : 0; }
 
 size_t xsq_wiener_iter_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int niter, int method) {
     if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0 || niter < 0 || method < 0 || method > 2) return 0;
-    return al256(xsq_wiener_workspace(nblocks, F, T, Bn, S, win_len)) + (size_t)xsq_wiener_num_windows(nblocks, F, T, Bn, S, win_len, 1) * 4 + 256;
+    return iter_bytes(nblocks, F, T, Bn, S, win_len, 4);
+}
+
+// ---- the option set: softmask start, residual fifth source (norbert.wiener use_softmask, norbert.contrib.residual_model) -----
+size_t xsq_wiener_options_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len, int niter, int method,
+                                    int flags) {
+    if (nblocks <= 0 || !F || !T || Bn <= 0 || S <= 0 || win_len <= 0 || niter < 0 || method < 0 || method > 2 ||
+        (flags & ~(XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)))
+        return 0;
+    return iter_bytes(nblocks, F, T, Bn, S, win_len, sources_of(flags));
+}
+
+int xsq_wiener_start(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* mag, float* Y, int Bn, int S, int flags,
+                     void* stream_) {
+    int rc = check_table("xsq_wiener_start", nblocks, F, T, Bn, S);
+    if (rc) return rc;
+    XSQ_REQUIRE(X && mag && Y, "xsq_wiener_start: null argument");
+    XSQ_REQUIRE(flags && (flags & ~(XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)) == 0,
+                "xsq_wiener_start: flags=%d (XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL, at least one)", flags);
+    WTable t;
+    if ((rc = get_wtable(nblocks, F, T, Bn, S, 5000, Bn, &t))) return rc;
+    return launch_start(t, X, mag, false, Y, Bn, S, flags, (hipStream_t)stream_);
+}
+
+int xsq_wiener_em_options(int nblocks, const int32_t* F, const int32_t* T, const float* X, float* Y, int Bn, int S, int win_len,
+                          int batch_group, int niter, int method, int flags, void* ws, size_t ws_bytes, void* stream_) {
+    EmCall c{nblocks, F, T, X, nullptr, Y, Bn, S, win_len, batch_group, nullptr, ws, ws_bytes, (hipStream_t)stream_};
+    c.flags = flags;
+    return em("xsq_wiener_em_options", c, false, true, niter, method);
+}
+
+int xsq_wiener_em_masked_options(int nblocks, const int32_t* F, const int32_t* T, const float* X, const float* masks, float* Y, int Bn,
+                                 int S, int win_len, int batch_group, const float* ext_max, int niter, int method, int flags, void* ws,
+                                 size_t ws_bytes, void* stream_) {
+    EmCall c{nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, (hipStream_t)stream_};
+    c.flags = flags;
+    return em("xsq_wiener_em_masked_options", c, true, true, niter, method);
 }
 
 int xsq_wiener_window_max(int nblocks, const int32_t* F, const int32_t* T, const float* X, int Bn, int S, int win_len,

@@ -13,6 +13,17 @@ namespace xsq {
 static const int STAT = 24;   // floats per (row, window): 4 sources x (C00, C11, Re C01, Im C01), max|x|^2, pad[3],
                               // 4 x 1/(sum_n v + eps) (kept for the backward pass)
 
+// The slot of J sources.  J = 4 is the layout above (the training backward reads it); J = 5 (the four targets and the residual
+// of norbert.contrib.residual_model) has 20 sums, max|x|^2 at [20], pad[3], 5 denominators at [24], pad[3].
+template <int J> struct Slot;
+template <> struct Slot<4> { static constexpr int N = STAT, MAX = 16, DEN = 20; };
+template <> struct Slot<5> { static constexpr int N = 32, MAX = 20, DEN = 24; };
+
+// How the initial estimates of a time-frequency point come about (norbert.wiener :247-251): the mixture phase on the magnitudes
+// v_j (use_softmask=False) or the ratio mask x v_j / (eps + sum_j v_j) (softmask, :263-309).  Kernels fed by estimates take them
+// as given.
+enum class Start { MixPhase, Softmask };
+
 struct WRow {          // one (block, batch item, bin) row of the arena
     int F, T;          // block geometry
     int b, f;          // batch item, bin
@@ -26,7 +37,7 @@ __device__ inline float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.
 __device__ inline float abs2(float2 a) { return a.x * a.x + a.y * a.y; }
 
 // arena index of (chan, f, frame n) for a block; nchan = packed channels of the arena.  The complex arenas (mix: 2B channels,
-// estimates: 8B) and the real arena of the masks (8B) share it: an element is a float2 in the former, a float in the latter.
+// estimates: 2JB) and the real arena of the masks (8B) share it: an element is a float2 in the former, a float in the latter.
 __device__ inline int64_t aidx(const WRow& r, int nchan, int S, int chan, int64_t n) {
     return (int64_t)nchan * S * r.cum + ((int64_t)chan * r.F + r.f) * ((int64_t)S * r.T) + n;
 }
@@ -67,33 +78,35 @@ __device__ inline float tree(const float (*red)[NV], int i) {
     return p[0];
 }
 
-// The workgroup's NV accumulators (16 sums; NV = 17: and a maximum in slot 16) over WAVES wavefronts: wavefront butterfly, then
+// The workgroup's NV accumulators (4J sums; NV = 4J + 1: and a maximum in the last slot) over WAVES wavefronts: wavefront butterfly, then
 // the tree over the wave partials.  No atomics: bitwise reproducible.  Thread i < NV stores the total of slot i to out[i] (LDS or
 // global memory).  `red` may be written again after the workgroup's next barrier.
 template <int WAVES, int NV>
 __device__ inline void reduce(const float (&acc)[NV], float (*red)[NV], float* out) {
+    constexpr bool HASMAX = NV % 4 == 1;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float v = acc[i];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const float o = __shfl_xor(v, off, 64);
-            v = (i == 16) ? fmaxf(v, o) : v + o;
+            v = (HASMAX && i == NV - 1) ? fmaxf(v, o) : v + o;
         }
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = v;
     }
     __syncthreads();
     if (threadIdx.x < NV) {
         const int i = threadIdx.x;
-        if (NV == 17 && i == 16) out[i] = tree<WAVES, true>(red, i);
+        if (HASMAX && i == NV - 1) out[i] = tree<WAVES, true>(red, i);
         else out[i] = tree<WAVES, false>(red, i);
     }
 }
 
 // ---- R and the point solve ---------------------------------------------------------------------------------------------
-struct WR {                     // R_j = [[r00, r01], [conj(r01), r11]] of the four sources
-    float r00[4], r11[4];
-    float2 r01[4];
+template <int J>
+struct WR {                     // R_j = [[r00, r01], [conj(r01), r11]] of the J sources
+    float r00[J], r11[J];
+    float2 r01[J];
 };
 
 // raw sums of one source -> R and den = 1 / (sum_n v' + eps)   (norbert :491-493).  inv_ma2 = 1 / ma^2 brings sums of
@@ -107,7 +120,8 @@ __device__ inline void sums_to_R(float s00, float s11, float s01x, float s01y, f
     r01 = make_float2(s01x * inv_ma2 * den, s01y * inv_ma2 * den);
 }
 
-// the same on a statistics slot in place: st[0..15] sums -> R, st[20..23] = den
+// the same on a statistics slot in place: st[0..4J-1] sums -> R, st[DEN..DEN+J-1] = den
+template <int J>
 __device__ inline void sums_to_R_slot(float* st, int j, const float* sums, float inv_ma2) {
     float r00, r11, den;
     float2 r01;
@@ -116,12 +130,13 @@ __device__ inline void sums_to_R_slot(float* st, int j, const float* sums, float
     st[4 * j + 1] = r11;
     st[4 * j + 2] = r01.x;
     st[4 * j + 3] = r01.y;
-    st[20 + j] = den;
+    st[Slot<J>::DEN + j] = den;
 }
 
-__device__ inline void load_R(const float* __restrict__ st, WR& R) {
+template <int J>
+__device__ inline void load_R(const float* __restrict__ st, WR<J>& R) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < J; ++j) {
         R.r00[j] = st[4 * j];
         R.r11[j] = st[4 * j + 1];
         R.r01[j] = make_float2(st[4 * j + 2], st[4 * j + 3]);
@@ -136,12 +151,13 @@ struct WInv {
     float i00, i11;
     float2 i01, i10;
 };
-__device__ inline WInv invert_cxx(const WR& R, const float (&v)[4]) {
+template <int J>
+__device__ inline WInv invert_cxx(const WR<J>& R, const float (&v)[J]) {
     const float reg = sqrtf(FLT_EPSILON);
     float c00 = reg, c11 = reg;
     float2 c01 = make_float2(0.f, 0.f);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < J; ++j) {
         c00 += v[j] * R.r00[j];
         c11 += v[j] * R.r11[j];
         c01.x += v[j] * R.r01[j].x;
@@ -164,7 +180,8 @@ __device__ inline void solve(const WInv& I, float2 a0, float2 a1, float2& z0, fl
 }
 
 // R_j z
-__device__ inline void mul_R(const WR& R, int j, float2 z0, float2 z1, float2& o0, float2& o1) {
+template <int J>
+__device__ inline void mul_R(const WR<J>& R, int j, float2 z0, float2 z1, float2& o0, float2& o1) {
     const float2 a = cmul(R.r01[j], z1);
     const float2 b = cmulc(z0, R.r01[j]);      // conj(R01) * z0
     o0 = make_float2(R.r00[j] * z0.x + a.x, R.r00[j] * z0.y + a.y);
@@ -172,7 +189,8 @@ __device__ inline void mul_R(const WR& R, int j, float2 z0, float2 z1, float2& o
 }
 
 // y_j = v_j R_j z
-__device__ inline void source(const WR& R, int j, float vj, float2 z0, float2 z1, float2& y0, float2& y1) {
+template <int J>
+__device__ inline void source(const WR<J>& R, int j, float vj, float2 z0, float2 z1, float2& y0, float2& y1) {
     float2 o0, o1;
     mul_R(R, j, z0, z1, o0, o1);
     y0 = make_float2(vj * o0.x, vj * o0.y);
@@ -180,17 +198,72 @@ __device__ inline void source(const WR& R, int j, float vj, float2 z0, float2 z1
 }
 
 // one time-frequency point of the filter: estimates y (unscaled), statistics slot st -> filtered estimates o
-__device__ inline void wiener_point(const float* __restrict__ st, float2 x0, float2 x1, const float2 (&y)[4][2], float2 (&o)[4][2]) {
-    const float inv_ma2 = st[16];
-    WR R;
+template <int J>
+__device__ inline void wiener_point(const float* __restrict__ st, float2 x0, float2 x1, const float2 (&y)[J][2], float2 (&o)[J][2]) {
+    const float inv_ma2 = st[Slot<J>::MAX];
+    WR<J> R;
     load_R(st, R);
-    float v[4];
+    float v[J];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = power(y[j][0], y[j][1], inv_ma2);
+    for (int j = 0; j < J; ++j) v[j] = power(y[j][0], y[j][1], inv_ma2);
     float2 z0, z1;
     solve(invert_cxx(R, v), x0, x1, z0, z1);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) source(R, j, v[j], z0, z1, o[j][0], o[j][1]);
+    for (int j = 0; j < J; ++j) source(R, j, v[j], z0, z1, o[j][0], o[j][1]);
+}
+
+// ---- the initial estimates of one channel of one point -------------------------------------------------------------------
+// x/|x| for every finite x.  re^2 + im^2 is a normal fp32 number for |x| in about (1.1e-19, 1.8e19): there the plain form
+// is used (and its bits kept).  Below, the sum of squares is subnormal or 0 (the phase would be lost: x = (1e-30, 1e-30) gave
+// (1, 0)), above it is inf (the output was 0): x is first divided by max(|re|, |im|), which puts the modulus in [1, sqrt 2].
+__device__ __forceinline__ float2 unit_phase(float2 x) {
+    const float a2 = x.x * x.x + x.y * x.y;
+    if (a2 >= FLT_MIN && a2 <= FLT_MAX) {
+        const float ax = sqrtf(a2);
+        return make_float2(x.x / ax, x.y / ax);
+    }
+    const float s = fmaxf(fabsf(x.x), fabsf(x.y));
+    if (!(s > 0.f)) return make_float2(1.f, 0.f);            // angle(0) = 0
+    const float re = x.x / s, im = x.y / s;
+    const float ax = sqrtf(re * re + im * im);
+    return make_float2(re / ax, im / ax);
+}
+
+// The J starts y of one channel from the mix x and a[0..3]: the sigmoid masks m_j (MASKS; v_j = m_j |x|, one fp32 rounding, the
+// products the fp32 oracle forms) or the magnitudes v_j themselves.
+//   J = 5      v_4 = relu(max(|x|, eps) - (((v_0 + v_1) + v_2) + v_3))   (norbert/contrib.py:11-77 with alpha = 1; F.threshold
+//              replaces values <= eps).  Never stored as a magnitude: formed here, as the frame is loaded.
+//   MixPhase   y_j = m_j x for the targets of the masked forms (what every masked kernel formed before there were options),
+//              v_j x/|x| otherwise; the residual is v_4 x/|x|, real where x = 0 (angle(0) = 0).
+//   Softmask   y_j = x v_j / (eps + sum_j v_j), the sum over all J sources.
+template <int J, Start ST, bool MASKS>
+__device__ inline void start_channel(float2 x, const float (&a)[4], float2 (&y)[J]) {
+    if constexpr (J == 4 && ST == Start::MixPhase && MASKS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = make_float2(a[j] * x.x, a[j] * x.y);
+    } else {
+        const float ax = sqrtf(abs2(x));
+        float v[J];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = MASKS ? a[j] * ax : a[j];
+        const float tot4 = ((v[0] + v[1]) + v[2]) + v[3];
+        if constexpr (J == 5) v[4] = fmaxf((ax > FLT_EPSILON ? ax : FLT_EPSILON) - tot4, 0.f);
+        if constexpr (ST == Start::Softmask) {
+            const float den = FLT_EPSILON + (J == 5 ? tot4 + v[J - 1] : tot4);
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const float g = v[j] / den;
+                y[j] = make_float2(g * x.x, g * x.y);
+            }
+        } else {
+            const float2 u = unit_phase(x);
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                if (MASKS && j < 4) y[j] = make_float2(a[j] * x.x, a[j] * x.y);
+                else y[j] = make_float2(v[j] * u.x, v[j] * u.y);
+            }
+        }
+    }
 }
 
 }  // namespace xsq

@@ -119,7 +119,7 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
 
     dev = torch.device(device)
     out_dir = Path(out_dir)
-    names = list(separator.sources) if remix is None else list(remix[0])
+    names = list(separator.sources) + (["residual"] if getattr(separator, "residual", False) else []) if remix is None else list(remix[0])
     model_rate = int(float(separator.sample_rate))
     # the staging buffers outlive the call (page-locking a 339 MB block costs more than demixing the track it carries)
     pool_in, pool_out = _POOLS.setdefault("in", _PinnedPool()), _POOLS.setdefault("out", _PinnedPool())
@@ -187,7 +187,7 @@ def demix_directory(separator, wavs, out_dir, device="cuda", readers: int = 3, w
             else:
                 est = separator(x) if remix is None else separator.remix(x, remix[1])      # (4 | R, 1, 2, N')
             t1.record(main)
-            inter = est[:, 0].transpose(1, 2).contiguous()           # (4, N', 2): the wav payload of each target
+            inter = est[:, 0].transpose(1, 2).contiguous()           # (4 | 5 | R, N', 2): the wav payload of each target
             ready = torch.cuda.Event()
             ready.record(main)
             buf_out = pool_out.take(inter.numel(), depth + writers)
@@ -255,6 +255,11 @@ def parse_args(p: argparse.ArgumentParser, argv=None):
             p.error(f"--niter {args.niter}: the iteration count is >= 0")
         if args.realtime:
             p.error("--niter counts the EM iterations of the offline model's Wiener filter; --realtime is mix-phase and has none")
+    for opt in ("softmask", "residual"):
+        if getattr(args, opt) and args.realtime:
+            p.error(f"--{opt} is an option of the offline model's Wiener filter; --realtime is mix-phase and has none")
+    if args.residual and args.remix:
+        p.error("--residual writes residual.wav beside the four stems; --remix weights the four targets and has no column for it")
     if args.segment is not None or args.overlap is not None:
         if args.remix:
             p.error("--segment / --overlap write the four stems from overlapped, cross-faded segments; an overlapped --remix is not built")
@@ -282,6 +287,12 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--niter", type=int, default=None, metavar="N",
                    help="EM iterations of the Wiener post-filter of the offline model (default 1, the reference's; 0 = mix-phase); "
                         "not with --realtime, which has no EM")
+    p.add_argument("--softmask", action="store_true",
+                   help="start the Wiener post-filter from the ratio mask instead of the mixture phase (norbert's use_softmask); "
+                        "not with --realtime")
+    p.add_argument("--residual", action="store_true",
+                   help="add a fifth source holding what the four target models do not explain and write it as residual.wav beside "
+                        "the four stems; not with --realtime or --remix")
     p.add_argument("--segment", type=float, default=None, metavar="SECONDS",
                    help="demix in overlapped, cross-faded segments of this hop (Separator.forward_overlapped, default 10.0 once "
                         "--segment or --overlap is given) instead of hard-joined chunks; not with --remix")
@@ -300,9 +311,11 @@ def inference_main(argv=None):
         p.error(str(e))
     if args.model_path:
         separator = Separator.load(model_path=args.model_path, runtime_backend="hip-rocm",
-                                   warmup=args.warmup, realtime=args.realtime, device=args.device, niter=args.niter)
+                                   warmup=args.warmup, realtime=args.realtime, device=args.device, niter=args.niter,
+                                   softmask=args.softmask or None, residual=args.residual or None)
     else:
-        separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter)
+        separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter, softmask=args.softmask or None,
+                                     residual=args.residual or None)
     overlapped = overlapped_option(args)
     if overlapped is not None:
         try:

@@ -234,6 +234,11 @@ class Unmix(nn.Module):
         self.niter = 1
         # form of niter >= 2 ("auto", "looped", "resident": phase.wiener_em_arena); anything but "auto" is an A/B switch
         self.niter_method = "auto"
+        # the other two post-filter options of the Open-Unmix family, read per call: ``softmask`` starts the filter from the ratio
+        # mask (norbert.wiener use_softmask), ``residual`` adds a fifth source holding what the four targets do not explain
+        # (norbert.contrib.residual_model): forward then returns (5, B, 2, ...) per block, residual last
+        self.softmask = False
+        self.residual = False
         self.precision = os.environ.get("XSQ_CDAE_PRECISION", "fp32")
         if self.precision not in _PRECISIONS:
             raise ValueError(f"XSQ_CDAE_PRECISION={self.precision!r} not in {sorted(_PRECISIONS)}")
@@ -315,6 +320,8 @@ class Unmix(nn.Module):
         ver = self._version()
         cached = self._handles.get(idx)
         if cached is not None and cached[0] == ver:
+            # (the option set of the whole native call is state of the handle, read per call: two ints, set every time)
+            _lib.check(_lib.lib.xsq_model_set_wiener_options(cached[1], *self.wiener_options()), "xsq_model_set_wiener_options")
             return cached[1]
         if cached is not None:
             _lib.lib.xsq_model_destroy(cached[1])
@@ -330,8 +337,19 @@ class Unmix(nn.Module):
             # inside the device guard: bf16 modes allocate and launch on the CURRENT device
             _lib.check(_lib.lib.xsq_model_set_precision(out, _PRECISIONS[self.precision]), "xsq_model_set_precision")
             _lib.check(_lib.lib.xsq_model_set_winograd(out, int(getattr(self, "winograd", 7))), "xsq_model_set_winograd")
+            _lib.check(_lib.lib.xsq_model_set_wiener_options(out, *self.wiener_options()), "xsq_model_set_wiener_options")
         self._handles[idx] = (ver, out)
         return out
+
+    def wiener_options(self):
+        """(softmask, residual) as ints; ``XsqError`` naming the option when a mix-phase-only (realtime) block is asked for one: both
+        belong to the Wiener filter of the offline model (``niter`` = 0 is its initial estimate)."""
+        soft, res = int(bool(getattr(self, "softmask", False))), int(bool(getattr(self, "residual", False)))
+        if (soft or res) and any(bool(blk.realtime) for blk in self.sliced_umx):
+            which = " and ".join(n for n, on in (("softmask", soft), ("residual", res)) if on)
+            raise _lib.XsqError(f"{which}: an option of the offline model's Wiener post-filter; a realtime (mix-phase) model has none "
+                                "(niter = 0 on the offline model is its initial estimate)")
+        return soft, res
 
     def set_precision(self, precision: str):
         """Arithmetic of the convolution contractions: "fp32" (exact, v_mfma_f32_32x32x2_f32) or "bf16x3"
@@ -412,7 +430,8 @@ class Unmix(nn.Module):
     def forward(self, Xcomplex: List[Tensor], return_masks=False, wiener_batch_group: int = 0, xin_ready: bool = False):
         """list over blocks of (B, 2, F_b, S, T_b, 2) -> list of (4, B, 2, F_b, S, T_b, 2)
         [+ masks (4, B, 2, F_b, S, T_b)].  model.py:69-82.  An offline model runs ``self.niter`` EM iterations
-        (default 1, the reference's; 0 = mix-phase).  ``wiener_batch_group`` (extension):
+        (default 1, the reference's; 0 = mix-phase) from the start ``self.softmask`` selects, over five sources with
+        ``self.residual`` ((5, B, 2, ...) per block, residual last).  ``wiener_batch_group`` (extension):
         runs of that many batch items share the Wiener window maximum (0 = the whole batch, the
         reference's behaviour); Separator uses it to stack independent chunks along the batch."""
         from .phase import wiener_em_arena, wiener_em_masked_arena
@@ -429,6 +448,10 @@ class Unmix(nn.Module):
         if niter < 0:
             raise _lib.XsqError(f"Unmix.niter must be >= 0 (got {niter})")
         method = getattr(self, "niter_method", "auto")
+        softmask, residual = self.wiener_options()
+        if softmask or residual:
+            return self._forward_options(X, B, S, h, niter, method, bool(softmask), bool(residual), return_masks, wiener_batch_group,
+                                         xin_ready)
         phasemix = modes.pop() or niter == 0           # no EM iteration: the initial estimate mask * X is the result
         # Wiener-EM from the masks (default): the last layer stores the real masks only and both EM passes form the
         # initial estimate mask * X while they load -- same bits, a third less traffic.  ``wiener_masked = False`` /
@@ -451,6 +474,29 @@ class Unmix(nn.Module):
             elif not phasemix:
                 wiener_em_arena(self.table, X, Y, B, S, batch_group=wiener_batch_group, niter=niter, method=method)
         Ylist = self.table.views(Y, (4, B, 2), S)
+        if return_masks:
+            return Ylist, self.table.views(masks, (4, B, 2), S, complex_=False)
+        return Ylist
+
+    def _forward_options(self, X, B, S, h, niter, method, softmask, residual, return_masks, group, xin_ready):
+        """``forward`` under an option set: the last layer stores the masks only and the filter forms its J starts from them and
+        the mix as the frames are loaded (``wiener_em_masked_arena``; ``niter`` = 0 writes the starts).  There is no two-step arm."""
+        from .phase import nb_sources, wiener_em_masked_arena
+        if not all(int(t) % 2 == 0 for t in self._T):
+            raise _lib.XsqError("softmask / residual run from the masks, two frames per thread: every block needs an even T")
+        dev, J = X.device, nb_sources(residual)
+        with torch.cuda.device(dev):
+            Y = torch.empty(self.table.numel(2 * J * B, S), dtype=torch.float32, device=dev)
+            masks = torch.empty(self.table.numel(8 * B, S, complex_=False), dtype=torch.float32, device=dev)
+            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
+            if nbytes == 0:
+                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
+            ws = self._workspace(dev, nbytes)
+            _lib.check(_lib.lib.xsq_cdae_forward_xin(h, X.data_ptr(), B, S, None, masks.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _lib.stream_ptr(), int(bool(xin_ready))), "xsq_cdae_forward")
+            wiener_em_masked_arena(self.table, X, masks, Y, B, S, batch_group=group, niter=niter, method=method, softmask=softmask,
+                                   residual=residual)
+        Ylist = self.table.views(Y, (J, B, 2), S)
         if return_masks:
             return Ylist, self.table.views(masks, (4, B, 2), S, complex_=False)
         return Ylist

@@ -51,16 +51,49 @@ def _niter_method(niter, method):
     return niter, METHODS[method]
 
 
-def resident_max_window() -> int:
-    """Longest window (frames) the window-resident EM kernel holds on chip."""
-    return int(_lib.lib.xsq_wiener_resident_max_window())
+SOFTMASK, RESIDUAL = 1, 2                              # XSQ_WIENER_SOFTMASK, XSQ_WIENER_RESIDUAL (include/xumx_slicq_hip.h)
 
 
-def _em(table: BlockTable, X: Tensor, masks, Y: Tensor, B: int, S: int, win_len: int, batch_group: int, niter: int, meth: int):
+def option_flags(softmask=False, residual=False) -> int:
+    """The flag word of the post-filter options: ``softmask`` (ratio-mask start, norbert.wiener use_softmask) and ``residual``
+    (a fifth source holding what the four targets do not explain, norbert.contrib.residual_model)."""
+    return (SOFTMASK if softmask else 0) | (RESIDUAL if residual else 0)
+
+
+def nb_sources(residual=False) -> int:
+    """Sources of the estimates' arena: the four targets, and the residual last when it is on."""
+    return 5 if residual else 4
+
+
+def resident_max_window(nb_sources: int = 4) -> int:
+    """Longest window (frames) the window-resident EM kernel holds on chip for ``nb_sources`` sources (4, or 5 with the
+    residual: fewer frames per thread fit)."""
+    if int(nb_sources) == 4:
+        return int(_lib.lib.xsq_wiener_resident_max_window())
+    n = int(_lib.lib.xsq_wiener_resident_max_window_sources(int(nb_sources)))
+    if n <= 0:
+        raise ValueError(f"nb_sources must be 4 or 5 (got {nb_sources})")
+    return n
+
+
+def _em(table: BlockTable, X: Tensor, masks, Y: Tensor, B: int, S: int, win_len: int, batch_group: int, niter: int, meth: int, flags: int = 0):
     """Workspace query, workspace and call of the entry point that (``masks is None``, ``niter``) select: one iteration is
-    xsq_wiener_em / xsq_wiener_em_masked, any other count the ``_iter`` form of the same."""
+    xsq_wiener_em / xsq_wiener_em_masked, any other count the ``_iter`` form of the same; an option set (``flags``) the
+    ``_options`` form."""
     F, T = _tables(table)
     geometry = (len(table), F.ctypes.data, T.ctypes.data)
+    if flags:
+        name = "xsq_wiener_em_options" if masks is None else "xsq_wiener_em_masked_options"
+        arenas = (X.data_ptr(), Y.data_ptr()) if masks is None else (X.data_ptr(), masks.data_ptr(), Y.data_ptr())
+        ext_max = () if masks is None else (None,)
+        with torch.cuda.device(X.device):
+            nbytes = _lib.lib.xsq_wiener_options_workspace(*geometry, B, S, win_len, niter, meth, flags)
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_wiener_options_workspace: bad arguments")
+            ws = _workspace(X.device, nbytes)
+            _lib.check(getattr(_lib.lib, name)(*geometry, *arenas, B, S, win_len, int(batch_group), *ext_max, niter, meth, flags,
+                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+        return
     name, arenas = "xsq_wiener_em", (X.data_ptr(), Y.data_ptr())
     if masks is not None:
         name, arenas = "xsq_wiener_em_masked", (X.data_ptr(), masks.data_ptr(), Y.data_ptr())
@@ -78,25 +111,37 @@ def _em(table: BlockTable, X: Tensor, masks, Y: Tensor, B: int, S: int, win_len:
 
 
 def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
-                    batch_group: int = 0, niter: int = 1, method: str = "auto"):
+                    batch_group: int = 0, niter: int = 1, method: str = "auto", softmask: bool = False, residual: bool = False):
     """``niter`` EM iterations in place on the estimates arena Y (8B channels) given the
     mix arena X (2B channels).  phase.py:43-59 + norbert/__init__.py:153-260 (the reference calls it with one).
     ``batch_group``: runs of that many batch items share the window maximum (0 = whole batch).
     ``niter`` = 0 leaves Y alone, 1 is the reference's call; ``method`` ("auto", "looped", "resident") picks the form of
-    ``niter`` >= 2 (include/xumx_slicq_hip.h, xsq_wiener_em_iter)."""
+    ``niter`` >= 2 (include/xumx_slicq_hip.h, xsq_wiener_em_iter).  ``residual``: Y has 10B channels, the residual's start
+    last (``wiener_start_arena`` writes the starts of an option set); ``softmask`` belongs to the start and changes nothing here."""
     niter, meth = _niter_method(niter, method)
     if niter:
-        _em(table, X, None, Y, B, S, win_len, batch_group, niter, meth)
+        _em(table, X, None, Y, B, S, win_len, batch_group, niter, meth, option_flags(False, residual))
+
+
+def wiener_start_arena(table: BlockTable, X: Tensor, mag: Tensor, Y: Tensor, B: int, S: int, softmask: bool = False, residual: bool = False):
+    """The initial estimates of an option set from the magnitudes ``mag`` (real arena, 8B channels) into Y (8B channels, 10B
+    with ``residual``): norbert.wiener :247-251 after contrib.residual_model.  At least one option (``xsq_phasemix`` is the
+    start without)."""
+    F, T = _tables(table)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.lib.xsq_wiener_start(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), mag.data_ptr(), Y.data_ptr(), B, S,
+                                             option_flags(softmask, residual), _lib.stream_ptr()), "xsq_wiener_start")
 
 
 def wiener_em_masked_arena(table: BlockTable, X: Tensor, masks: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
-                           batch_group: int = 0, niter: int = 1, method: str = "auto"):
+                           batch_group: int = 0, niter: int = 1, method: str = "auto", softmask: bool = False, residual: bool = False):
     """The same iteration fed by the sigmoid masks (real arena, 8B channels): the initial estimate mask * X
     (model.py:262-264) is formed while the two passes load, Y (8B channels, complex) is only written.
     Same bits as ``xsq_cdae_forward(Y)`` + ``wiener_em_arena``; a third less HBM traffic.  ``niter`` >= 1, ``method``:
-    as ``wiener_em_arena``."""
+    as ``wiener_em_arena``.  ``softmask`` / ``residual``: the option set, formed from the masks as the frames are loaded
+    (v_j = m_j |x|); Y then has 10B channels with ``residual``, and ``niter`` = 0 writes the starts."""
     niter, meth = _niter_method(niter, method)
-    _em(table, X, masks, Y, B, S, win_len, batch_group, niter, meth)
+    _em(table, X, masks, Y, B, S, win_len, batch_group, niter, meth, option_flags(softmask, residual))
 
 
 def _one_block(mix_slicqt: Tensor, slicqtgrams: Tensor):
@@ -123,16 +168,23 @@ def blockwise_phasemix_sep(X_block: Tensor, Ymag_block: Tensor) -> Tensor:
 
 
 def blockwise_wiener(mix_slicqt: Tensor, slicqtgrams: Tensor, wiener_win_len_param: int = 5000, niter: int = 1,
-                     method: str = "auto") -> Tensor:
+                     method: str = "auto", softmask: bool = False, residual: bool = False) -> Tensor:
     """phase.py:18-69.  (B,2,F,S,T,2), (4,B,2,F,S,T) -> (4,B,2,F,S,T,2).  ``niter`` (extension; the reference pins 1): the
-    iteration count of norbert.wiener, 0 = the mix-phase estimate; ``method``: "auto", "looped" or "resident" for
-    ``niter`` >= 2 (``wiener_em_arena``)."""
+    iteration count of norbert.wiener, 0 = the initial estimate; ``method``: "auto", "looped" or "resident" for
+    ``niter`` >= 2 (``wiener_em_arena``).  ``softmask`` (extension): norbert.wiener's use_softmask; ``residual`` (extension):
+    the magnitudes first go through norbert.contrib.residual_model(v, x, 1) and the result is (5,B,2,F,S,T,2), residual last."""
     table, B, S = _one_block(mix_slicqt, slicqtgrams)
     X = mix_slicqt.contiguous().float()
-    Y = blockwise_phasemix_sep(X, slicqtgrams)
     nb_frames = S * mix_slicqt.shape[4]
     win = int(wiener_win_len_param) if wiener_win_len_param else nb_frames
-    wiener_em_arena(table, X.view(-1), Y.view(-1), B, S, win, niter=niter, method=method)
+    if softmask or residual:
+        mag = slicqtgrams.contiguous().float()
+        with torch.cuda.device(X.device):
+            Y = torch.empty(nb_sources(residual), *mag.shape[1:], 2, dtype=torch.float32, device=X.device)
+        wiener_start_arena(table, X.view(-1), mag.view(-1), Y.view(-1), B, S, softmask=softmask, residual=residual)
+    else:
+        Y = blockwise_phasemix_sep(X, slicqtgrams)
+    wiener_em_arena(table, X.view(-1), Y.view(-1), B, S, win, niter=niter, method=method, residual=residual)
     return Y
 
 
@@ -141,9 +193,10 @@ def abs_of_real_complex(Xcomplex_real_view: Tensor) -> Tensor:
     return torch.sqrt(Xcomplex_real_view[..., 0] ** 2 + Xcomplex_real_view[..., 1] ** 2)
 
 
-def wiener(mix_slicqt: List[Tensor], slicqtgrams: List[Tensor], wiener_win_len: int = 5000, niter: int = 1, method: str = "auto"):
+def wiener(mix_slicqt: List[Tensor], slicqtgrams: List[Tensor], wiener_win_len: int = 5000, niter: int = 1, method: str = "auto",
+           softmask: bool = False, residual: bool = False):
     """phase.py:7-15."""
-    return [blockwise_wiener(m, s, wiener_win_len, niter, method) for m, s in zip(mix_slicqt, slicqtgrams)]
+    return [blockwise_wiener(m, s, wiener_win_len, niter, method, softmask, residual) for m, s in zip(mix_slicqt, slicqtgrams)]
 
 
 def phasemix_sep(X: List[Tensor], Ymag: List[Tensor]):

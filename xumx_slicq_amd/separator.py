@@ -35,8 +35,10 @@ class Separator(nn.Module):
     @classmethod
     def load(cls, chunk_size: int = 2621440, model_path: Optional[str] = None,
              runtime_backend: Optional[str] = _ACCELERATED, warmup: int = 0, realtime: bool = False,
-             device: Union[str, torch.device] = "cuda", niter: Optional[int] = None):
-        """separator.py:50-93.  ``niter`` (extension): EM iterations of the Wiener post-filter, see ``Separator.niter``."""
+             device: Union[str, torch.device] = "cuda", niter: Optional[int] = None, softmask: Optional[bool] = None,
+             residual: Optional[bool] = None):
+        """separator.py:50-93.  ``niter``, ``softmask``, ``residual`` (extensions): the options of the Wiener post-filter, see the
+        properties of the same names."""
         if runtime_backend not in _SUPPORTED_RUNTIMES:
             raise ValueError(f"requested runtime backend {runtime_backend} not in {_SUPPORTED_RUNTIMES}")
         xumx_model, encoder, sample_rate = load_target_models(
@@ -46,6 +48,10 @@ class Separator(nn.Module):
         separator.freeze()
         if niter is not None:
             separator.niter = niter
+        if softmask is not None:
+            separator.softmask = softmask
+        if residual is not None:
+            separator.residual = residual
         for _ in range(warmup):
             waveform = torch.rand((1, 2, int(100 * sample_rate)), dtype=torch.float32, device=device)
             separator.forward(waveform)
@@ -88,6 +94,36 @@ class Separator(nn.Module):
             raise ValueError(f"niter must be >= 0 (got {value})")
         self.xumx_model.niter = value
 
+    @property
+    def softmask(self) -> bool:
+        """Start the Wiener post-filter of an offline model from the ratio mask x v_j / (eps + sum_j v_j) instead of the mixture
+        phase on v_j: ``use_softmask`` of norbert.wiener, ``softmask`` of the Open-Unmix family (the reference pins False).  Lives on
+        the model (``Unmix.softmask``), read per call; with ``niter`` = 0 that start is the result."""
+        return bool(getattr(self.xumx_model, "softmask", False))
+
+    @softmask.setter
+    def softmask(self, value: bool):
+        self.xumx_model.softmask = bool(value)
+
+    @property
+    def residual(self) -> bool:
+        """Add a fifth source to the Wiener post-filter of an offline model, relu(|x| - sum_j v_j): what the four target models
+        do not explain (norbert.contrib.residual_model, ``residual`` of the Open-Unmix family).  ``forward``, ``forward_graphed``
+        and ``forward_overlapped`` then return (5, nb_samples, 2, N), the residual last.  Lives on the model (``Unmix.residual``)."""
+        return bool(getattr(self.xumx_model, "residual", False))
+
+    @residual.setter
+    def residual(self, value: bool):
+        self.xumx_model.residual = bool(value)
+
+    def _nb_sources(self) -> int:
+        return 5 if self.residual else 4
+
+    def _handle_key(self):
+        """What the workspace sizes of a native call depend on besides its shape: the packed-parameter version of the model handle
+        and the option set stored on it."""
+        return (self.xumx_model._version(), self.softmask, self.residual)
+
     def _graph_key(self, audio_big: Tensor):
         """Everything a captured forward depends on besides the input values: shape and device, the chunking
         switches, the packed-parameter version of the model (captured kernels hold raw pointers into the
@@ -100,7 +136,7 @@ class Separator(nn.Module):
                 bool(getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0")),
                 bool(getattr(m, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")), self._packed_fft(),
                 bool(getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0")), int(getattr(self, "max_item_slices", 0)),
-                int(getattr(m, "winograd", 7)), self.niter, getattr(m, "niter_method", "auto"))
+                int(getattr(m, "winograd", 7)), self.niter, getattr(m, "niter_method", "auto"), self.softmask, self.residual)
 
     def drop_graphs(self):
         """Forget every captured forward (they hold raw pointers into the model handle and the workspaces)."""
@@ -237,10 +273,14 @@ class Separator(nn.Module):
     def demix_into(self, audio, out: Tensor, row_offsets: Tensor, group: int = 1):
         """One pass over ``audio`` (k * group, 2, n): k independent work items of n <= chunk_size samples each
         (chunks of any tracks -- no state crosses the reference's chunk loop, separator.py:153-229), ``group``
-        = nb_samples of an item; or a LIST of k tensors (group, 2, n), read in place.  The stems of packed channel
+        = nb_samples of an item; or a LIST of k tensors (group, 2, n), read in place.  Four stems per item: ``residual`` is
+        refused (ValueError).  The stems of packed channel
         (target, item*group + b, c) land at out.view(-1)[row_offsets[target, item*group + b, c] : + n] -- the hard concat
         of separator.py:231 by placement.  The Wiener window maximum keeps its per-item scope (quirk A13) through
         ``group``.  Building block of ``sharding.ShardedDemixer``; ``forward`` is the single-track case."""
+        if self.residual:
+            raise ValueError("demix_into places four stems per work item (row_offsets (4, B, 2)); residual = True writes five: "
+                             "use forward, or switch residual off for the multi-track batch")
         x_rows, keep = None, None
         if isinstance(audio, (list, tuple)):
             keep = list(audio)
@@ -272,7 +312,7 @@ class Separator(nn.Module):
                 d = self.nsgt.nsgt.nsgt.demixer(dev)
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 n_pad = max(n, min_samples)
-                key = ("pass", B, n_pad, wiener, self.xumx_model._version(), dev.index)
+                key = ("pass", B, n_pad, wiener, self._handle_key(), dev.index)
                 nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
                 if nbytes is None:
                     nbytes = _lib.lib.xsq_demix_pass_workspace(d, model, B, n_pad, wiener)
@@ -296,7 +336,9 @@ class Separator(nn.Module):
     def _native_mode(self, audio: Tensor):
         """None when this call has to take the Python chunk loop (an A/B switch is off its default, a mixed or
         non-stereo model), else the post-filter of the native call: 0 mix-phase, k >= 1 Wiener-EM of k iterations
-        (``niter``; 0 on an offline model is mix-phase)."""
+        (``niter``; 0 on an offline model is mix-phase).  Every entry point comes through here: a realtime model asked for
+        ``softmask`` or ``residual`` is refused (``XsqError`` naming the option)."""
+        self.xumx_model.wiener_options()
         if not getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0"):
             return None
         if audio.dim() != 3 or audio.shape[1] != 2 or audio.device.type != "cuda" or audio.shape[-1] < 1:
@@ -351,7 +393,7 @@ class Separator(nn.Module):
             side = self._tail_stream(dev) if overlap else main
             cs = int(min(self.chunk_size, 1 << 62))
             max_stack = int(getattr(self, "max_stack", 8))
-            key = (nb, N, cs, max_stack, wiener, self.xumx_model._version(), dev.index, int(getattr(self, "max_item_slices", 0)))
+            key = (nb, N, cs, max_stack, wiener, self._handle_key(), dev.index, int(getattr(self, "max_item_slices", 0)))
             # the cap is sticky state of the native demixer and part of its plan key: set it on EVERY call, not only on a
             # cache miss here -- after 0 -> 20 -> 0 a cached shape would otherwise run under the stale cap
             _lib.check(_lib.lib.xsq_demixer_set_max_rows(d, int(getattr(self, "max_item_slices", 0))), "xsq_demixer_set_max_rows")
@@ -372,7 +414,7 @@ class Separator(nn.Module):
                                                         side.cuda_stream if two else main.cuda_stream, gains.data_ptr(),
                                                         int(gains.shape[0])), "xsq_separator_remix")
                 return out
-            out = torch.empty(4, nb, 2, N, dtype=torch.float32, device=dev)
+            out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=dev)
             fn, src = ((_lib.lib.xsq_separator_forward, audio_big.data_ptr()) if slot is None
                        else (_lib.lib.xsq_separator_forward_indirect, slot.data_ptr()))
             _lib.check(fn(d, model, src, nb, N, cs, max_stack, wiener, 1 if two else 0, out.data_ptr(),
@@ -382,8 +424,8 @@ class Separator(nn.Module):
 
     @torch.no_grad()
     def forward(self, audio_big: Tensor) -> Tensor:
-        """(nb_samples, 2, N) fp32 on a ROCm device -> (4, nb_samples, 2, N).  separator.py:133-232:
-        chunks of chunk_size samples, short chunks zero-padded to sllen/2+1, hard concat.
+        """(nb_samples, 2, N) fp32 on a ROCm device -> (4, nb_samples, 2, N); (5, ...) with ``residual``, the residual last.
+        separator.py:133-232: chunks of chunk_size samples, short chunks zero-padded to sllen/2+1, hard concat.
 
         The reference walks the chunks one by one; no state crosses the loop, so here all FULL
         chunks of the call are stacked along the batch axis and run as one pass (the Wiener
@@ -400,9 +442,10 @@ class Separator(nn.Module):
         self._packed_fft()
         # every chunk's stems are written straight into their place of the result (the hard concat
         # of separator.py:231 without a copy): packed channel (target, [chunk,] b, c) -> out row
-        out = torch.empty(4, nb, 2, N, dtype=torch.float32, device=dev)
-        rows = (torch.arange(4, device=dev).view(4, 1, 1, 1) * nb + torch.arange(nb, device=dev).view(1, 1, nb, 1)) * 2 \
-            + torch.arange(2, device=dev).view(1, 1, 1, 2)                       # (4, 1, nb, 2) row of `out`
+        J = self._nb_sources()
+        out = torch.empty(J, nb, 2, N, dtype=torch.float32, device=dev)
+        rows = (torch.arange(J, device=dev).view(J, 1, 1, 1) * nb + torch.arange(nb, device=dev).view(1, 1, nb, 1)) * 2 \
+            + torch.arange(2, device=dev).view(1, 1, 1, 2)                       # (J, 1, nb, 2) row of `out`
 
         def decode(audio, length, offsets, group=0):
             Xc, ready = self._encode(audio)
@@ -455,7 +498,7 @@ class Separator(nn.Module):
                 used.append(st)
             with torch.cuda.stream(st):
                 a = audio_big[..., s0:s0 + k * cs].reshape(nb, 2, k, cs).permute(2, 0, 1, 3).reshape(k * nb, 2, cs)
-                offs = rows * N + s0 + torch.arange(k, device=dev).view(1, k, 1, 1) * cs   # (4, k, nb, 2)
+                offs = rows * N + s0 + torch.arange(k, device=dev).view(1, k, 1, 1) * cs   # (J, k, nb, 2)
                 decode(a, cs, offs, group=nb)                                    # batch = (chunk, b)
         for st in used:
             main.wait_stream(st)
@@ -472,8 +515,12 @@ class Separator(nn.Module):
         such dicts).  The inverse transform is linear, so the native path runs R inverse transforms per chunk instead of
         four plus a sum (xsq_separator_remix); a target no row weights is never read.  When this call takes the Python
         chunk loop (``_native_mode`` is None: an A/B switch off its default, a mixed model) the result is computed by
-        definition, ``einsum("rt,tbcn->rbcn", G, forward(audio))``."""
+        definition, ``einsum("rt,tbcn->rbcn", G, forward(audio))``.  ``softmask`` is honoured; ``residual`` is refused
+        (ValueError): a gain row has four columns and the residual is no target."""
         G = remix_gains(gains)
+        if self.residual:
+            raise ValueError("remix weights the four targets; residual = True adds a fifth stem that no gain column names: "
+                             "switch residual off, or mix the five stems of forward yourself")
         if not isinstance(audio_big, Tensor) or audio_big.device.type != "cuda":
             raise ValueError("remix needs the audio on a ROCm device (as forward)")
         wiener = self._native_mode(audio_big)
@@ -492,7 +539,7 @@ class Separator(nn.Module):
 
     @torch.no_grad()
     def forward_overlapped(self, audio_big: Tensor, segment: float = 10.0, overlap: float = 0.1) -> Tensor:
-        """(nb_samples, 2, N) fp32 on a ROCm device -> (4, nb_samples, 2, N): ``forward`` over segments that overlap and are
+        """(nb_samples, 2, N) fp32 on a ROCm device -> (4, nb_samples, 2, N) ((5, ...) with ``residual``): ``forward`` over segments that overlap and are
         cross-faded, ``separate_sources`` of the reference's Cadenza caller (cadenza/enhance.py:35-99) instead of the hard
         concat of separator.py:231.  ``segment`` seconds per hop, ``overlap`` in [0, 1) of a second: with
         chunk_len = int(sr * segment * (1 + overlap)) and ov = int(overlap * sr), segment k starts at k * chunk_len - ov
@@ -525,7 +572,7 @@ class Separator(nn.Module):
             cs = int(min(self.chunk_size, 1 << 62))
             max_stack = int(getattr(self, "max_stack", 8))
             cap = int(getattr(self, "max_item_slices", 0))
-            key = ("segments", nb, N, cs, chunk_len, ov, max_stack, wiener, self.xumx_model._version(), dev.index, cap)
+            key = ("segments", nb, N, cs, chunk_len, ov, max_stack, wiener, self._handle_key(), dev.index, cap)
             _lib.check(_lib.lib.xsq_demixer_set_max_rows(d, cap), "xsq_demixer_set_max_rows")      # (sticky, part of the plan key)
             nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
             if nbytes is None:
@@ -534,7 +581,7 @@ class Separator(nn.Module):
                            "xsq_separator_segments_workspace")
                 nbytes = self._nsizes[key] = b.value
             ws = self._native_ws(dev, main.cuda_stream, "main", nbytes)
-            out = torch.empty(4, nb, 2, N, dtype=torch.float32, device=dev)
+            out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=dev)
             _lib.check(_lib.lib.xsq_separator_forward_segments(d, model, audio_big.data_ptr(), nb, N, cs, chunk_len, ov, max_stack, wiener,
                                                                out.data_ptr(), ws.data_ptr(), ws.numel(), main.cuda_stream),
                        "xsq_separator_forward_segments")
@@ -550,8 +597,10 @@ class Separator(nn.Module):
 
     @staticmethod
     def to_dict(estimates: Tensor, aggregate_dict: Optional[dict] = None) -> dict:
-        """separator.py:234-259."""
+        """separator.py:234-259.  Five estimates (``residual``) add the key "residual"."""
         estimates_dict = {target: estimates[k] for k, target in enumerate(Separator.sources)}
+        if len(estimates) == 5:
+            estimates_dict["residual"] = estimates[4]
         if aggregate_dict is not None:
             new_estimates = {}
             for key in aggregate_dict:
@@ -712,7 +761,8 @@ def load_target_models(model_path: str, runtime_backend: str = _ACCELERATED, rea
 
 
 def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed: int = 1234,
-                     device="cuda", chunk_size: int = 2621440, niter: Optional[int] = None, **cfg) -> Separator:
+                     device="cuda", chunk_size: int = 2621440, niter: Optional[int] = None, softmask: Optional[bool] = None,
+                     residual: Optional[bool] = None, **cfg) -> Separator:
     """Separator with the seeded synthetic weights (no checkpoint exists offline).
     ``wiener`` overrides the post-filter: None follows the reference (offline -> Wiener-EM,
     realtime -> mix-phase); False on the offline stack is BASELINE config 2."""
@@ -726,4 +776,8 @@ def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed
     sep.freeze()
     if niter is not None:
         sep.niter = niter
+    if softmask is not None:
+        sep.softmask = softmask
+    if residual is not None:
+        sep.residual = residual
     return sep

@@ -65,6 +65,10 @@ class Trainer:
         if len(causal) != 1 or len(wiener) != 1:
             raise _lib.XsqError("all blocks must share the same first-layer type and post-filter")
         self.causal, self.wiener = causal.pop(), wiener.pop()
+        for opt in ("softmask", "residual"):
+            if bool(getattr(unmix, opt, False)):
+                raise _lib.XsqError(f"the training step differentiates the reference's filter (mix-phase start, four sources); this model "
+                                    f"has {opt} = True: set it to False for training")
         if self.wiener and int(getattr(unmix, "niter", 1)) != 1:
             raise _lib.XsqError(f"training differentiates ONE Wiener-EM iteration (the reference trains with iterations=1, and the "
                                 f"backward kernels are the gradient of one); this model has niter = {unmix.niter}: set it to 1 "
