@@ -1,4 +1,4 @@
-"""The table / judge helper of the float64 parity tests (tests/test_ref64_gpu.py, tests/test_ref64_train_gpu.py, tests/test_ref64_stress_gpu.py).
+"""The table / judge helper of the float64 parity tests (tests/test_ref64_gpu.py, tests/test_ref64_mel_gpu.py, tests/test_ref64_train_gpu.py, tests/test_ref64_stress_gpu.py).
 
 TEST INFRASTRUCTURE (see oracle/__init__.py).  One rule for every stage:  e_gpu <= M * E,  e_gpu the kernels' error against
 oracle/ref64.py, E the LARGEST error of the fp32 CPU oracle over the members of the stage on the same input, both by
