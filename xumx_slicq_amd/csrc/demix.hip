@@ -22,10 +22,12 @@ namespace {
 // what the 32-bit float offsets of the band kernels allow for the 8-channel estimate arena of one pass:
 // 2 * (8 B) * S * sumFT < 2^31 (slicqt.hip: inverse_impl) -> B * S <= 7168 for the Bark-262 plan (sumFT = 18640)
 // (J sources: 2J channels per sample; 4 without the residual of xsq_model_set_wiener_options)
-static int default_max_item_slices(const xsq_plan* P, int J = 4) {
-    const int64_t lim = ((1ll << 31) - 1) / (4 * J * std::max<int64_t>(P->sumFT, P->nbins));
+// (coefs complex coefficients per channel-slice, floor = the L / 2 + 1 spectrum bins of a slice)
+static int default_max_item_slices(int64_t coefs, int64_t floor, int J = 4) {
+    const int64_t lim = ((1ll << 31) - 1) / (4 * J * std::max<int64_t>(coefs, floor));
     return (int)std::min<int64_t>(lim, 65535 / (2 * J));    // and BC * S <= 65535 rows per launch
 }
+static int default_max_item_slices(const xsq_plan* P, int J = 4) { return default_max_item_slices(P->sumFT, P->nbins, J); }
 
 static inline int sources_of(const xsq_model* Mo) { return (Mo->wiener_flags & XSQ_WIENER_RESIDUAL) ? 5 : 4; }
 
@@ -38,8 +40,8 @@ struct PassPlan {
     // the head of the workspace, -1 = none; set_first / set_count: the passes of the set (consecutive)
     int64_t ext_off = -1;
     int set_first = 0, set_count = 1;
-    int64_t* d_xrows = nullptr;      // [2B] input row offsets
-    int64_t* d_orows = nullptr;      // [2JB] output row offsets (J = 4 sources, 5 with the residual)
+    const int64_t* d_xrows = nullptr;      // [2B] input row offsets (null: rows one after the other)
+    const int64_t* d_orows = nullptr;      // [2JB] output row offsets (J = 4 sources, 5 with the residual)
     // a pass of overlapped segments (xsq_separator_forward_segments): d_orows point into the scratch arena and one
     // xsq_crossfade_place launch blends the seg_k segments at seg_start + j * seg_stride into the result
     int64_t seg_start = 0, seg_stride = 0;
@@ -128,10 +130,15 @@ static int run_remix(xsq_plan* P, const float* masks, const float* X, const floa
     return XSQ_OK;
 }
 
-static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* const* x_slot, const int64_t* x_rows, int B, int64_t n, int64_t n_pad,
-                    int group, int wiener, float* out, const int64_t* out_rows, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const float* ext_max = nullptr, const float* gains = nullptr, int R = 0) {
+// The input of a call: the audio itself, or a device slot that holds its address (xsq_separator_forward_indirect).
+struct PassInput { const float* x; const float* const* x_slot; };
+
+// One pass: of `p` this reads d_xrows / d_orows, B, n, n_pad and group.
+static int run_pass(xsq_demixer* d, xsq_model* Mo, PassInput in, const PassPlan& p, int wiener, float* out, void* ws, size_t ws_bytes,
+                    hipStream_t stream, const float* ext_max = nullptr, const float* gains = nullptr, int R = 0) {
     xsq_plan* P = d->plan;
+    const int64_t n = p.n, n_pad = p.n_pad;
+    const int B = p.B, group = p.group;
     PassLayout L;
     int rc = pass_layout(d, Mo, B, n_pad, wiener, &L);
     if (rc) return rc;
@@ -149,7 +156,7 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
     if ((rc = xsq_model_whitening(Mo, &mean, &scale, &split))) return rc;
     // the analysis kernels write the whitened magnitude into the head of the CDAE workspace (xsq_cdae_forward_xin, xin_ready)
     float* xin = (float*)(w + L.cdae);
-    if ((rc = xsq_slicqt_forward_rows_indirect(P, x, x_slot, x_rows, 2 * B, n, n_pad, X, xin, mean, scale, split, w + L.fwd, L.fwd_bytes, stream)))
+    if ((rc = xsq_slicqt_forward_rows_indirect(P, in.x, in.x_slot, p.d_xrows, 2 * B, n, n_pad, X, xin, mean, scale, split, w + L.fwd, L.fwd_bytes, stream)))
         return rc;
     if ((rc = xsq_cdae_forward_xin(Mo, X, B, S, nullptr, masks, w + L.cdae, L.cdae_bytes, stream, 1))) return rc;
     const int flags = Mo->wiener_flags, J = sources_of(Mo);
@@ -159,11 +166,11 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
         if ((rc = xsq_wiener_em_masked_options(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max, wiener, 0, flags,
                                                w + L.wien, L.wien_bytes, stream)))
             return rc;
-        if (!gains) return xsq_slicqt_inverse_rows(P, Y, 2 * J * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
-        return run_remix(P, nullptr, nullptr, Y, gains, R, B, S, n, out, out_rows, w + L.inv, L.total - L.inv, stream);
+        if (!gains) return xsq_slicqt_inverse_rows(P, Y, 2 * J * B, S, n, out, p.d_orows, w + L.inv, L.inv_bytes, stream);
+        return run_remix(P, nullptr, nullptr, Y, gains, R, B, S, n, out, p.d_orows, w + L.inv, L.total - L.inv, stream);
     }
     if (!wiener && !gains)
-        return xsq_slicqt_inverse_masked(P, masks, X, 8 * B, 2 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
+        return xsq_slicqt_inverse_masked(P, masks, X, 8 * B, 2 * B, S, n, out, p.d_orows, w + L.inv, L.inv_bytes, stream);
     // `wiener` counts the EM iterations: one runs the three launches it always ran, more take the form xsq_wiener_em_masked_iter
     // chooses (the window-resident kernel: 5000 frames fit)
     if (wiener == 1 && (rc = xsq_wiener_em_masked_ext(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
@@ -172,14 +179,13 @@ static int run_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* 
     if (wiener >= 2 && (rc = xsq_wiener_em_masked_iter(P->nblocks, d->F.data(), d->T.data(), X, masks, Y, B, S, 5000, group, ext_max,
                                                        wiener, 0, w + L.wien, L.wien_bytes, stream)))
         return rc;
-    if (!gains) return xsq_slicqt_inverse_rows(P, Y, 8 * B, S, n, out, out_rows, w + L.inv, L.inv_bytes, stream);
-    return run_remix(P, wiener ? nullptr : masks, wiener ? nullptr : X, wiener ? Y : nullptr, gains, R, B, S, n, out, out_rows,
+    if (!gains) return xsq_slicqt_inverse_rows(P, Y, 8 * B, S, n, out, p.d_orows, w + L.inv, L.inv_bytes, stream);
+    return run_remix(P, wiener ? nullptr : masks, wiener ? nullptr : X, wiener ? Y : nullptr, gains, R, B, S, n, out, p.d_orows,
                      w + L.inv, L.total - L.inv, stream);
 }
 
 // One pass of a split batch, first half: its mix transform and the window maxima of its samples folded into the set's table.
-static int run_prepass(xsq_demixer* d, xsq_model* Mo, const float* x, const float* const* x_slot, const PassPlan& p, void* ws, size_t ws_bytes, float* ext,
-                       hipStream_t stream) {
+static int run_prepass(xsq_demixer* d, xsq_model* Mo, PassInput in, const PassPlan& p, void* ws, size_t ws_bytes, float* ext, hipStream_t stream) {
     xsq_plan* P = d->plan;
     PassLayout L;
     int rc = pass_layout(d, Mo, p.B, p.n_pad, 1, &L);
@@ -188,7 +194,7 @@ static int run_prepass(xsq_demixer* d, xsq_model* Mo, const float* x, const floa
     const int S = xsq_plan_num_slices(P, p.n_pad);
     char* w = (char*)ws;
     float* X = (float*)(w + L.X);
-    if ((rc = xsq_slicqt_forward_rows_indirect(P, x, x_slot, p.d_xrows, 2 * p.B, p.n, p.n_pad, X, nullptr, nullptr, nullptr, 0, w + L.fwd, L.fwd_bytes,
+    if ((rc = xsq_slicqt_forward_rows_indirect(P, in.x, in.x_slot, p.d_xrows, 2 * p.B, p.n, p.n_pad, X, nullptr, nullptr, nullptr, 0, w + L.fwd, L.fwd_bytes,
                                                stream)))
         return rc;
     return xsq_wiener_window_max(P->nblocks, d->F.data(), d->T.data(), X, p.B, S, 5000, p.group, ext + p.ext_off, stream);
@@ -206,7 +212,7 @@ struct SchedPass {
     int needs_ext;           // 1: the set shares a window-maximum table (Wiener-EM, set_count > 1)
 };
 
-static inline int slices_of(int64_t n, int h) { return (int)(((n + h - 1) / h + 1) / 2 + 1); }      // nsgt/slicing.py:47-72
+static inline int64_t slices_of(int64_t n, int h) { return ((n + h - 1) / h + 1) / 2 + 1; }      // nsgt/slicing.py:47-72 (64 bits: chunk_size may be "none")
 
 static void build_schedule(int L, int nb, int64_t N, int64_t cs, int max_stack, int wiener, int cap, std::vector<SchedPass>* out) {
     const int h = L / 4;
@@ -218,7 +224,7 @@ static void build_schedule(int L, int nb, int64_t N, int64_t cs, int max_stack, 
         }
     };
     const int64_t full = N / cs;
-    const int S_full = slices_of(std::max(cs, min_samples), h);
+    const int S_full = (int)slices_of(std::max(cs, min_samples), h);
     // samples per pass: the whole batch when one chunk of it fits a launch, else the largest share that does
     const int nbb_max = std::max(1, std::min(nb, cap / std::max(1, S_full)));
     const int per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(max_stack / std::max(1, nbb_max), cap / ((int64_t)nbb_max * S_full)));
@@ -233,7 +239,7 @@ static void build_schedule(int L, int nb, int64_t N, int64_t cs, int max_stack, 
     const bool stacked = !out->empty();
     for (; start < N; start += cs) {
         const int64_t n = std::min(cs, N - start);
-        const int S_n = slices_of(std::max(n, min_samples), h);      // the sample split of a short chunk follows its own slice count
+        const int S_n = (int)slices_of(std::max(n, min_samples), h);     // the sample split of a short chunk follows its own slice count
         const int nbb_n = std::max(1, std::min(nb, cap / std::max(1, S_n)));
         const size_t first = out->size();
         for (int b0 = 0; b0 < nb; b0 += nbb_n) out->push_back(SchedPass{start, n, 1, b0, std::min(nbb_n, nb - b0), stacked ? 1 : 0, 0, 1, 0});
@@ -263,60 +269,45 @@ static int evict_for_new_plan(xsq_demixer* d) {
     return XSQ_OK;
 }
 
-static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<int64_t>& key, ForwardPlan& fp,
-                        const std::vector<std::vector<int64_t>>& xr, const std::vector<std::vector<int64_t>>& orw, int wiener,
-                        ForwardPlan** out);
-
-// The schedule with its device tables and workspace sizes.
-static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
-                            ForwardPlan** out) {
-    xsq_plan* P = d->plan;
-    const int J = sources_of(Mo);
-    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal | ((int64_t)Mo->wiener_flags << 8)};
-    auto it = d->plans.find(key);
-    if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
-    if (int rc = evict_for_new_plan(d)) return rc;
-    const int64_t min_samples = P->L / 2 + 1;                      // separator.py:162
-    const int cap = d->max_item_slices > 0 ? std::min(d->max_item_slices, default_max_item_slices(P, J)) : default_max_item_slices(P, J);
+// A plan while it is built: the passes, their row tables still on the host.
+struct PlanBuild {
     ForwardPlan fp;
-    std::vector<SchedPass> sched;
-    build_schedule(P->L, nb, N, cs, max_stack, wiener ? 1 : 0, cap, &sched);
-    std::vector<std::vector<int64_t>> xr, orw;
-    for (const SchedPass& sp : sched) {
-        PassPlan p;
-        p.n = sp.n; p.n_pad = std::max(sp.n, min_samples); p.B = sp.k * sp.nbb; p.group = sp.nbb; p.tail = sp.tail;
-        p.set_first = sp.set_first; p.set_count = sp.set_count;
-        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)2 * J * p.B);
-        for (int j2 = 0; j2 < sp.k; ++j2)
-            for (int b = 0; b < sp.nbb; ++b)
-                for (int c = 0; c < 2; ++c) {
-                    const int item = j2 * sp.nbb + b;
-                    xrow[(size_t)item * 2 + c] = ((int64_t)(sp.b0 + b) * 2 + c) * N + sp.start + j2 * cs;
-                    for (int t = 0; t < J; ++t)
-                        orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * nb + sp.b0 + b) * 2 + c) * N + sp.start + j2 * cs;
-                }
-        xr.push_back(xrow); orw.push_back(orow);
+    std::vector<int64_t> rows;          // the row tables of the passes, one after the other
+    // One more pass (B, group, n, ... set by the caller), its items (stacked chunk or segment j, sample b) = j * group + b:
+    // channel c of an item is read at row x_of(item, c), source t of it is written at row o_of(t, item, c).
+    template <class XOf, class OOf> void add_pass(const PassPlan& p, int J, XOf x_of, OOf o_of) {
+        const size_t x0 = rows.size(), o0 = x0 + (size_t)2 * p.B;        // [2B] input rows, then [2JB] output rows
+        rows.resize(o0 + (size_t)2 * J * p.B);
+        for (int item = 0; item < p.B; ++item)
+            for (int c = 0; c < 2; ++c) {
+                rows[x0 + (size_t)item * 2 + c] = x_of(item, c);
+                for (int t = 0; t < J; ++t) rows[o0 + ((size_t)t * p.B + item) * 2 + c] = o_of(t, item, c);
+            }
         fp.passes.push_back(p);
     }
-    // the window-maximum tables of the split sets (one per set, shared by its passes)
-    for (size_t i = 0; i < sched.size(); ++i) {
-        if (!sched[i].needs_ext) continue;
-        if ((int)i == sched[i].set_first) {
-            const int64_t off = (int64_t)fp.ext_floats;
-            fp.ext_floats += (size_t)xsq_wiener_num_windows(P->nblocks, d->F.data(), d->T.data(), sched[i].k,
-                                                            xsq_plan_num_slices(P, fp.passes[i].n_pad), 5000, 1);
-            for (int q = 0; q < sched[i].set_count; ++q) fp.passes[i + q].ext_off = off;
-        }
-    }
-    return publish_plan(d, Mo, key, fp, xr, orw, wiener, out);
+};
+
+// The plan of a known call shape, stamped as used now.
+static bool cached_plan(xsq_demixer* d, const std::vector<int64_t>& key, ForwardPlan** out) {
+    auto it = d->plans.find(key);
+    if (it == d->plans.end()) return false;
+    it->second.last_use = ++d->clock;
+    *out = &it->second;
+    return true;
 }
 
-// Device tables and workspace sizes of a new plan; the plan enters the cache once its tables are on the device.
-static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<int64_t>& key, ForwardPlan& fp,
-                        const std::vector<std::vector<int64_t>>& xr, const std::vector<std::vector<int64_t>>& orw, int wiener,
-                        ForwardPlan** out) {
-    size_t total = 0;
-    for (size_t i = 0; i < fp.passes.size(); ++i) total += xr[i].size() + orw[i].size();
+// item-slices per pass: the caller's cap (xsq_demixer_set_max_rows) inside what the offsets allow for J sources
+static int item_cap(const xsq_demixer* d, int J) {
+    const int hard = default_max_item_slices(d->plan, J);
+    return d->max_item_slices > 0 ? std::min(d->max_item_slices, hard) : hard;
+}
+
+// Device tables and workspace sizes of a new plan, after room was made for it (a known shape never comes here, so a cache hit
+// never evicts); the plan enters the cache once its tables are on the device.
+static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<int64_t>& key, PlanBuild& pb, int wiener, ForwardPlan** out) {
+    if (int rc = evict_for_new_plan(d)) return rc;
+    ForwardPlan& fp = pb.fp;
+    const size_t total = pb.rows.size(), J = sources_of(Mo);
     XSQ_HIP(hipMalloc(&fp.d_tables, std::max<size_t>(total, 1) * sizeof(int64_t)));
     if (hipHostMalloc(&fp.h_tables, std::max<size_t>(total, 1) * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) {
         (void)hipFree(fp.d_tables);
@@ -324,15 +315,13 @@ static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<i
         return XSQ_ERR_HIP;
     }
     fp.table_words = total;
-    int64_t* host = fp.h_tables;
+    std::copy(pb.rows.begin(), pb.rows.end(), fp.h_tables);
     size_t o = 0;
-    for (size_t i = 0; i < fp.passes.size(); ++i) {
-        PassPlan& p = fp.passes[i];
-        p.d_xrows = fp.d_tables + o; std::copy(xr[i].begin(), xr[i].end(), host + o); o += xr[i].size();
-        p.d_orows = fp.d_tables + o; std::copy(orw[i].begin(), orw[i].end(), host + o); o += orw[i].size();
+    for (PassPlan& p : fp.passes) {
+        p.d_xrows = fp.d_tables + o; o += (size_t)2 * p.B;
+        p.d_orows = fp.d_tables + o; o += 2 * J * p.B;
         PassLayout L;
-        int rc = pass_layout(d, Mo, p.B, p.n_pad, wiener, &L);
-        if (rc) { (void)hipFree(fp.d_tables); (void)hipHostFree(fp.h_tables); return rc; }
+        if (int rc = pass_layout(d, Mo, p.B, p.n_pad, wiener, &L)) { (void)hipFree(fp.d_tables); (void)hipHostFree(fp.h_tables); return rc; }
         size_t& dst = p.tail ? fp.tail_bytes : fp.main_bytes;
         dst = std::max(dst, L.total);
     }
@@ -353,6 +342,36 @@ static int publish_plan(xsq_demixer* d, const xsq_model* Mo, const std::vector<i
     auto ins = d->plans.emplace(key, fp);
     *out = &ins.first->second;
     return XSQ_OK;
+}
+
+// The schedule with its device tables and workspace sizes.
+static int get_forward_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int max_stack, int wiener, ForwardPlan** out) {
+    xsq_plan* P = d->plan;
+    const int J = sources_of(Mo);
+    const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal | ((int64_t)Mo->wiener_flags << 8)};
+    if (cached_plan(d, key, out)) return XSQ_OK;
+    const int64_t min_samples = P->L / 2 + 1;                      // separator.py:162
+    PlanBuild pb;
+    ForwardPlan& fp = pb.fp;
+    std::vector<SchedPass> sched;
+    build_schedule(P->L, nb, N, cs, max_stack, wiener ? 1 : 0, item_cap(d, J), &sched);
+    for (const SchedPass& sp : sched) {
+        PassPlan p;
+        p.n = sp.n; p.n_pad = std::max(sp.n, min_samples); p.B = sp.k * sp.nbb; p.group = sp.nbb; p.tail = sp.tail;
+        p.set_first = sp.set_first; p.set_count = sp.set_count;
+        // chunk j of the pass, sample b0 + b of the batch: where the chunk lies in the (nb, 2, N) input and the (J, nb, 2, N) result
+        auto at = [&](int64_t lead, int item, int c) { return ((lead + sp.b0 + item % sp.nbb) * 2 + c) * N + sp.start + item / sp.nbb * cs; };
+        pb.add_pass(p, J, [&](int item, int c) { return at(0, item, c); }, [&](int t, int item, int c) { return at((int64_t)t * nb, item, c); });
+    }
+    // the window-maximum tables of the split sets (one per set, shared by its passes)
+    for (size_t i = 0; i < sched.size(); ++i) {
+        if (!sched[i].needs_ext || (int)i != sched[i].set_first) continue;
+        const int64_t off = (int64_t)fp.ext_floats;
+        fp.ext_floats += (size_t)xsq_wiener_num_windows(P->nblocks, d->F.data(), d->T.data(), sched[i].k,
+                                                        xsq_plan_num_slices(P, fp.passes[i].n_pad), 5000, 1);
+        for (int q = 0; q < sched[i].set_count; ++q) fp.passes[i + q].ext_off = off;
+    }
+    return publish_plan(d, Mo, key, pb, wiener, out);
 }
 
 
@@ -376,19 +395,16 @@ static int get_segment_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
     // (nine words: never the seven of an xsq_separator_forward shape)
     const int J = sources_of(Mo);
     const std::vector<int64_t> key{nb, N, cs, max_stack, wiener, d->max_item_slices, Mo->causal | ((int64_t)Mo->wiener_flags << 8), cl, ov};
-    auto it = d->plans.find(key);
-    if (it != d->plans.end()) { it->second.last_use = ++d->clock; *out = &it->second; return XSQ_OK; }
+    if (cached_plan(d, key, out)) return XSQ_OK;
     const int h = P->L / 4;
     const int64_t min_samples = P->L / 2 + 1;
     const int64_t hard = default_max_item_slices(P, J);
-    const int64_t cap = d->max_item_slices > 0 ? std::min<int64_t>(d->max_item_slices, hard) : hard;
     // what bounds a stacked pass of full chunks today: max_stack items of a full chunk's slices, and the cap
-    const int64_t S_full = ((std::max(cs, min_samples) + h - 1) / h + 1) / 2 + 1;
-    const int64_t budget = std::min<int64_t>(cap, (max_stack > hard / S_full) ? hard : max_stack * S_full);
+    const int64_t S_full = slices_of(std::max(cs, min_samples), h);
+    const int64_t budget = std::min<int64_t>(item_cap(d, J), (max_stack > hard / S_full) ? hard : max_stack * S_full);
     std::vector<Segment> segs;
     build_segments(N, cl, ov, &segs);
-    ForwardPlan fp;
-    std::vector<std::vector<int64_t>> xr, orw;
+    PlanBuild pb;
     for (size_t s0 = 0; s0 < segs.size();) {
         const int64_t n = segs[s0].n, n_pad = std::max(n, min_samples);
         const int64_t S = slices_of(n_pad, h);
@@ -401,32 +417,39 @@ static int get_segment_plan(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
         p.seg_k = (int)(s1 - s0); p.seg_start = segs[s0].start; p.seg_stride = cl;
         p.fade_in = segs[s0].fade_in ? 1 : 0; p.fade_out = segs[s1 - 1].fade_out ? 1 : 0;
         p.n = n; p.n_pad = n_pad; p.B = p.seg_k * nb; p.group = nb;
-        std::vector<int64_t> xrow((size_t)2 * p.B), orow((size_t)2 * J * p.B);
-        for (int j = 0; j < p.seg_k; ++j)
-            for (int b = 0; b < nb; ++b)
-                for (int c = 0; c < 2; ++c) {
-                    const int item = j * nb + b;
-                    xrow[(size_t)item * 2 + c] = ((int64_t)b * 2 + c) * N + segs[s0 + j].start;
-                    for (int t = 0; t < J; ++t) orow[((size_t)t * p.B + item) * 2 + c] = (((int64_t)t * p.B + item) * 2 + c) * n;
-                }
-        fp.scratch_bytes = std::max(fp.scratch_bytes, al256((size_t)2 * J * p.B * n * sizeof(float)));
-        xr.push_back(xrow); orw.push_back(orow);
-        fp.passes.push_back(p);
+        // segment j of the pass, sample b: read where it lies in the input, written as (J, B, 2, n) into the scratch arena
+        pb.add_pass(p, J, [&](int item, int c) { return ((int64_t)(item % nb) * 2 + c) * N + segs[s0 + item / nb].start; },
+                    [&](int t, int item, int c) { return (((int64_t)t * p.B + item) * 2 + c) * n; });
+        pb.fp.scratch_bytes = std::max(pb.fp.scratch_bytes, al256((size_t)2 * J * p.B * n * sizeof(float)));
         s0 = s1;
     }
-    if (int rc = evict_for_new_plan(d)) return rc;
-    return publish_plan(d, Mo, key, fp, xr, orw, wiener, out);
+    return publish_plan(d, Mo, key, pb, wiener, out);
+}
+
+static int check_call(const char* who, int nb, int64_t N, int64_t cs, int max_stack, int wiener) {
+    XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "%s: nb=%d N=%lld chunk_size=%lld max_stack=%d", who, nb, (long long)N, (long long)cs, max_stack);
+    XSQ_REQUIRE(wiener >= 0, "%s: wiener=%d iterations", who, wiener);
+    return XSQ_OK;
 }
 
 static int check_segments(const char* who, int nb, int64_t N, int64_t cs, int64_t cl, int64_t ov, int max_stack, int wiener) {
-    XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "%s: nb=%d N=%lld chunk_size=%lld max_stack=%d", who, nb, (long long)N, (long long)cs, max_stack);
-    XSQ_REQUIRE(wiener >= 0, "%s: wiener=%d iterations", who, wiener);
+    if (int rc = check_call(who, nb, N, cs, max_stack, wiener)) return rc;
     XSQ_REQUIRE(cl >= 1, "%s: chunk_len=%lld samples per segment (>= 1)", who, (long long)cl);
     XSQ_REQUIRE(ov >= 0, "%s: ov=%lld overlapping samples (>= 0)", who, (long long)ov);
     XSQ_REQUIRE(ov < cl, "%s: ov=%lld >= chunk_len=%lld: segments two apart would overlap", who, (long long)ov, (long long)cl);
     XSQ_REQUIRE(cl <= cs && ov <= cs - cl, "%s: a segment of chunk_len + ov = %lld + %lld samples is longer than chunk_size=%lld", who, (long long)cl,
                 (long long)ov, (long long)cs);
     XSQ_REQUIRE(N > ov, "%s: N=%lld samples are not more than ov=%lld: no segment exists", who, (long long)N, (long long)ov);
+    return XSQ_OK;
+}
+
+// The plan `get` finds or makes under the demixer's lock, for a call that launches on `stream`: while that stream is
+// capturing, the plan is pinned (the graph's nodes will hold its tables).
+template <class Get> static int acquire_plan(xsq_demixer* d, hipStream_t stream, Get get, ForwardPlan** fp) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (int rc = get(fp)) return rc;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) (*fp)->pinned = true;
     return XSQ_OK;
 }
 
@@ -466,8 +489,7 @@ int xsq_separator_schedule(int L, int64_t coefs_per_slice, int nb, int64_t N, in
     XSQ_REQUIRE(L > 0 && L % 4 == 0 && coefs_per_slice > 0 && nb > 0 && N > 0 && cs > 0 && max_stack > 0 && (passes || max_passes == 0),
                 "xsq_separator_schedule: bad argument");
     XSQ_REQUIRE(wiener >= 0, "xsq_separator_schedule: wiener=%d iterations", wiener);
-    const int64_t lim = ((1ll << 31) - 1) / (16 * std::max<int64_t>(coefs_per_slice, L / 2 + 1));
-    const int dflt = (int)std::min<int64_t>(lim, 65535 / 8);
+    const int dflt = default_max_item_slices(coefs_per_slice, L / 2 + 1);      // (four sources: the schedule has no model)
     const int cap = max_item_slices > 0 ? std::min(max_item_slices, dflt) : dflt;
     std::vector<SchedPass> sched;
     build_schedule(L, nb, N, cs, max_stack, wiener ? 1 : 0, cap, &sched);
@@ -501,19 +523,18 @@ int xsq_demix_pass(xsq_demixer* d, xsq_model* Mo, const float* x, const int64_t*
     XSQ_REQUIRE(wiener >= 0, "xsq_demix_pass: wiener=%d iterations", wiener);
     XSQ_REQUIRE(!(Mo->wiener_flags & XSQ_WIENER_RESIDUAL), "xsq_demix_pass: out_rows name four stems per item; the residual option "
                 "(xsq_model_set_wiener_options) writes five: use xsq_separator_forward");
-    return run_pass(d, Mo, x, nullptr, x_rows, B, n, n_pad, group, wiener, out, out_rows, ws, ws_bytes, (hipStream_t)stream);
+    PassPlan p;
+    p.n = n; p.n_pad = n_pad; p.B = B; p.group = group; p.d_xrows = x_rows; p.d_orows = out_rows;
+    return run_pass(d, Mo, PassInput{x, nullptr}, p, wiener, out, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int xsq_separator_workspace(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
                             size_t* main_bytes, size_t* tail_bytes) {
     XSQ_REQUIRE(d && Mo && main_bytes && tail_bytes, "xsq_separator_workspace: null argument");
-    XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "xsq_separator_workspace: nb=%d N=%lld chunk_size=%lld max_stack=%d",
-                nb, (long long)N, (long long)cs, max_stack);
-    XSQ_REQUIRE(wiener >= 0, "xsq_separator_workspace: wiener=%d iterations", wiener);
+    if (int rc = check_call("xsq_separator_workspace", nb, N, cs, max_stack, wiener)) return rc;
     std::lock_guard<std::mutex> lk(d->mu);
     ForwardPlan* fp;
-    int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, &fp);
-    if (rc) return rc;
+    if (int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, &fp)) return rc;
     *main_bytes = fp->main_bytes;
     *tail_bytes = fp->tail_bytes;
     return XSQ_OK;
@@ -521,40 +542,13 @@ int xsq_separator_workspace(xsq_demixer* d, const xsq_model* Mo, int nb, int64_t
 
 static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* audio, const float* const* x_slot, int nb, int64_t N, int64_t cs,
                                   int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_, const float* gains = nullptr, int R = 0);
-
-int xsq_separator_forward(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack,
-                          int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                          size_t tail_ws_bytes, void* stream_, void* tail_stream_) {
-    XSQ_REQUIRE(audio, "xsq_separator_forward: null argument");
-    return separator_forward_impl(d, Mo, audio, nullptr, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws, tail_ws_bytes,
-                                  stream_, tail_stream_);
-}
-
-int xsq_separator_forward_indirect(xsq_demixer* d, xsq_model* Mo, const float* const* audio_slot, int nb, int64_t N, int64_t cs,
-                                   int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                                   size_t tail_ws_bytes, void* stream_, void* tail_stream_) {
-    XSQ_REQUIRE(audio_slot, "xsq_separator_forward_indirect: null argument");
-    return separator_forward_impl(d, Mo, nullptr, audio_slot, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws,
-                                  tail_ws_bytes, stream_, tail_stream_);
-}
-
-static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* audio, const float* const* x_slot, int nb, int64_t N, int64_t cs,
-                                  int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
-                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_, const float* gains, int R) {
+                                  size_t tail_ws_bytes, void* stream_, void* tail_stream_, const float* gains = nullptr, int R = 0) {
     XSQ_REQUIRE(d && Mo && (audio || x_slot) && out && ws, "xsq_separator_forward: null argument");
-    XSQ_REQUIRE(nb > 0 && N > 0 && cs > 0 && max_stack > 0, "xsq_separator_forward: nb=%d N=%lld chunk_size=%lld max_stack=%d",
-                nb, (long long)N, (long long)cs, max_stack);
-    XSQ_REQUIRE(wiener >= 0, "xsq_separator_forward: wiener=%d iterations", wiener);
+    if (int rc = check_call("xsq_separator_forward", nb, N, cs, max_stack, wiener)) return rc;
     hipStream_t main = (hipStream_t)stream_, side = (hipStream_t)tail_stream_;
+    const PassInput in{audio, x_slot};
     ForwardPlan* fp;
-    {
-        std::lock_guard<std::mutex> lk(d->mu);
-        int rc = get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, &fp);
-        if (rc) return rc;
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(main, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) fp->pinned = true;
-    }
+    if (int rc = acquire_plan(d, main, [&](ForwardPlan** o) { return get_forward_plan(d, Mo, nb, N, cs, max_stack, wiener, o); }, &fp)) return rc;
     bool any_tail = false;
     for (const PassPlan& p : fp->passes) any_tail = any_tail || p.tail;
     const bool beside = any_tail && overlap_tail && side != main && tail_ws != nullptr;
@@ -574,15 +568,14 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
         XSQ_HIP(hipStreamWaitEvent(main, d->ev_join, 0));
         return XSQ_OK;
     };
+    auto fail = [&](int code) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return code; };
     if (beside) {
         XSQ_HIP(hipEventRecord(d->ev_fork, main));
         XSQ_HIP(hipStreamWaitEvent(side, d->ev_fork, 0));
         forked = true;
         for (const PassPlan& p : fp->passes)
-            if (p.tail && (rc = run_pass(d, Mo, audio, x_slot, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, out, p.d_orows, tail_ws, tail_ws_bytes, side,
-                                         nullptr, gains, R)))
-                break;
-        if (rc) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return rc; }
+            if (p.tail && (rc = run_pass(d, Mo, in, p, wiener, out, tail_ws, tail_ws_bytes, side, nullptr, gains, R))) break;
+        if (rc) return fail(rc);
     }
     float* ext = (float*)ws;                                  // window-maximum tables of split sets (head of the workspace)
     const size_t ext_bytes = al256(fp->ext_floats * 4);
@@ -598,13 +591,26 @@ static int separator_forward_impl(xsq_demixer* d, xsq_model* Mo, const float* au
         if (p.tail && beside) continue;
         if (p.ext_off >= 0 && (int)i == p.set_first)       // first pass of a split set: every pass's maxima first
             for (int j = 0; j < p.set_count && rc == XSQ_OK; ++j)
-                rc = run_prepass(d, Mo, audio, x_slot, fp->passes[i + j], pws, pws_bytes, ext, main);
-        if (rc == XSQ_OK)
-            rc = run_pass(d, Mo, audio, x_slot, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, out, p.d_orows, pws, pws_bytes, main,
-                          p.ext_off >= 0 ? ext + p.ext_off : nullptr, gains, R);
+                rc = run_prepass(d, Mo, in, fp->passes[i + j], pws, pws_bytes, ext, main);
+        if (rc == XSQ_OK) rc = run_pass(d, Mo, in, p, wiener, out, pws, pws_bytes, main, p.ext_off >= 0 ? ext + p.ext_off : nullptr, gains, R);
     }
-    if (rc) { const std::string why = xsq_last_error(); (void)join(); set_error("%s", why.c_str()); return rc; }
-    return join();
+    return rc ? fail(rc) : join();
+}
+
+int xsq_separator_forward(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack,
+                          int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
+                          size_t tail_ws_bytes, void* stream_, void* tail_stream_) {
+    XSQ_REQUIRE(audio, "xsq_separator_forward: null argument");
+    return separator_forward_impl(d, Mo, audio, nullptr, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws, tail_ws_bytes,
+                                  stream_, tail_stream_);
+}
+
+int xsq_separator_forward_indirect(xsq_demixer* d, xsq_model* Mo, const float* const* audio_slot, int nb, int64_t N, int64_t cs,
+                                   int max_stack, int wiener, int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws,
+                                   size_t tail_ws_bytes, void* stream_, void* tail_stream_) {
+    XSQ_REQUIRE(audio_slot, "xsq_separator_forward_indirect: null argument");
+    return separator_forward_impl(d, Mo, nullptr, audio_slot, nb, N, cs, max_stack, wiener, overlap_tail, out, ws, ws_bytes, tail_ws,
+                                  tail_ws_bytes, stream_, tail_stream_);
 }
 
 int xsq_segment_schedule(int64_t N, int64_t chunk_len, int64_t ov, int64_t* segs, int max_segs) {
@@ -637,12 +643,8 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* Mo, const float* a
     if (int rc = check_segments("xsq_separator_forward_segments", nb, N, cs, cl, ov, max_stack, wiener)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     ForwardPlan* fp;
-    {
-        std::lock_guard<std::mutex> lk(d->mu);
-        if (int rc = get_segment_plan(d, Mo, nb, N, cs, cl, ov, max_stack, wiener, &fp)) return rc;
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) fp->pinned = true;
-    }
+    if (int rc = acquire_plan(d, stream, [&](ForwardPlan** o) { return get_segment_plan(d, Mo, nb, N, cs, cl, ov, max_stack, wiener, o); }, &fp))
+        return rc;
     XSQ_REQUIRE(ws_bytes >= fp->scratch_bytes + fp->main_bytes, "xsq_separator_forward_segments: workspace too small (%zu needed, %zu given)",
                 fp->scratch_bytes + fp->main_bytes, ws_bytes);
     // scratch (the un-faded stems of one pass) | workspace of the pass.  In segment order on ONE stream: the head of a
@@ -650,9 +652,7 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* Mo, const float* a
     float* scratch = (float*)ws;
     char* pws = (char*)ws + fp->scratch_bytes;
     for (const PassPlan& p : fp->passes) {
-        if (int rc = run_pass(d, Mo, audio, nullptr, p.d_xrows, p.B, p.n, p.n_pad, p.group, wiener, scratch, p.d_orows, pws,
-                              ws_bytes - fp->scratch_bytes, stream))
-            return rc;
+        if (int rc = run_pass(d, Mo, PassInput{audio, nullptr}, p, wiener, scratch, pws, ws_bytes - fp->scratch_bytes, stream)) return rc;
         if (int rc = xsq_crossfade_place_sources(scratch, p.d_orows, out, sources_of(Mo), nb, N, p.seg_start, p.seg_stride, p.n, p.seg_k, (int)ov,
                                                  p.fade_in, p.fade_out, stream))
             return rc;

@@ -435,6 +435,7 @@ class Unmix(nn.Module):
         runs of that many batch items share the Wiener window maximum (0 = the whole batch, the
         reference's behaviour); Separator uses it to stack independent chunks along the batch."""
         from .phase import wiener_em_arena, wiener_em_masked_arena
+        from .separator import switch                  # (the one table of A/B switches; separator imports this module)
         X, lead, S = self.table.as_arena(list(Xcomplex))
         if len(lead) != 2 or lead[1] != 2:
             raise ValueError(f"expected blocks of shape (nb_samples, 2, F, S, T, 2); got lead dims {lead}")
@@ -457,7 +458,7 @@ class Unmix(nn.Module):
         # initial estimate mask * X while they load -- same bits, a third less traffic.  ``wiener_masked = False`` /
         # XSQ_WIENER_MASKED=0 restores the two-step form (layer 4 writes mask * X, the EM refines it in place).
         masked = (not phasemix and all(int(t) % 2 == 0 for t in self._T) and
-                  bool(getattr(self, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")))
+                  switch(self, "wiener_masked"))
         with torch.cuda.device(dev):
             Y = torch.empty(self.table.numel(8 * B, S), dtype=torch.float32, device=dev)
             masks = torch.empty(self.table.numel(8 * B, S, complex_=False), dtype=torch.float32,

@@ -8,10 +8,11 @@ outside the accelerated path.
 """
 from __future__ import annotations
 
-import os
-
+import ctypes as C
 import json
+import os
 import sys
+from collections import namedtuple
 from pathlib import Path
 from typing import Optional, Tuple, Union
 
@@ -19,6 +20,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from . import _lib
 from .model import Unmix
 from .transforms import ComplexNorm, NSGTBase, make_filterbanks
 from .weights import seeded_state_dict
@@ -26,6 +28,53 @@ from .weights import seeded_state_dict
 # the reference's list (separator.py:29) plus the backend this package provides
 _SUPPORTED_RUNTIMES = ["torch-cpu", "torch-cuda", "onnx-cpu", "onnx-cuda", "hip-rocm"]
 _ACCELERATED = "hip-rocm"
+
+# THE list of A/B switches, each a plain instance attribute of its owner that is absent by default (tests set and delete
+# it).  name: (owner: the Separator or its Unmix ("model"), environment variable read per call while the attribute is absent
+# -- None: there is none --, default -- its type is the type of every value read --, whether a change drops the captured
+# forwards (True) or is captured beside them (False)).  ``switch`` reads them; ``Separator._graph_key`` iterates them.
+SWITCHES = {
+    "native": ("separator", "XSQ_NATIVE_FORWARD", True, True),
+    "fuse_whiten": ("separator", "XSQ_FUSE_WHITEN", True, True),
+    "fuse_phasemix": ("separator", "XSQ_FUSE_PHASEMIX", True, True),
+    "packed_fft": ("separator", "XSQ_PACKED_FFT", False, True),
+    "batch_chunks": ("separator", None, True, False),
+    "overlap_tail": ("separator", None, True, False),
+    "max_stack": ("separator", None, 8, False),
+    "pass_streams": ("separator", None, 1, False),
+    "max_item_slices": ("separator", None, 0, True),
+    "wiener_masked": ("model", "XSQ_WIENER_MASKED", True, True),
+    "niter_method": ("model", None, "auto", True),
+    "winograd": ("model", None, 7, True),
+    "precision": ("model", None, "fp32", False),
+}
+_ABSENT = object()
+# the key of a captured forward: captures of one device that differ in ``coexist`` live side by side in the cache, one that
+# differs from the current call in ``invalidating`` is stale
+GraphKey = namedtuple("GraphKey", "device coexist invalidating")
+_Native = namedtuple("_Native", "dev model d main cs max_stack cap")      # ``Separator._native_call``
+
+
+def switch(owner, name: str):
+    """Value of switch ``name`` on ``owner``: the instance attribute when there is one, else its environment variable (read per
+    call; "0" is off, anything else on), else the default.  KeyError for a name that ``SWITCHES`` does not list."""
+    _, env, default, _ = SWITCHES[name]
+    value = vars(owner).get(name, _ABSENT)         # (a plain instance attribute: no walk through nn.Module.__getattr__)
+    if value is not _ABSENT:
+        return type(default)(value)
+    env = os.environ.get(env) if env else None
+    return default if env is None else env != "0"
+
+
+def _fp32(audio: Tensor) -> Tensor:
+    return audio if audio.dtype == torch.float32 and audio.is_contiguous() else audio.contiguous().float()
+
+
+def _set_wiener_options(separator, niter, softmask, residual):
+    """The post-filter options of ``Separator.load`` / ``seeded_separator``: None leaves the model's own."""
+    for name, value in (("niter", niter), ("softmask", softmask), ("residual", residual)):
+        if value is not None:
+            setattr(separator, name, value)
 
 
 class Separator(nn.Module):
@@ -46,12 +95,7 @@ class Separator(nn.Module):
         separator = cls(xumx_model=xumx_model, encoder=encoder, sample_rate=sample_rate,
                         runtime_backend=runtime_backend, chunk_size=chunk_size, device=device).to(device)
         separator.freeze()
-        if niter is not None:
-            separator.niter = niter
-        if softmask is not None:
-            separator.softmask = softmask
-        if residual is not None:
-            separator.residual = residual
+        _set_wiener_options(separator, niter, softmask, residual)
         for _ in range(warmup):
             waveform = torch.rand((1, 2, int(100 * sample_rate)), dtype=torch.float32, device=device)
             separator.forward(waveform)
@@ -129,14 +173,13 @@ class Separator(nn.Module):
         switches, the packed-parameter version of the model (captured kernels hold raw pointers into the
         xsq_model handle), the arithmetic mode and the post-filter / fusion switches read per call."""
         m = self.xumx_model
-        return (tuple(audio_big.shape), audio_big.device.index, self.chunk_size, getattr(m, "precision", "fp32"),
-                bool(getattr(self, "overlap_tail", True)), bool(getattr(self, "batch_chunks", True)),
-                int(getattr(self, "max_stack", 8)), int(getattr(self, "pass_streams", 1)),
-                m._version(), tuple(bool(b.realtime) for b in m.sliced_umx), self._fused(),
-                bool(getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0")),
-                bool(getattr(m, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")), self._packed_fft(),
-                bool(getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0")), int(getattr(self, "max_item_slices", 0)),
-                int(getattr(m, "winograd", 7)), self.niter, getattr(m, "niter_method", "auto"), self.softmask, self.residual)
+        # two switches enter as what the call makes of them (the fusion on an all-mix-phase model, ``_packed_fft``), not as read
+        derived = {"fuse_phasemix": self._fused(), "packed_fft": self._packed_fft()}
+        items = [(drops, (name, derived[name] if name in derived else switch(m if owner == "model" else self, name)))
+                 for name, (owner, _, _, drops) in SWITCHES.items()]
+        coexist, dropping = (tuple(kv for d, kv in items if d is drops) for drops in (False, True))
+        return GraphKey(audio_big.device.index, (tuple(audio_big.shape), self.chunk_size) + coexist,
+                        (m._version(), tuple(bool(b.realtime) for b in m.sliced_umx), self.niter, self.softmask, self.residual) + dropping)
 
     def drop_graphs(self):
         """Forget every captured forward (they hold raw pointers into the model handle and the workspaces)."""
@@ -150,13 +193,12 @@ class Separator(nn.Module):
         model handle they point into is rebuilt (``Unmix._model`` frees it)."""
         key = self._graph_key(audio_big)
         cache = self.__dict__.setdefault("_graphs", {})
-        ver = key[8:]
-        for k in [k for k in cache if k[1] == key[1] and k[8:] != ver]:
+        for k in [k for k in cache if k.device == key.device and k.invalidating != key.invalidating]:
             del cache[k]                              # stale: would replay against freed device memory
         entry = cache.get(key)
         wiener = self._native_mode(audio_big)
-        if wiener is not None and (audio_big.dtype != torch.float32 or not audio_big.is_contiguous()):
-            audio_big = audio_big.contiguous().float()
+        if wiener is not None:
+            audio_big = _fp32(audio_big)
         if entry is None:
             # native path: the captured kernels read the input through a DEVICE pointer slot (xsq_separator_forward_indirect),
             # so a replay follows the caller's tensor -- no copy of the input into a static buffer (85 MB for a 240 s track).
@@ -199,7 +241,7 @@ class Separator(nn.Module):
         (tools/probe/pk_mfma_hazard.hip).  ``packed_fft = True`` / XSQ_PACKED_FFT=1 asks the library for them; the product
         build refuses with ``XsqError``.  A diagnostic build honours it only while no model or trainer of this process
         contracts on split-bf16 MFMAs."""
-        want = bool(getattr(self, "packed_fft", os.environ.get("XSQ_PACKED_FFT", "0") != "0"))
+        want = switch(self, "packed_fft")
         eng = self.nsgt.nsgt.nsgt
         if not want and not eng._packed_fft:
             return False
@@ -212,25 +254,25 @@ class Separator(nn.Module):
     def _fused(self) -> bool:
         """Mix-phase models: the CDAE writes the masks only and the inverse transform forms mask * X while it
         loads (same products, same order: bitwise equal to decoding the materialised estimates)."""
-        return bool(getattr(self, "fuse_phasemix", os.environ.get("XSQ_FUSE_PHASEMIX", "1") != "0")
-                    and all(bool(b.realtime) for b in self.xumx_model.sliced_umx))
+        return bool(switch(self, "fuse_phasemix") and all(bool(b.realtime) for b in self.xumx_model.sliced_umx))
 
-    def _encode(self, audio: Tensor):
-        """Forward transform of (B, 2, n) audio -> (coefficient list, xin_ready).  By default the analysis kernels also
-        write the CDAE's whitened magnitude straight into the model's workspace (xsq_slicqt_forward_xin; same values as
-        the separate magnitude pass, which is then skipped); ``fuse_whiten = False`` / XSQ_FUSE_WHITEN=0 restores it."""
-        if not getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0") or audio.dim() != 3 or audio.shape[1] != 2 \
-                or audio.device.type != "cuda":
-            return self.nsgt(audio), False
+    def _demix_py(self, out: Tensor, audio: Tensor, length: int, offsets: Tensor, group: int = 0):
+        """One pass of the Python chunk loop over (B, 2, n) audio, a short chunk zero-padded to sllen/2 + 1 (separator.py:162-170):
+        forward transform, CDAE + post-filter, inverse transform; packed channel (target, b, c) is written to
+        out.view(-1)[offsets[target, b, c] : +length].  By default the analysis kernels also write the CDAE's whitened
+        magnitude straight into the model's workspace (xsq_slicqt_forward_xin; same values as the separate magnitude pass,
+        which is then skipped); ``fuse_whiten = False`` / XSQ_FUSE_WHITEN=0 restores it."""
+        short = int(self.nsgt.nsgt.sllen / 2) + 1 - audio.shape[-1]
+        if short > 0:
+            audio = torch.cat([audio, torch.zeros((*audio.shape[:-1], short), device=audio.device, dtype=audio.dtype)], dim=-1)
         eng = self.nsgt.nsgt.nsgt
-        S = eng.plan.num_slices(audio.shape[-1])
-        ws, mean, scale, split = self.xumx_model.whitening_target(audio.device, audio.shape[0], S)
-        arena, lead, S = eng.forward(audio, whiten=(ws.data_ptr(), mean, scale, split))
-        return eng.table.views(arena, lead, S), True
-
-    def _decode_into(self, out: Tensor, Xc, length: int, offsets: Tensor, group: int = 0, xin_ready: bool = False):
-        """CDAE + post-filter + inverse transform of the coefficient list ``Xc`` (batch B); packed channel
-        (target, b, c) is written to out.view(-1)[offsets[target, b, c] : +length]."""
+        if not switch(self, "fuse_whiten") or audio.dim() != 3 or audio.shape[1] != 2 or audio.device.type != "cuda":
+            Xc, xin_ready = self.nsgt(audio), False
+        else:
+            S = eng.plan.num_slices(audio.shape[-1])
+            ws, mean, scale, split = self.xumx_model.whitening_target(audio.device, audio.shape[0], S)
+            arena, lead, S = eng.forward(audio, whiten=(ws.data_ptr(), mean, scale, split))
+            Xc, xin_ready = eng.table.views(arena, lead, S), True
         eng = self.insgt.nsgt.nsgt
         offs = offsets.reshape(-1).contiguous()
         if self._fused():
@@ -298,39 +340,32 @@ class Separator(nn.Module):
             raise ValueError(f"work items are at most chunk_size = {self.chunk_size} samples (got {n})")
         if tuple(row_offsets.shape) != (4, B, 2) or row_offsets.dtype != torch.int64:
             raise ValueError(f"row_offsets must be int64 (4, {B}, 2); got {tuple(row_offsets.shape)}")
-        min_samples = int(self.nsgt.nsgt.sllen / 2) + 1
         wiener = self._native_mode(audio)
         if wiener is not None and out.is_contiguous() and out.dtype == torch.float32 and B % max(1, group) == 0:
             # one C call per pass (xsq_demix_pass): the zero padding of a short item is a slice count, not a copy
-            from . import _lib
-            if x_rows is None and (audio.dtype != torch.float32 or not audio.is_contiguous()):
-                audio = audio.contiguous().float()
-            dev = audio.device
+            if x_rows is None:                     # (a row table addresses the items where they lie)
+                audio = _fp32(audio)
             offs = row_offsets if row_offsets.is_contiguous() else row_offsets.contiguous()
-            with torch.cuda.device(dev):
-                model = self.xumx_model._model(dev)
-                d = self.nsgt.nsgt.nsgt.demixer(dev)
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                n_pad = max(n, min_samples)
-                key = ("pass", B, n_pad, wiener, self._handle_key(), dev.index)
+            c = self._native_call(audio.device)
+            with torch.cuda.device(c.dev):
+                stream = c.main.cuda_stream
+                n_pad = max(n, int(self.nsgt.nsgt.sllen / 2) + 1)
+                # (no schedule cuts a pass: neither the cap nor ``_plan_sizes`` has a part in it)
+                key = ("pass", B, n_pad, wiener, self._handle_key(), c.dev.index)
                 nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
                 if nbytes is None:
-                    nbytes = _lib.lib.xsq_demix_pass_workspace(d, model, B, n_pad, wiener)
+                    nbytes = _lib.lib.xsq_demix_pass_workspace(c.d, c.model, B, n_pad, wiener)
                     if nbytes == 0:
                         raise _lib.XsqError("xsq_demix_pass_workspace: " + _lib.last_error())
                     self._nsizes[key] = nbytes
-                ws = self._native_ws(dev, stream, "pass", nbytes)
-                _lib.check(_lib.lib.xsq_demix_pass(d, model, audio.data_ptr(), x_rows.data_ptr() if x_rows is not None else None,
+                ws = self._native_ws(c.dev, stream, "pass", nbytes)
+                _lib.check(_lib.lib.xsq_demix_pass(c.d, c.model, audio.data_ptr(), x_rows.data_ptr() if x_rows is not None else None,
                                                    B, n, n_pad, int(group), wiener, out.data_ptr(), offs.data_ptr(),
                                                    ws.data_ptr(), ws.numel(), stream), "xsq_demix_pass")
             return
         if x_rows is not None:
             audio = torch.cat(keep, dim=0)
-        if n < min_samples:
-            audio = torch.cat([audio, torch.zeros((*audio.shape[:-1], min_samples - n), device=audio.device,
-                                                  dtype=audio.dtype)], dim=-1)
-        Xc, ready = self._encode(audio)
-        self._decode_into(out, Xc, n, row_offsets, group=group, xin_ready=ready)
+        self._demix_py(out, audio, n, row_offsets, group)
 
     # -- the native whole-call path ---------------------------------------------------------------------------
     def _native_mode(self, audio: Tensor):
@@ -339,15 +374,11 @@ class Separator(nn.Module):
         (``niter``; 0 on an offline model is mix-phase).  Every entry point comes through here: a realtime model asked for
         ``softmask`` or ``residual`` is refused (``XsqError`` naming the option)."""
         self.xumx_model.wiener_options()
-        if not getattr(self, "native", os.environ.get("XSQ_NATIVE_FORWARD", "1") != "0"):
-            return None
         if audio.dim() != 3 or audio.shape[1] != 2 or audio.device.type != "cuda" or audio.shape[-1] < 1:
             return None
-        if not (getattr(self, "batch_chunks", True) and int(getattr(self, "pass_streams", 1)) == 1
-                and getattr(self, "fuse_whiten", os.environ.get("XSQ_FUSE_WHITEN", "1") != "0")
-                and getattr(self, "fuse_phasemix", os.environ.get("XSQ_FUSE_PHASEMIX", "1") != "0")
-                and getattr(self.xumx_model, "wiener_masked", os.environ.get("XSQ_WIENER_MASKED", "1") != "0")
-                and getattr(self.xumx_model, "niter_method", "auto") == "auto"):
+        if not (switch(self, "native") and switch(self, "batch_chunks") and switch(self, "pass_streams") == 1
+                and switch(self, "fuse_whiten") and switch(self, "fuse_phasemix")
+                and switch(self.xumx_model, "wiener_masked") and switch(self.xumx_model, "niter_method") == "auto"):
             return None
         modes = {bool(b.realtime) for b in self.xumx_model.sliced_umx}
         if len(modes) != 1:
@@ -364,11 +395,34 @@ class Separator(nn.Module):
             ws = pool[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
         return ws
 
-    def _tail_stream(self, dev: torch.device):
+    def _stream_pool(self, dev: torch.device, n: int = 1) -> list:
+        """At least ``n`` side streams of ``dev``: pool[0] = the tail's, pool[1:] = extra pass streams."""
         pool = self.__dict__.setdefault("_side_streams", {}).setdefault(dev.index, [])
-        if not pool:
+        while len(pool) < n:
             pool.append(torch.cuda.Stream(device=dev))
-        return pool[0]
+        return pool
+
+    def _native_call(self, dev: torch.device) -> _Native:
+        """What a native entry point needs before its C calls: the device with an index, the model handle, the demixer, the
+        caller's stream and the chunking numbers (``cs``, ``max_stack``, the ``max_item_slices`` cap)."""
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return _Native(dev, self.xumx_model._model(dev), self.nsgt.nsgt.nsgt.demixer(dev), torch.cuda.current_stream(dev),
+                       int(min(self.chunk_size, 1 << 62)), switch(self, "max_stack"), switch(self, "max_item_slices"))
+
+    def _plan_sizes(self, c: _Native, kind: str, args: tuple, fn, nout: int):
+        """The ``nout`` workspace byte counts of a whole-call shape under the current cap, ``fn(d, model, *args, &size...)``:
+        asked of the library once per (kind, args, model handle, device, cap) and kept in ``_nsizes``."""
+        # the cap is sticky state of the native demixer and part of its plan key: set it on EVERY call, not only on a
+        # miss of ``_nsizes`` -- after 0 -> 20 -> 0 a cached shape would otherwise run under the stale cap (ADVICE round 4)
+        _lib.check(_lib.lib.xsq_demixer_set_max_rows(c.d, c.cap), "xsq_demixer_set_max_rows")
+        key = (kind,) + args + (self._handle_key(), c.dev.index, c.cap)
+        sizes = self.__dict__.setdefault("_nsizes", {})
+        if key not in sizes:
+            outs = [C.c_size_t() for _ in range(nout)]
+            _lib.check(fn(c.d, c.model, *args, *map(C.byref, outs)), fn.__name__)
+            sizes[key] = outs[0].value if nout == 1 else tuple(o.value for o in outs)
+        return sizes[key]
 
     def _forward_native(self, audio_big: Tensor, wiener: int, slot: Optional[Tensor] = None, gains: Optional[Tensor] = None) -> Tensor:
         """``forward`` as ONE C call (xsq_separator_forward, csrc/demix.hip): the stacked full chunks on the caller's
@@ -376,51 +430,42 @@ class Separator(nn.Module):
         row-offset tables cached per call shape.  Per call the host allocates the result and makes one ctypes call.
         ``gains`` (host fp32 (R, 4)): the R mixes of ``remix`` instead of the stems (xsq_separator_remix, same schedule
         and workspaces)."""
-        from . import _lib
-        import ctypes as C
-        if audio_big.dtype != torch.float32 or not audio_big.is_contiguous():
-            audio_big = audio_big.contiguous().float()
-        nb, N, dev = audio_big.shape[0], audio_big.shape[-1], audio_big.device
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        eng = self.nsgt.nsgt.nsgt
+        audio_big = _fp32(audio_big)
         self._packed_fft()
-        with torch.cuda.device(dev):
-            model = self.xumx_model._model(dev)
-            d = eng.demixer(dev)
-            main = torch.cuda.current_stream(dev)
-            overlap = bool(getattr(self, "overlap_tail", True))
-            side = self._tail_stream(dev) if overlap else main
-            cs = int(min(self.chunk_size, 1 << 62))
-            max_stack = int(getattr(self, "max_stack", 8))
-            key = (nb, N, cs, max_stack, wiener, self._handle_key(), dev.index, int(getattr(self, "max_item_slices", 0)))
-            # the cap is sticky state of the native demixer and part of its plan key: set it on EVERY call, not only on a
-            # cache miss here -- after 0 -> 20 -> 0 a cached shape would otherwise run under the stale cap (ADVICE round 4)
-            _lib.check(_lib.lib.xsq_demixer_set_max_rows(d, int(getattr(self, "max_item_slices", 0))), "xsq_demixer_set_max_rows")
-            sizes = self.__dict__.setdefault("_nsizes", {}).get(key)
-            if sizes is None:
-                mb, tb = C.c_size_t(), C.c_size_t()
-                _lib.check(_lib.lib.xsq_separator_workspace(d, model, nb, N, cs, max_stack, wiener, C.byref(mb), C.byref(tb)),
-                           "xsq_separator_workspace")
-                sizes = self._nsizes[key] = (mb.value, tb.value)
+        c = self._native_call(audio_big.device)
+        with torch.cuda.device(c.dev):
+            nb, N, dev, main = audio_big.shape[0], audio_big.shape[-1], c.dev, c.main
+            overlap = switch(self, "overlap_tail")
+            side = self._stream_pool(dev)[0] if overlap else main
+            sizes = self._plan_sizes(c, "forward", (nb, N, c.cs, c.max_stack, wiener), _lib.lib.xsq_separator_workspace, 2)
             two = overlap and sizes[1] > 0
             ws = self._native_ws(dev, main.cuda_stream, "main", sizes[0] if two else max(sizes))
             wt = self._native_ws(dev, main.cuda_stream, "tail", sizes[1]) if two else None
+            out = torch.empty(self._nb_sources() if gains is None else gains.shape[0], nb, 2, N, dtype=torch.float32, device=dev)
+            # the result, the two workspaces and the two streams: the arguments all three whole-call signatures share
+            shared = (1 if two else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), wt.data_ptr() if two else None, wt.numel() if two else 0,
+                      main.cuda_stream, side.cuda_stream if two else main.cuda_stream)
             if gains is not None:
-                out = torch.empty(gains.shape[0], nb, 2, N, dtype=torch.float32, device=dev)
-                _lib.check(_lib.lib.xsq_separator_remix(d, model, audio_big.data_ptr(), nb, N, cs, max_stack, wiener, 1 if two else 0,
-                                                        out.data_ptr(), ws.data_ptr(), ws.numel(), wt.data_ptr() if two else None,
-                                                        wt.numel() if two else 0, main.cuda_stream,
-                                                        side.cuda_stream if two else main.cuda_stream, gains.data_ptr(),
-                                                        int(gains.shape[0])), "xsq_separator_remix")
+                _lib.check(_lib.lib.xsq_separator_remix(c.d, c.model, audio_big.data_ptr(), nb, N, c.cs, c.max_stack, wiener, *shared,
+                                                        gains.data_ptr(), int(gains.shape[0])), "xsq_separator_remix")
                 return out
-            out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=dev)
             fn, src = ((_lib.lib.xsq_separator_forward, audio_big.data_ptr()) if slot is None
                        else (_lib.lib.xsq_separator_forward_indirect, slot.data_ptr()))
-            _lib.check(fn(d, model, src, nb, N, cs, max_stack, wiener, 1 if two else 0, out.data_ptr(),
-                          ws.data_ptr(), ws.numel(), wt.data_ptr() if two else None, wt.numel() if two else 0,
-                          main.cuda_stream, side.cuda_stream if two else main.cuda_stream), "xsq_separator_forward")
+            _lib.check(fn(c.d, c.model, src, nb, N, c.cs, c.max_stack, wiener, *shared), "xsq_separator_forward")
         return out
+
+    def _stacked_chunks(self, nb: int, N: int, cs: int):
+        """[(first sample, chunks)] of the stacked passes of the Python chunk loop: the FULL chunks of an N-sample call, at
+        most ``max_stack`` (chunk, sample) pairs per pass -- that bounds the workspaces (~1.8 GB per stacked full chunk) and
+        keeps BC*S inside one launch for any track length; a single chunk is no stack.  ``batch_chunks = False``: none."""
+        full = N // cs if switch(self, "batch_chunks") else 0
+        per_pass = max(1, switch(self, "max_stack") // nb)
+        stacked, start0 = [], 0
+        while full - start0 // cs >= 2 and per_pass >= 2:
+            k = min(per_pass, full - start0 // cs)
+            stacked.append((start0, k))
+            start0 += k * cs
+        return stacked
 
     @torch.no_grad()
     def forward(self, audio_big: Tensor) -> Tensor:
@@ -437,7 +482,6 @@ class Separator(nn.Module):
         if wiener is not None:
             return self._forward_native(audio_big, wiener)
         nb, N, cs = audio_big.shape[0], audio_big.shape[-1], self.chunk_size
-        min_samples = int(self.nsgt.nsgt.sllen / 2) + 1
         dev = audio_big.device
         self._packed_fft()
         # every chunk's stems are written straight into their place of the result (the hard concat
@@ -447,30 +491,12 @@ class Separator(nn.Module):
         rows = (torch.arange(J, device=dev).view(J, 1, 1, 1) * nb + torch.arange(nb, device=dev).view(1, 1, nb, 1)) * 2 \
             + torch.arange(2, device=dev).view(1, 1, 1, 2)                       # (J, 1, nb, 2) row of `out`
 
-        def decode(audio, length, offsets, group=0):
-            Xc, ready = self._encode(audio)
-            self._decode_into(out, Xc, length, offsets, group, xin_ready=ready)
-
-        full = N // cs if getattr(self, "batch_chunks", True) else 0
-        start0 = 0
-        # stack at most `max_stack` (chunk, sample) pairs per pass: bounds the workspaces (~1.8 GB per
-        # stacked full chunk) and keeps BC*S inside one launch for any track length
-        per_pass = max(1, getattr(self, "max_stack", 8) // nb)
-        stacked = []                                                                 # (first sample, chunks)
-        while full - start0 // cs >= 2 and per_pass >= 2:
-            k = min(per_pass, full - start0 // cs)
-            stacked.append((start0, k))
-            start0 += k * cs
-
         def rest(first):
             for start in range(first, N, cs):
                 audio = audio_big[..., start:min(start + cs, N)]
-                n_samples = audio.shape[-1]
-                if n_samples < min_samples:
-                    audio = torch.cat([audio, torch.zeros((*audio.shape[:-1], min_samples - n_samples),
-                                                          device=dev, dtype=audio.dtype)], dim=-1)
-                decode(audio, n_samples, rows * N + start)
+                self._demix_py(out, audio, audio.shape[-1], rows * N + start)
 
+        stacked = self._stacked_chunks(nb, N, cs)
         if not stacked:
             rest(0)
             return out
@@ -480,11 +506,9 @@ class Separator(nn.Module):
         # stacked passes themselves are dealt to `pass_streams` streams (default 1: all on the caller's).
         main = torch.cuda.current_stream(dev)
         tail_first = stacked[-1][0] + stacked[-1][1] * cs
-        pool = self.__dict__.setdefault("_side_streams", {}).setdefault(dev.index, [])
-        nstreams = max(1, min(int(getattr(self, "pass_streams", 1)), len(stacked)))
-        overlap_tail = tail_first < N and getattr(self, "overlap_tail", True)
-        while len(pool) < nstreams:                       # pool[0] = tail, pool[1:] = extra pass streams
-            pool.append(torch.cuda.Stream(device=dev))
+        nstreams = max(1, min(switch(self, "pass_streams"), len(stacked)))
+        overlap_tail = tail_first < N and switch(self, "overlap_tail")
+        pool = self._stream_pool(dev, nstreams)
         used = []
         if overlap_tail:
             pool[0].wait_stream(main)
@@ -499,7 +523,7 @@ class Separator(nn.Module):
             with torch.cuda.stream(st):
                 a = audio_big[..., s0:s0 + k * cs].reshape(nb, 2, k, cs).permute(2, 0, 1, 3).reshape(k * nb, 2, cs)
                 offs = rows * N + s0 + torch.arange(k, device=dev).view(1, k, 1, 1) * cs   # (J, k, nb, 2)
-                decode(a, cs, offs, group=nb)                                    # batch = (chunk, b)
+                self._demix_py(out, a, cs, offs, group=nb)                       # batch = (chunk, b)
         for st in used:
             main.wait_stream(st)
         if not overlap_tail:
@@ -557,34 +581,16 @@ class Separator(nn.Module):
         wiener = self._native_mode(audio_big)
         if wiener is None:
             return overlapped_loop(self.forward, audio_big, chunk_len, ov)
-        from . import _lib
-        import ctypes as C
-        if audio_big.dtype != torch.float32 or not audio_big.is_contiguous():
-            audio_big = audio_big.contiguous().float()
-        nb, N, dev = audio_big.shape[0], audio_big.shape[-1], audio_big.device
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        audio_big = _fp32(audio_big)
         self._packed_fft()
-        with torch.cuda.device(dev):
-            model = self.xumx_model._model(dev)
-            d = self.nsgt.nsgt.nsgt.demixer(dev)
-            main = torch.cuda.current_stream(dev)
-            cs = int(min(self.chunk_size, 1 << 62))
-            max_stack = int(getattr(self, "max_stack", 8))
-            cap = int(getattr(self, "max_item_slices", 0))
-            key = ("segments", nb, N, cs, chunk_len, ov, max_stack, wiener, self._handle_key(), dev.index, cap)
-            _lib.check(_lib.lib.xsq_demixer_set_max_rows(d, cap), "xsq_demixer_set_max_rows")      # (sticky, part of the plan key)
-            nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
-            if nbytes is None:
-                b = C.c_size_t()
-                _lib.check(_lib.lib.xsq_separator_segments_workspace(d, model, nb, N, cs, chunk_len, ov, max_stack, wiener, C.byref(b)),
-                           "xsq_separator_segments_workspace")
-                nbytes = self._nsizes[key] = b.value
-            ws = self._native_ws(dev, main.cuda_stream, "main", nbytes)
-            out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.xsq_separator_forward_segments(d, model, audio_big.data_ptr(), nb, N, cs, chunk_len, ov, max_stack, wiener,
-                                                               out.data_ptr(), ws.data_ptr(), ws.numel(), main.cuda_stream),
-                       "xsq_separator_forward_segments")
+        c = self._native_call(audio_big.device)
+        with torch.cuda.device(c.dev):
+            nb, N, stream = audio_big.shape[0], audio_big.shape[-1], c.main.cuda_stream
+            args = (nb, N, c.cs, chunk_len, ov, c.max_stack, wiener)
+            ws = self._native_ws(c.dev, stream, "main", self._plan_sizes(c, "segments", args, _lib.lib.xsq_separator_segments_workspace, 1))
+            out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=c.dev)
+            _lib.check(_lib.lib.xsq_separator_forward_segments(c.d, c.model, audio_big.data_ptr(), *args, out.data_ptr(),
+                                                               ws.data_ptr(), ws.numel(), stream), "xsq_separator_forward_segments")
         return out
 
     @torch.no_grad()
@@ -632,7 +638,6 @@ def segments(N: int, chunk_len: int, ov: int):
     """[(start, samples, fade_in, fade_out)] of the overlapped segments of an N-sample track (xsq_segment_schedule: host
     arithmetic, the one statement of the rule that the native call, the fallback loop and the tests share)."""
     import numpy as np
-    from . import _lib
     buf = np.zeros((max(1, N // max(1, chunk_len) + 2), 4), dtype=np.int64)
     n = _lib.lib.xsq_segment_schedule(int(N), int(chunk_len), int(ov), buf.ctypes.data, len(buf))
     if n < 0 or n > len(buf):
@@ -774,10 +779,5 @@ def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed
     sep = Separator(xumx_model=xumx_model, encoder=encoder, sample_rate=sr, chunk_size=chunk_size,
                     device=device, quiet=True).to(device)
     sep.freeze()
-    if niter is not None:
-        sep.niter = niter
-    if softmask is not None:
-        sep.softmask = softmask
-    if residual is not None:
-        sep.residual = residual
+    _set_wiener_options(sep, niter, softmask, residual)
     return sep
