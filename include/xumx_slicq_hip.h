@@ -576,6 +576,66 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* model, const float
                                    int64_t chunk_size, int64_t chunk_len, int64_t ov, int max_stack, int wiener, float* out,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the streaming session: Separator.stream, block-by-block demixing equal to one forward ---------------------------
+ * With h = L / 4, slice s covers the samples [(2s - 2)h, (2s + 2)h) and block k = samples [2kh, (2k + 2)h) is the second half
+ * of inverted slice k plus the first half of slice k + 1.  In mix-phase mode the mask of slice s depends on the coefficients
+ * of the slices s - back .. s + XSQ_STREAM_AHEAD only (back = XSQ_STREAM_BACK_CAUSAL for the causal stack, whose first layer
+ * is left-padded, XSQ_STREAM_BACK_OFFLINE for the offline one; tests/test_stream_cpu.py perturbs the oracle), so a block is
+ * final 8h samples after its first one, whatever back is.  Steps fire on the ABSOLUTE block grid: step j closes the blocks
+ * [j m, (j + 1) m), m = hop_slices, once sample (2 ((j + 1) m + ahead) + 2) h has been fed; what a session returns depends on
+ * the samples and m only, not on how they were split into pushes.  Wiener-EM cannot stream (window statistics over 5000
+ * frames from the start of a chunk): sessions are mix-phase, xsq_model_set_wiener_options must be 0.
+ *
+ * xsq_stream_schedule: the rule as pure host arithmetic (no device needed) for a stream of N samples in all: steps[6 j ..] =
+ *   (first block, blocks, first slice inverted, first and last slice of the CDAE window, samples that must have been fed --
+ *   beyond N for the steps that only the end of the stream releases).  The window is clipped to the slices N samples have
+ *   (at least L / 2 + 1 samples are assumed, as the whole call pads) and never shorter than 3.  Returns the number of steps.
+ * xsq_stream_create: a session of nb_samples rows on the demixer's plan (not owned).  Host state only: the DEVICE state --
+ *   xsq_stream_state_bytes: an audio ring of (2 (back + ahead + m) + 2) h samples per channel, and twice the 2h-sample second
+ *   half of the last inverted slice per packed output channel -- is the caller's and is passed to every call; it does not
+ *   grow with the stream.  It needs no initialisation.
+ * xsq_stream_push: count more samples of every row (row r at x + r * row_stride; rows (sample, channel)) into the ring, by one
+ *   launch on `stream`.  XSQ_ERR_ARG when that would pass xsq_stream_next_trigger: the step has to run first.
+ * xsq_stream_step: the next step, every launch on `stream`, no host synchronisation, no device-to-host read:
+ *     xsq_slicqt_forward_ring (the window's slices from the ring at their absolute index; only samples before 0 and from
+ *       `total` on are zero) -> xsq_cdae_forward_xin (masks of the window) -> xsq_slicqt_inverse_masked_carry (the NEW slices
+ *       only: mask * mix formed on the way in, the first block added onto the carried half, the last half carried on).
+ *   total < 0: the stream is open and the step's trigger must have been fed; total >= 0 (= the samples fed): the stream has
+ *   ended, windows are clipped at its last slice and the last block is cut at `total`.  x / row_stride / count (count may be 0):
+ *   the samples that release the step, exactly up to xsq_stream_next_trigger, instead of a push of their own -- the step's
+ *   first kernel reads them where they lie and stores them to the ring.  out: packed channel (target, sample, c)
+ *   at out + row * out_stride, `length` samples = what the step emits (XSQ_ERR_ARG otherwise).  workspace:
+ *   xsq_stream_workspace bytes (0 on error).  A session belongs to one stream at a time.                                */
+#define XSQ_STREAM_BACK_CAUSAL 3
+#define XSQ_STREAM_BACK_OFFLINE 2
+#define XSQ_STREAM_AHEAD 2
+typedef struct xsq_stream xsq_stream;
+int xsq_stream_schedule(int64_t N, int L, int hop_slices, int back, int ahead, int64_t* steps, int max_steps);
+int xsq_stream_create(xsq_stream** out, xsq_demixer* d, const xsq_model* model, int nb_samples, int hop_slices, int back, int ahead);
+int xsq_stream_destroy(xsq_stream* s);
+size_t xsq_stream_state_bytes(const xsq_stream* s);
+size_t xsq_stream_workspace(const xsq_stream* s, const xsq_model* model);
+int64_t xsq_stream_next_trigger(const xsq_stream* s);
+int xsq_stream_push(xsq_stream* s, void* state, const float* x, int64_t row_stride, int64_t count, void* stream);
+int xsq_stream_step(xsq_stream* s, xsq_model* model, void* state, const float* x, int64_t row_stride, int64_t count, int64_t total,
+                    float* out, int64_t out_stride, int64_t length, void* workspace, size_t workspace_bytes, void* stream);
+/* The two transform halves of a step.  xsq_slicqt_forward_ring: S slices per channel from absolute slice first_slice on, read
+ * from a ring of ring_len samples per channel that holds absolute sample i at i % ring_len; n = samples of the stream so far
+ * (later ones read as zero, as do those before 0), the last new_count of which are not in the ring yet: they are read from x_new
+ * (row bc at x_new + bc * new_stride) and stored to the ring; they must lie in the second halves of the call's slices.
+ * xsq_slicqt_inverse_masked_carry: slices [first, first + S) of the window
+ * arenas (S_window slices; masks BC channels, mix BCx) are inverted; they lie at positions shift .. of the step (shift = 0: the
+ * stream's slice 0 is the first of them; 1: carry_in holds the second half of their predecessor), close S - 1 + shift blocks
+ * of 2h samples, `length` samples of which are written to row bc of y (y + bc * y_stride), and leave the second half of the
+ * last one in carry_out (BC x 2h floats; not carry_in).  No slice is inverted twice.                                       */
+int xsq_slicqt_forward_ring(xsq_plan* plan, float* ring, int ring_len, int BC, int64_t first_slice, int S, int64_t n, const float* x_new,
+                            int64_t new_stride, int64_t new_count, float* coef, float* xin, const float* mean, const float* scale,
+                            int split, void* workspace, size_t workspace_bytes, void* stream);
+size_t xsq_slicqt_inverse_carry_workspace(xsq_plan* plan, int BC, int BCx, int S);
+int xsq_slicqt_inverse_masked_carry(xsq_plan* plan, const float* masks, const float* mix, int BC, int BCx, int S_window, int first, int S,
+                                    int shift, int64_t length, float* y, int64_t y_stride, const float* carry_in, float* carry_out,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- per-kernel timing (bench.py roofline) ------------------------------------------
  * When enabled, every kernel launch of the library is bracketed by hipEvents recorded on
  * its own launch stream.  xsq_profile_read synchronises the outstanding events and

@@ -6,3 +6,11 @@ host-side plan builder and the ``nn.Module`` mirrors of the reference surface
 (``separator``, ``inference``, ``cadenza.separate_sources`` for overlapped, cross-faded segments).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the public names of ``separator`` without importing the HIP library (and torch) when the package is imported
+    if name in ("Separator", "StreamSession", "StreamGrid", "streamed_loop", "stream_steps"):
+        from . import separator
+        return getattr(separator, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -107,6 +107,19 @@ _SIGS = {
     "xsq_crossfade_place": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "xsq_separator_segments_workspace": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "xsq_separator_forward_segments": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_stream_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    "xsq_stream_create": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "xsq_stream_destroy": (C.c_int, [_vp]),
+    "xsq_stream_state_bytes": (C.c_size_t, [_vp]),
+    "xsq_stream_workspace": (C.c_size_t, [_vp, _vp]),
+    "xsq_stream_next_trigger": (C.c_int64, [_vp]),
+    "xsq_stream_push": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp]),
+    "xsq_stream_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp]),
+    "xsq_slicqt_forward_ring": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, C.c_int,
+                                          _vp, C.c_size_t, _vp]),
+    "xsq_slicqt_inverse_carry_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
+    "xsq_slicqt_inverse_masked_carry": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp, _vp,
+                                                  _vp, C.c_size_t, _vp]),
     "xsq_comm_load": (C.c_int, [C.c_char_p]),
     "xsq_comm_version": (C.c_int, []),
     "xsq_comm_unique_id": (C.c_int, [_vp]),

@@ -453,9 +453,200 @@ template <class Get> static int acquire_plan(xsq_demixer* d, hipStream_t stream,
     return XSQ_OK;
 }
 
+// ---- the streaming session (Separator.stream): steps on the absolute block grid, pure host arithmetic ------------------
+// Block k = samples [2kh, (2k + 2)h) = second half of slice k + first half of slice k + 1.  Step j closes the blocks
+// [j m, (j + 1) m): it inverts the slices (j m, (j + 1) m] (and slice 0 in step 0) with masks from a CDAE window that reaches
+// `back` slices behind the first and `ahead` beyond the last of them, clipped to the slices the signal has.
+struct StreamStep { int64_t block0; int blocks; int64_t first, w0, w1, trigger; };
+
+// total < 0: the stream is open (no last slice to clip at)
+static bool stream_step(int h, int m, int back, int ahead, int64_t j, int64_t total, StreamStep* o) {
+    const int64_t S = total < 0 ? (1ll << 60) : slices_of(std::max<int64_t>(total, 2 * h + 1), h);      // separator.py:162: at least L/2 + 1 samples
+    const int64_t nblk = total < 0 ? (1ll << 60) : (total + 2 * h - 1) / (2 * h);
+    o->block0 = j * m;
+    if (o->block0 >= nblk) return false;
+    o->blocks = (int)std::min<int64_t>(m, nblk - o->block0);
+    o->first = j == 0 ? 0 : o->block0 + 1;
+    const int64_t last = o->block0 + o->blocks;
+    o->w0 = std::max<int64_t>(0, o->first - back);
+    o->w1 = std::min<int64_t>(S - 1, last + ahead);
+    if (o->w1 - o->w0 < 2) o->w0 = std::max<int64_t>(0, o->w1 - 2);       // the conv stack needs 3 slices
+    o->trigger = (2 * ((j + 1) * m + ahead) + 2) * h;
+    return true;
+}
+
+}  // namespace
+
+struct xsq_stream {
+    xsq_demixer* d = nullptr;
+    int nb = 0, m = 0, back = 0, ahead = 0;
+    int ring = 0;                    // samples per channel of the audio ring
+    int64_t fed = 0, steps = 0;
+    int cur = 0;                     // which of the two carry buffers the next step reads
+    size_t ring_bytes() const { return al256((size_t)2 * nb * ring * 4); }
+    size_t carry_bytes() const { return al256((size_t)8 * nb * 2 * d->plan->h * 4); }
+};
+
+namespace {
+
+// grid (ceil(count / 256), 2 nb): sample i of row r of the block goes to ring position (fed + i) % ring
+__global__ __launch_bounds__(256) void k_ring_write(const float* __restrict__ x, int64_t row_stride, float* __restrict__ ring_buf, int ring,
+                                                     int64_t fed, int count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int r = blockIdx.y;
+    ring_buf[(int64_t)r * ring + (fed + i) % ring] = x[(int64_t)r * row_stride + i];
+}
+
+struct StreamLayout { size_t X, masks, fwd, cdae, inv, total, fwd_bytes, cdae_bytes, inv_bytes; };
+
+// workspace of one step: X arena of the window | masks arena of the window | forward ws | CDAE ws | emission ws
+static int stream_layout(const xsq_stream* st, const xsq_model* Mo, int Sw, int Sn, StreamLayout* L) {
+    xsq_plan* P = st->d->plan;
+    const int B = st->nb;
+    const size_t coefs = (size_t)Sw * P->sumFT;
+    size_t o = 0;
+    L->X = o;     o += al256((size_t)2 * B * coefs * 8);
+    L->masks = o; o += al256((size_t)8 * B * coefs * 4);
+    L->fwd_bytes = xsq_slicqt_forward_workspace(P, 2 * B, (int64_t)(2 * Sw - 3) * P->h);      // (that many samples give Sw slices)
+    L->cdae_bytes = xsq_cdae_workspace(Mo, B, Sw);
+    L->inv_bytes = xsq_slicqt_inverse_carry_workspace(P, 8 * B, 2 * B, Sn);
+    if (!L->fwd_bytes || !L->cdae_bytes || !L->inv_bytes) {
+        const std::string why = xsq_last_error();
+        set_error("xsq_stream_step: nb=%d, a window of %d slices: a stage's workspace query failed (%s)", B, Sw, why.c_str());
+        return XSQ_ERR_ARG;
+    }
+    L->fwd = o;  o += al256(L->fwd_bytes);
+    L->cdae = o; o += al256(L->cdae_bytes);
+    L->inv = o;  o += al256(L->inv_bytes);
+    L->total = o + 256;
+    return XSQ_OK;
+}
+
+static int stream_model_ok(const xsq_stream* st, const xsq_model* Mo, const char* who) {
+    xsq_plan* P = st->d->plan;
+    XSQ_REQUIRE(Mo->sumFT == P->sumFT && Mo->nblocks == P->nblocks, "%s: the model's block table is not the plan's", who);
+    XSQ_REQUIRE(!Mo->wiener_flags, "%s: softmask / residual are options of the Wiener filter, whose statistics span a 5000-frame window: "
+                "a streaming session is mix-phase", who);
+    XSQ_REQUIRE(st->back >= (Mo->causal ? XSQ_STREAM_BACK_CAUSAL : XSQ_STREAM_BACK_OFFLINE), "%s: the masks of a slice depend on %d slices "
+                "behind it (session: %d)", who, Mo->causal ? XSQ_STREAM_BACK_CAUSAL : XSQ_STREAM_BACK_OFFLINE, st->back);
+    return XSQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int xsq_stream_schedule(int64_t N, int L, int hop_slices, int back, int ahead, int64_t* steps, int max_steps) {
+    XSQ_REQUIRE(N >= 0 && L > 0 && L % 4 == 0 && hop_slices >= 1 && back >= 0 && ahead >= 0 && (steps || max_steps <= 0),
+                "xsq_stream_schedule: N=%lld L=%d hop_slices=%d back=%d ahead=%d", (long long)N, L, hop_slices, back, ahead);
+    XSQ_REQUIRE(N / (L / 2) / hop_slices < (1 << 30), "xsq_stream_schedule: N=%lld in steps of %d blocks", (long long)N, hop_slices);
+    StreamStep sp;
+    int64_t j = 0;
+    for (; stream_step(L / 4, hop_slices, back, ahead, j, N, &sp); ++j)
+        if (j < max_steps) {
+            int64_t* o = steps + 6 * j;
+            o[0] = sp.block0; o[1] = sp.blocks; o[2] = sp.first; o[3] = sp.w0; o[4] = sp.w1; o[5] = sp.trigger;
+        }
+    return (int)j;
+}
+
+int xsq_stream_create(xsq_stream** out, xsq_demixer* d, const xsq_model* Mo, int nb, int hop_slices, int back, int ahead) {
+    XSQ_REQUIRE(out && d && Mo, "xsq_stream_create: null argument");
+    XSQ_REQUIRE(nb >= 1 && hop_slices >= 1 && hop_slices <= 4096, "xsq_stream_create: nb=%d hop_slices=%d", nb, hop_slices);
+    XSQ_REQUIRE(ahead >= XSQ_STREAM_AHEAD && back <= 64 && ahead <= 64, "xsq_stream_create: back=%d ahead=%d (the masks of a slice depend on %d "
+                "slices beyond it)", back, ahead, XSQ_STREAM_AHEAD);
+    xsq_stream* st = new xsq_stream();
+    st->d = d; st->nb = nb; st->m = hop_slices; st->back = back; st->ahead = ahead;
+    // from the first sample of the oldest window slice, (2 (j m + 1 - back) - 2) h, to the trigger of the step, (2 ((j + 1) m + ahead) + 2) h
+    st->ring = (2 * (back + ahead + hop_slices) + 2) * d->plan->h;
+    if (int rc = stream_model_ok(st, Mo, "xsq_stream_create")) { delete st; return rc; }
+    *out = st;
+    return XSQ_OK;
+}
+
+int xsq_stream_destroy(xsq_stream* st) { delete st; return XSQ_OK; }
+
+size_t xsq_stream_state_bytes(const xsq_stream* st) { return st ? st->ring_bytes() + 2 * st->carry_bytes() : 0; }
+
+size_t xsq_stream_workspace(const xsq_stream* st, const xsq_model* Mo) {
+    if (!st || !Mo || stream_model_ok(st, Mo, "xsq_stream_workspace")) return 0;
+    size_t need = 0;
+    for (int Sw = 3; Sw <= st->m + st->back + st->ahead + 1; ++Sw) {
+        StreamLayout L;
+        if (stream_layout(st, Mo, Sw, std::min(Sw, st->m + 1), &L)) return 0;
+        need = std::max(need, L.total);
+    }
+    return need;
+}
+
+int64_t xsq_stream_next_trigger(const xsq_stream* st) {
+    if (!st) return XSQ_ERR_ARG;
+    StreamStep sp;
+    stream_step(st->d->plan->h, st->m, st->back, st->ahead, st->steps, -1, &sp);
+    return sp.trigger;
+}
+
+int xsq_stream_push(xsq_stream* st, void* state, const float* x, int64_t row_stride, int64_t count, void* stream) {
+    XSQ_REQUIRE(st && state && x, "xsq_stream_push: null argument");
+    XSQ_REQUIRE(count >= 1 && row_stride >= count, "xsq_stream_push: %lld samples per row, row stride %lld", (long long)count, (long long)row_stride);
+    // the ring holds what the next step's window needs as long as nothing is written past that step's trigger
+    XSQ_REQUIRE(st->fed + count <= xsq_stream_next_trigger(st), "xsq_stream_push: %lld + %lld samples pass the trigger of step %lld (%lld): run "
+                "xsq_stream_step first", (long long)st->fed, (long long)count, (long long)st->steps, (long long)xsq_stream_next_trigger(st));
+    hipLaunchKernelGGL(k_ring_write, dim3((unsigned)((count + 255) / 256), 2 * st->nb), dim3(256), 0, (hipStream_t)stream, x, row_stride,
+                       (float*)state, st->ring, st->fed, (int)count);
+    XSQ_HIP(hipGetLastError());
+    st->fed += count;
+    return XSQ_OK;
+}
+
+int xsq_stream_step(xsq_stream* st, xsq_model* Mo, void* state, const float* x, int64_t row_stride, int64_t count, int64_t total, float* out,
+                    int64_t out_stride, int64_t length, void* ws, size_t ws_bytes, void* stream) {
+    XSQ_REQUIRE(st && Mo && state && out && ws, "xsq_stream_step: null argument");
+    if (int rc = stream_model_ok(st, Mo, "xsq_stream_step")) return rc;
+    XSQ_REQUIRE(count >= 0 && (count == 0 || (x && row_stride >= count)), "xsq_stream_step: %lld new samples per row, row stride %lld",
+                (long long)count, (long long)row_stride);
+    // the samples that release the step ride on its first kernel, which stores them to the ring (xsq_slicqt_forward_ring)
+    XSQ_REQUIRE(count == 0 || (total < 0 && st->fed + count == xsq_stream_next_trigger(st)), "xsq_stream_step: %lld + %lld samples are not the %lld "
+                "that release step %lld", (long long)st->fed, (long long)count, (long long)xsq_stream_next_trigger(st), (long long)st->steps);
+    XSQ_REQUIRE(total < 0 || total == st->fed, "xsq_stream_step: the final length %lld is not the %lld samples fed", (long long)total, (long long)st->fed);
+    xsq_plan* P = st->d->plan;
+    const int h = P->h, B = st->nb;
+    StreamStep sp;
+    XSQ_REQUIRE(stream_step(h, st->m, st->back, st->ahead, st->steps, total, &sp), "xsq_stream_step: step %lld lies behind the last block of %lld "
+                "samples", (long long)st->steps, (long long)total);
+    XSQ_REQUIRE(total >= 0 || st->fed + count >= sp.trigger, "xsq_stream_step: step %lld needs %lld samples (%lld fed)", (long long)st->steps,
+                (long long)sp.trigger, (long long)st->fed);
+    const int64_t want = total < 0 ? (int64_t)sp.blocks * 2 * h : std::min<int64_t>((int64_t)sp.blocks * 2 * h, total - sp.block0 * 2 * h);
+    XSQ_REQUIRE(length == want && out_stride >= length, "xsq_stream_step: step %lld emits %lld samples (length %lld, row stride %lld)",
+                (long long)st->steps, (long long)want, (long long)length, (long long)out_stride);
+    const int Sw = (int)(sp.w1 - sp.w0 + 1), shift = st->steps == 0 ? 0 : 1;
+    const int Sn = (int)(sp.block0 + sp.blocks - sp.first + 1);
+    StreamLayout L;
+    if (int rc = stream_layout(st, Mo, Sw, Sn, &L)) return rc;
+    XSQ_REQUIRE(L.total <= ws_bytes, "xsq_stream_step: workspace too small (%zu needed, %zu given)", L.total, ws_bytes);
+    char* w = (char*)ws;
+    float* X = (float*)(w + L.X);
+    float* masks = (float*)(w + L.masks);
+    float* ring_buf = (float*)state;
+    float* carry[2] = {(float*)((char*)state + st->ring_bytes()), (float*)((char*)state + st->ring_bytes() + st->carry_bytes())};
+    const float *mean, *scale;
+    int split, rc;
+    if ((rc = xsq_model_whitening(Mo, &mean, &scale, &split))) return rc;
+    float* xin = (float*)(w + L.cdae);           // (the head of the CDAE workspace, as in a pass)
+    // the forward transform of the whole window, context slices included, is recomputed every step
+    if ((rc = xsq_slicqt_forward_ring(P, ring_buf, st->ring, 2 * B, sp.w0, Sw, st->fed + count, x, row_stride, count, X, xin, mean, scale, split,
+                                      w + L.fwd, L.fwd_bytes, stream)))
+        return rc;
+    st->fed += count;
+    if ((rc = xsq_cdae_forward_xin(Mo, X, B, Sw, nullptr, masks, w + L.cdae, L.cdae_bytes, stream, 1))) return rc;
+    if ((rc = xsq_slicqt_inverse_masked_carry(P, masks, X, 8 * B, 2 * B, Sw, (int)(sp.first - sp.w0), Sn, shift, length, out, out_stride,
+                                              carry[st->cur], carry[1 - st->cur], w + L.inv, L.inv_bytes, stream)))
+        return rc;
+    st->cur = 1 - st->cur;
+    st->steps += 1;
+    return XSQ_OK;
+}
 
 int xsq_demixer_create(xsq_demixer** out, xsq_plan* plan) {
     XSQ_REQUIRE(out && plan, "xsq_demixer_create: null argument");

@@ -298,13 +298,24 @@ __device__ __forceinline__ void fft_steps_2_3(float2* Z, const float2* __restric
 //           (lanes 256..511), both holding the column's 43 inputs: the longest serial stage of the transform is
 //           halved, steps 2 / 3 take 2 rounds instead of 3, and a CU holds 16 waves instead of 8 -- the kernel is
 //           bound by dependent LDS / memory round trips, not by issue slots (27 % VALU utilisation measured).
-template <int NT, bool PK = false>
+// RING (the streaming session, xsq_stream_step): x is a ring of `ring` samples per channel that holds absolute sample i at
+//           i % ring; row (bc, s) is the slice of ABSOLUTE index s0 + s, and only samples before 0 and at or after n (the
+//           samples fed so far, or the final length) read as zero -- not everything outside a call's own [0, n).  The samples
+//           from new0 on are not in the ring yet: they are read from xnew (row bc at bc * new_stride, sample new0 first) and
+//           stored to the ring by the slice whose second half holds them -- the push that releases a step rides on the step's
+//           first kernel (their ring slots held samples older than any slice of the window reads).  A template parameter: the
+//           instantiations of every other entry point keep their code.
+template <int NT, bool PK = false, bool RING = false>
 __global__ __launch_bounds__(NT, NT / 128) void k_slice_rfft(const float* __restrict__ x, const float* __restrict__ tw,
                                                               const FftTables T, float2* __restrict__ U,
                                                               int S, int64_t n, int h,
                                                               const int64_t* __restrict__ xrows = nullptr,
-                                                              const float* const* __restrict__ xslot = nullptr) {
+                                                              const float* const* __restrict__ xslot = nullptr,
+                                                              int64_t s0 = 0, int ring = 0, float* ring_w = nullptr,
+                                                              const float* __restrict__ xnew = nullptr, int64_t new0 = 0,
+                                                              int64_t new_stride = 0) {
 #pragma clang fp contract(off)          // fused multiply-adds only where written (fmaf): same bits from every instantiation
+    static_assert(!RING || NT == 512, "the ring form exists for the 512-thread kernel");
     __shared__ float2 Z[FFT_N];
     __shared__ float2 w2s[FFT_R2 * FFT_R3];
     const int tid = threadIdx.x;
@@ -315,8 +326,8 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_rfft(const float* __rest
     // instead (one uniform 8-byte load) -- a captured HIP graph then follows the caller's tensor from replay to replay
     // without a copy into a static input buffer (Separator.forward_graphed).
     const float* xb = xslot ? *xslot : x;
-    const float* xr = xb + (xrows ? xrows[bc] : (int64_t)bc * n);
-    const int64_t i0 = (int64_t)(2 * s - 2) * h;
+    const float* xr = RING ? xb + (int64_t)bc * ring : xb + (xrows ? xrows[bc] : (int64_t)bc * n);
+    const int64_t i0 = RING ? (2 * (s0 + s) - 2) * h : (int64_t)(2 * s - 2) * h;
     const int part = tid >> 8, m = tid & 255;            // wave-uniform part
     const float2* tw2 = reinterpret_cast<const float2*>(tw);
     if constexpr (NT == 256) {
@@ -353,7 +364,9 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_rfft(const float* __rest
         // flight together), then both wave groups read the columns they share from there
         constexpr int NLD = (FFT_N + NT - 1) / NT;
         float2 xv[NLD], wv[NLD];
-        const bool inner = i0 >= 0 && i0 + FFT_L <= n;      // workgroup-uniform
+        const bool inner = !RING && i0 >= 0 && i0 + FFT_L <= n;      // workgroup-uniform
+        // ring position of the slice's first sample (ring > FFT_L: one wrap at most inside a slice)
+        const int rb = RING ? (int)(((i0 % ring) + ring) % ring) : 0;
 #pragma unroll
         for (int it = 0; it < NLD; ++it) {
             const int p2 = tid + NT * it;
@@ -361,7 +374,21 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_rfft(const float* __rest
             wv[it] = tw2[pc];
             const int64_t i = i0 + 2 * pc;
             if (inner) { xv[it].x = xr[i]; xv[it].y = xr[i + 1]; }
-            else {
+            else if constexpr (RING) {
+                int ra = rb + 2 * pc, rc = ra + 1;
+                ra = ra >= ring ? ra - ring : ra;
+                rc = rc >= ring ? rc - ring : rc;
+                const bool na = i >= new0 && i < n, nc = i + 1 >= new0 && i + 1 < n;        // (new0 = n: none)
+                const float* xn = xnew + (int64_t)bc * new_stride - new0;
+                const float xa = na ? xn[i] : xr[ra], xc = nc ? xn[i + 1] : xr[rc];
+                xv[it].x = (i >= 0 && i < n) ? xa : 0.f;
+                xv[it].y = (i + 1 >= 0 && i + 1 < n) ? xc : 0.f;
+                if (2 * pc >= 2 * h) {                 // second half (2h is even: both samples of the pair)
+                    float* rw = ring_w + (int64_t)bc * ring;
+                    if (na) rw[ra] = xa;
+                    if (nc) rw[rc] = xc;
+                }
+            } else {
                 const int64_t ia = i < 0 ? 0 : (i >= n ? n - 1 : i), ib = i + 1 < 0 ? 0 : (i + 1 >= n ? n - 1 : i + 1);
                 const float xa = xr[ia], xb = xr[ib];
                 xv[it].x = (i >= 0 && i < n) ? xa : 0.f;
@@ -441,15 +468,28 @@ struct OlaArgs {
     int64_t length;
 };
 
+// The overlap-add of a streaming step (CARRY, xsq_stream_step): the launch inverts the S NEW slices of a step only.  Slice s of
+// the launch lies at position s + shift of the step; the first half of position p belongs to output block p - 1, the second
+// half to block p, a block is 2h samples.  Blocks below nblk go to y (row bc at bc * out_stride, `length` samples of it),
+// block nblk -- the second half of the last slice -- becomes the carry of the next step, and with shift = 1 block 0 is the
+// first half of slice 0 plus carry_in, the half the previous step left.  Two buffers: a launch never reads the carry it writes.
+struct CarryArgs {
+    const float* carry_in;
+    float* carry_out;
+    int64_t out_stride;
+    int shift, nblk;
+};
+
 
 // SHORT: the short bands are synthesised inside this kernel (ShortSched; an A/B switch that measured slower) -- a template
 // parameter, so that the default instantiation carries neither that code nor its registers (as a run-time branch it
 // pushed the gather prologue of the default path over the 128-register cap: spilled loads, each waited for in turn).
 // FAST4: the four-phases-in-flight gather (see below); chosen by the host when the plan's phases fit.
-template <int NT, bool PK = false, bool SHORT = false, bool FAST4 = false>
+// CARRY: the overlap-add of a streaming step (CarryArgs) instead of the one of a whole call; a template parameter like the others.
+template <int NT, bool PK = false, bool SHORT = false, bool FAST4 = false, bool CARRY = false>
 __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __restrict__ Zrow, const GatherSched G,
                                                       const FftTables T, const OlaArgs O, const ShortSched SS,
-                                                      const ShortIn SI) {
+                                                      const ShortIn SI, const CarryArgs C = CarryArgs{}) {
 #pragma clang fp contract(off)          // fused multiply-adds only where written (fmaf): same bits from every instantiation
     __shared__ float2 Z[FFT_N + 1];        // bins 0..N while gathering, then the complex sequence
     __shared__ float2 w2s[FFT_R2 * FFT_R3];
@@ -726,6 +766,48 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __re
     if (!(XSQ_ABLATE & 64)) fft_steps_2_3<+1, NT, PK>(Z, T.w1, w2s, tid);
     XSQ_STAMP(4);
     if (XSQ_ABLATE & 128) return;
+    if constexpr (CARRY) {
+        // even slices of the launch store, odd ones add (as below); the sums are those of the whole call in either order
+        // (all loads of the partner sums first, then all stores, as in the interior path below)
+        float* const yo = O.y + (int64_t)bc * C.out_stride;
+        const int h2 = 2 * O.h;
+        float2 prev[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int nn = tid + NT * it;
+            const bool lo = 2 * nn < h2;
+            const int blk = s + C.shift - (lo ? 1 : 0), off = 2 * nn - (lo ? 0 : h2);
+            const int64_t ia = (int64_t)blk * h2 + off;
+            prev[it] = make_float2(0.f, 0.f);
+            if (nn >= FFT_N || blk < 0 || blk >= C.nblk) continue;
+            if (blk == 0 && C.shift && lo) {           // the half the previous step left (slice 0 of the launch is even: a store)
+                const float* c = C.carry_in + (int64_t)bc * h2 + off;
+                prev[it] = make_float2(c[0], c[1]);
+            } else if (lo ? add_lo : add_hi) {
+                if (ia < O.length) prev[it].x = yo[ia];
+                if (ia + 1 < O.length) prev[it].y = yo[ia + 1];
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int nn = tid + NT * it;
+            if (nn >= FFT_N) break;
+            const float2 v = Z[fft_pos(nn)];
+            const bool lo = 2 * nn < h2;
+            const int blk = s + C.shift - (lo ? 1 : 0), off = 2 * nn - (lo ? 0 : h2);
+            if (blk < 0) continue;
+            if (blk >= C.nblk) {                       // the second half of the last slice: never added to
+                float* c = C.carry_out + (int64_t)bc * h2 + off;
+                c[0] = v.x; c[1] = v.y;
+                continue;
+            }
+            const bool sum = (blk == 0 && C.shift && lo) || (lo ? add_lo : add_hi);
+            const int64_t ia = (int64_t)blk * h2 + off;
+            if (ia < O.length) yo[ia] = sum ? prev[it].x + v.x : v.x;
+            if (ia + 1 < O.length) yo[ia + 1] = sum ? prev[it].y + v.y : v.y;
+        }
+        return;
+    }
     if (interior) {
         // interior slice, 8-byte aligned: all loads of the partner sums first, then all stores
         float2 prev[NIT];

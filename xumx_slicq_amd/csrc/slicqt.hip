@@ -40,18 +40,31 @@ void set_error(const char* fmt, ...) {
 // streaming kernels
 // ------------------------------------------------------------------------------------------
 // grid (ceil(L/256), BC*S).  Reads x once (each sample lands in two slices), writes seg once.
+// ring > 0 (the streaming session, xsq_slicqt_forward_ring): x is a ring of `ring` samples per channel holding absolute sample
+// i at i % ring, row (bc, s) is the slice of absolute index s0 + s, and n counts the samples of the whole stream so far; those
+// from new0 on are read from xnew and stored to the ring by the slice whose second half holds them (k_slice_rfft, RING).
 __global__ __launch_bounds__(256) void k_slice_window(const float* __restrict__ x,
                                                        const float* __restrict__ tw,
                                                        float* __restrict__ seg, int S, int64_t n, int L,
                                                        int h, const int64_t* __restrict__ xrows = nullptr,
-                                                       const float* const* __restrict__ xslot = nullptr) {
+                                                       const float* const* __restrict__ xslot = nullptr,
+                                                       int64_t s0 = 0, int ring = 0, float* ring_w = nullptr,
+                                                       const float* __restrict__ xnew = nullptr, int64_t new0 = 0,
+                                                       int64_t new_stride = 0) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= L) return;
     const int row = blockIdx.y;  // bc*S + s
     const int bc = row / S, s = row - bc * S;
-    const int64_t i = (int64_t)(2 * s - 2) * h + p;
+    const int64_t i = (2 * (s0 + s) - 2) * h + p;
     float v = 0.f;
-    if (i >= 0 && i < n) v = tw[p] * (xslot ? *xslot : x)[(xrows ? xrows[bc] : (int64_t)bc * n) + i];
+    if (ring) {
+        if (i >= 0 && i < n) {
+            const int64_t r = (int64_t)bc * ring + i % ring;
+            const float xv = i >= new0 ? xnew[(int64_t)bc * new_stride + i - new0] : x[r];
+            if (i >= new0 && p >= 2 * h) ring_w[r] = xv;
+            v = tw[p] * xv;
+        }
+    } else if (i >= 0 && i < n) v = tw[p] * (xslot ? *xslot : x)[(xrows ? xrows[bc] : (int64_t)bc * n) + i];
     seg[(int64_t)row * L + p] = v;
 }
 
@@ -92,6 +105,51 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float* __restrict__ s
     float v = base[(int64_t)s0 * L + p1 + 2 * h];
     if (s0 + 1 < S) v += base[(int64_t)(s0 + 1) * L + p1];
     y[(row_off ? row_off[bc] : (int64_t)bc * length) + i] = v;
+}
+
+// The overlap-add of a streaming step over the S new slices of the step (CarryArgs, slice_fft.h): grid (ceil((nblk + 1) * 2h
+// / 256), BC).  Block b of the step = second half of position b (slice b - shift, or the carried half when there is none) +
+// first half of position b + 1, summed in the order of k_overlap_add; block nblk is the new carry.
+__global__ __launch_bounds__(256) void k_overlap_add_carry(const float* __restrict__ seg, float* __restrict__ y, const CarryArgs C,
+                                                            int S, int64_t length, int L, int h) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int h2 = 2 * h;
+    if (i >= (C.nblk + 1) * h2) return;
+    const int bc = blockIdx.y;
+    const int blk = i / h2, p1 = i - blk * h2;
+    const float* base = seg + (int64_t)bc * S * L;
+    const int sa = blk - C.shift, sb = sa + 1;      // the slices whose second / first half meet in this block
+    float v = sa >= 0 ? base[(int64_t)sa * L + p1 + h2] : C.carry_in[(int64_t)bc * h2 + p1];
+    if (blk >= C.nblk) { C.carry_out[(int64_t)bc * h2 + p1] = v; return; }
+    if (sb < S) v += base[(int64_t)sb * L + p1];
+    if (i < length) y[(int64_t)bc * C.out_stride + i] = v;
+}
+
+// Slices [s0, s0 + Sdst) of an arena of Ssrc slices as an arena of Sdst slices (the new slices of a streaming step out of the
+// window the CDAE ran on): block j holds [C][F][S][T] entries of cplx floats from C * S * cum_j on.  grid (ceil(per / 1024), nblocks, C).
+constexpr int TAKE_MAX_BLOCKS = 256;
+struct TakeArgs {
+    const float* src[2];                // the complex mix arena (C[0] channels), the real mask arena (C[1] channels): one launch
+    float* dst[2];
+    int C[2];
+    int Ssrc, Sdst, s0;
+    int cum[TAKE_MAX_BLOCKS + 1];       // coefficients per channel-slice before block j
+    int T[TAKE_MAX_BLOCKS];
+};
+
+// grid (ceil(2 * per / 1024), nblocks, C[0] + C[1])
+__global__ __launch_bounds__(256) void k_take_slices(TakeArgs a) {
+    const int j = blockIdx.y;
+    const int which = (int)blockIdx.z < a.C[0] ? 0 : 1, ch = blockIdx.z - (which ? a.C[0] : 0), C = a.C[which], cplx = which ? 1 : 2;
+    const int Tc = a.T[j] * cplx;                                    // floats of one (f, s) row (% 4 == 0: T % 4 == 0)
+    const int FT = (a.cum[j + 1] - a.cum[j]) * cplx;                 // F * Tc
+    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e >= (int64_t)a.Sdst * FT) return;
+    const int row = (int)(e / Tc), t = (int)(e - (int64_t)row * Tc); // row = f * Sdst + s
+    const int f = row / a.Sdst, s = row - f * a.Sdst;
+    const float* src = a.src[which] + ((int64_t)C * a.cum[j] * cplx + (int64_t)ch * FT) * a.Ssrc + ((int64_t)f * a.Ssrc + a.s0 + s) * Tc + t;
+    float* dst = a.dst[which] + ((int64_t)C * a.cum[j] * cplx + (int64_t)ch * FT) * a.Sdst + e;
+    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -939,14 +997,46 @@ int xsq_slicqt_forward_rows(xsq_plan* P, const float* x, const int64_t* x_rows, 
     return xsq_slicqt_forward_rows_indirect(P, x, nullptr, x_rows, BC, n, n_pad, coef, xin, mean, scale, split, ws, ws_bytes, stream_);
 }
 
+// S slices per channel from absolute slice s0 on; ring > 0: x is the ring of a streaming session (k_slice_rfft, RING)
+struct RingNew { const float* x; int64_t first, stride; };       // the samples from `first` on, not yet in the ring (row bc at x + bc * stride)
+static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n, int S, int64_t s0,
+                        int ring, float* coef, float* xin, const float* mean, const float* scale, int split, void* ws, size_t ws_bytes,
+                        void* stream_, RingNew fresh = RingNew{nullptr, 0, 0});
+
 int xsq_slicqt_forward_rows_indirect(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n,
                                      int64_t n_pad, float* coef, float* xin, const float* mean, const float* scale, int split,
                                      void* ws, size_t ws_bytes, void* stream_) {
     XSQ_REQUIRE(P && (x || x_slot) && coef && ws, "xsq_slicqt_forward: null argument");
-    XSQ_REQUIRE(!xin || (mean && scale), "xsq_slicqt_forward_xin: xin needs the mean / scale tables");
     XSQ_REQUIRE(BC > 0 && n > 0 && n_pad >= n, "xsq_slicqt_forward: BC=%d n=%lld n_pad=%lld", BC, (long long)n, (long long)n_pad);
+    // the kernels read zeros outside [0, n): padding is a slice count
+    return forward_impl(P, x, x_slot, x_rows, BC, n, xsq_plan_num_slices(P, n_pad), 0, 0, coef, xin, mean, scale, split, ws, ws_bytes, stream_);
+}
+
+int xsq_slicqt_forward_ring(xsq_plan* P, float* ring, int ring_len, int BC, int64_t first_slice, int S, int64_t n, const float* x_new,
+                            int64_t new_stride, int64_t new_count, float* coef, float* xin, const float* mean, const float* scale, int split,
+                            void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(P && ring && coef && ws, "xsq_slicqt_forward_ring: null argument");
+    XSQ_REQUIRE(new_count >= 0 && new_count <= n && (new_count == 0 || (x_new && new_stride >= new_count)),
+                "xsq_slicqt_forward_ring: %lld new samples of %lld, row stride %lld", (long long)new_count, (long long)n, (long long)new_stride);
+    // every new sample lies in the second half of one slice of the call, which stores it to the ring
+    XSQ_REQUIRE(new_count == 0 || ((n - new_count) / (2 * P->h) >= first_slice && (n - 1) / (2 * P->h) < first_slice + S),
+                "xsq_slicqt_forward_ring: the new samples [%lld, %lld) are not covered by the second halves of the slices [%lld, %lld)",
+                (long long)(n - new_count), (long long)n, (long long)first_slice, (long long)(first_slice + S));
+    XSQ_REQUIRE(BC > 0 && S >= 2 && first_slice >= 0 && n > 0, "xsq_slicqt_forward_ring: BC=%d S=%d first_slice=%lld n=%lld", BC, S,
+                (long long)first_slice, (long long)n);
+    // every sample a row reads is one of the last ring_len fed, and a slice wraps at most once
+    XSQ_REQUIRE(ring_len > P->L && (2 * (first_slice + S - 1) + 2) * P->h - std::max<int64_t>(0, (2 * first_slice - 2) * P->h) <= ring_len,
+                "xsq_slicqt_forward_ring: %d slices of %d samples do not fit a ring of %d", S, P->L, ring_len);
+    XSQ_REQUIRE(first_slice + S < (1ll << 40), "xsq_slicqt_forward_ring: slice index %lld", (long long)first_slice);
+    return forward_impl(P, ring, nullptr, nullptr, BC, n, S, first_slice, ring_len, coef, xin, mean, scale, split, ws, ws_bytes, stream_,
+                        RingNew{x_new, n - new_count, new_stride});
+}
+
+static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n, int S, int64_t s0,
+                        int ring, float* coef, float* xin, const float* mean, const float* scale, int split, void* ws, size_t ws_bytes,
+                        void* stream_, RingNew fresh) {
+    XSQ_REQUIRE(!xin || (mean && scale), "xsq_slicqt_forward_xin: xin needs the mean / scale tables");
     hipStream_t stream = (hipStream_t)stream_;
-    const int S = xsq_plan_num_slices(P, n_pad);        // the kernels read zeros outside [0, n): padding is a slice count
     const int rows = BC * S;
     XSQ_REQUIRE(S >= 2, "xsq_slicqt_forward: signal too short");
     XSQ_REQUIRE((int64_t)BC * S <= 65535, "xsq_slicqt_forward: BC*S=%lld rows exceed one launch", (long long)BC * S);
@@ -972,11 +1062,13 @@ int xsq_slicqt_forward_rows_indirect(xsq_plan* P, const float* x, const float* c
 #if XSQ_PACKED_FFT_KERNELS
         if (P->packed_fft) kernel = k_slice_rfft<512, true>;
 #endif
-        hipLaunchKernelGGL(kernel, dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot);
+        if (ring) kernel = k_slice_rfft<512, false, true>;
+        hipLaunchKernelGGL(kernel, dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot, s0, ring,
+                           const_cast<float*>(x), fresh.x, fresh.first, fresh.stride);
     } else {
         { XSQ_PROF("slice_window", stream);
         hipLaunchKernelGGL(k_slice_window, dim3((P->L + 255) / 256, rows), dim3(256), 0, stream, x, P->d_tw, seg,
-                           S, n, P->L, P->h, x_rows, x_slot); }
+                           S, n, P->L, P->h, x_rows, x_slot, s0, ring, const_cast<float*>(x), fresh.x, fresh.first, fresh.stride); }
         { XSQ_PROF("rfft_L", stream); rc = run_fft(f, seg, U, fwork, stream); }
         if (rc) return rc;
     }
@@ -1011,8 +1103,9 @@ int xsq_slicqt_inverse(xsq_plan* P, const float* coef, int BC, int S, int64_t le
     return xsq_slicqt_inverse_rows(P, coef, BC, S, length, y, nullptr, ws, ws_bytes, stream_);
 }
 
+// carry != nullptr: the S slices are the new ones of a streaming step and `y` takes its blocks (CarryArgs, slice_fft.h)
 static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int BCx, int BC, int S, int64_t length, float* y,
-                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_);
+                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry = nullptr);
 
 int xsq_slicqt_inverse_rows(xsq_plan* P, const float* coef, int BC, int S, int64_t length, float* y,
                             const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_) {
@@ -1027,11 +1120,11 @@ int xsq_slicqt_inverse_masked(xsq_plan* P, const float* masks, const float* mix,
 }
 
 static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int BCx, int BC, int S, int64_t length, float* y,
-                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_) {
+                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry) {
     XSQ_REQUIRE(P && coef && y && ws, "xsq_slicqt_inverse: null argument");
-    XSQ_REQUIRE(BC > 0 && S >= 2 && length > 0, "xsq_slicqt_inverse: BC=%d S=%d length=%lld", BC, S,
+    XSQ_REQUIRE(BC > 0 && S >= (carry ? 1 : 2) && length > 0, "xsq_slicqt_inverse: BC=%d S=%d length=%lld", BC, S,
                 (long long)length);
-    XSQ_REQUIRE(length <= (int64_t)2 * S * P->h, "xsq_slicqt_inverse: length %lld exceeds the %d slices",
+    XSQ_REQUIRE(length <= (int64_t)2 * (carry ? carry->nblk : S) * P->h, "xsq_slicqt_inverse: length %lld exceeds the %d slices",
                 (long long)length, S);
     XSQ_REQUIRE((int64_t)BC * S <= 65535, "xsq_slicqt_inverse: BC*S=%lld rows exceed one launch", (long long)BC * S);
     // the band kernels carry arena offsets in 32 bits (band_dft4.h: xoff / moff; the mix arena is the smaller one)
@@ -1064,7 +1157,7 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
         if ((rc = launch_dft4<false>(P, a4, rows, mask ? BCx * S : 0, stream))) return rc;
     }
     // short bands: inside k_slice_irfft when the plan allows it, else dense GEMM + Z round trip
-    const bool inl = lds_fft(P) && P->band_radix4 && P->short_inline && P->short_n1 > 0;
+    const bool inl = lds_fft(P) && P->band_radix4 && P->short_inline && P->short_n1 > 0 && !carry;
     if (tt.ntiles && !inl) { XSQ_PROF("band_synthesis_gemm", stream);
     hipLaunchKernelGGL((grouped_gemm_kernel<BandInvOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
@@ -1091,10 +1184,12 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
 #if XSQ_PACKED_FFT_KERNELS
         if (P->packed_fft && !inl) kernel = fast4 ? k_slice_irfft<512, true, false, true> : k_slice_irfft<512, true>;
 #endif
+        if (carry) kernel = fast4 ? k_slice_irfft<512, false, false, true, true> : k_slice_irfft<512, false, false, false, true>;
         for (int parity = 0; parity < 2; ++parity) {
             const int nsl = (S + 1 - parity) / 2;
+            if (!nsl) continue;                   // (a step of one slice has no odd one)
             OlaArgs O{y, row_offsets, S, P->h, parity, length};
-            hipLaunchKernelGGL(kernel, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI);
+            hipLaunchKernelGGL(kernel, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI, carry ? *carry : CarryArgs{});
         }
         XSQ_HIP(hipGetLastError());
         return XSQ_OK;
@@ -1105,11 +1200,58 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
         { XSQ_PROF("irfft_L", stream); rc = run_fft(f, fr, seg, fwork, stream); }
         if (rc) return rc;
     }
-    { XSQ_PROF("overlap_add", stream);
+    if (carry) { XSQ_PROF("overlap_add_carry", stream);
+    hipLaunchKernelGGL(k_overlap_add_carry, dim3((unsigned)(((carry->nblk + 1) * 2 * P->h + 255) / 256), BC), dim3(256), 0, stream, seg, y,
+                       *carry, S, length, P->L, P->h); }
+    else { XSQ_PROF("overlap_add", stream);
     hipLaunchKernelGGL(k_overlap_add, dim3((unsigned)((length + 255) / 256), BC), dim3(256), 0, stream, seg, y,
                        row_offsets, S, length, P->L, P->h); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
+}
+
+// ---- the emission of a streaming step: masked inverse of the new slices only, overlap-added onto the carried half ----
+size_t xsq_slicqt_inverse_carry_workspace(xsq_plan* P, int BC, int BCx, int S) {
+    if (!P || BC <= 0 || BCx <= 0 || S <= 0) return 0;
+    const size_t inv = xsq_slicqt_inverse_workspace(P, BC, S);
+    if (!inv) return 0;
+    return al256((size_t)BCx * S * P->sumFT * 8) + al256((size_t)BC * S * P->sumFT * 4) + inv;
+}
+
+int xsq_slicqt_inverse_masked_carry(xsq_plan* P, const float* masks, const float* mix, int BC, int BCx, int S_window, int first, int S,
+                                    int shift, int64_t length, float* y, int64_t y_stride, const float* carry_in, float* carry_out,
+                                    void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(P && masks && mix && y && carry_out && ws, "xsq_slicqt_inverse_masked_carry: null argument");
+    XSQ_REQUIRE(BCx > 0 && BC > 0 && BC % BCx == 0, "xsq_slicqt_inverse_masked_carry: %d mix channels do not divide %d mask channels", BCx, BC);
+    XSQ_REQUIRE(S >= 1 && first >= 0 && first + S <= S_window, "xsq_slicqt_inverse_masked_carry: slices [%d, %d) of a window of %d", first,
+                first + S, S_window);
+    XSQ_REQUIRE(shift == 0 || (shift == 1 && carry_in), "xsq_slicqt_inverse_masked_carry: shift=%d (0: the first slice of the stream is among "
+                "these; 1: its predecessor's second half is carry_in)", shift);
+    const int nblk = S - 1 + shift;              // S slices at positions shift .. S - 1 + shift close the blocks 0 .. nblk - 1
+    XSQ_REQUIRE(nblk >= 1 && length >= 1 && length <= (int64_t)nblk * 2 * P->h && y_stride >= length,
+                "xsq_slicqt_inverse_masked_carry: %lld samples of %d blocks, row stride %lld", (long long)length, nblk, (long long)y_stride);
+    XSQ_REQUIRE(P->nblocks <= TAKE_MAX_BLOCKS && BC + BCx <= 65535, "xsq_slicqt_inverse_masked_carry: %d band blocks, %d channels", P->nblocks, BC);
+    const size_t need = xsq_slicqt_inverse_carry_workspace(P, BC, BCx, S);
+    XSQ_REQUIRE(need && need <= ws_bytes, "xsq_slicqt_inverse_masked_carry: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    char* w = (char*)ws;
+    float* Xn = (float*)w; w += al256((size_t)BCx * S * P->sumFT * 8);
+    float* Mn = (float*)w; w += al256((size_t)BC * S * P->sumFT * 4);
+    TakeArgs a;
+    a.Ssrc = S_window; a.Sdst = S; a.s0 = first;
+    int64_t per_max = 0;
+    for (int j = 0; j < P->nblocks; ++j) {
+        a.cum[j] = (int)P->blocks[j].cum; a.T[j] = P->blocks[j].T;
+        per_max = std::max<int64_t>(per_max, (int64_t)S * P->blocks[j].F * P->blocks[j].T);
+    }
+    a.cum[P->nblocks] = (int)P->sumFT;
+    a.src[0] = mix; a.dst[0] = Xn; a.C[0] = BCx;
+    a.src[1] = masks; a.dst[1] = Mn; a.C[1] = BC;
+    { XSQ_PROF("take_slices", stream);
+    hipLaunchKernelGGL(k_take_slices, dim3((unsigned)((2 * per_max / 4 + 255) / 256), P->nblocks, BCx + BC), dim3(256), 0, stream, a); }
+    XSQ_HIP(hipGetLastError());
+    const CarryArgs c{carry_in, carry_out, y_stride, shift, nblk};
+    return inverse_impl(P, Xn, Mn, BCx, BC, S, length, y, nullptr, w, ws_bytes - (size_t)(w - (char*)ws), stream_, &c);
 }
 
 // ---- remix: R gain-weighted mixes of the four targets through R (not four) inverse transforms ----

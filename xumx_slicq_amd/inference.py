@@ -240,6 +240,26 @@ def _overlapped_one(audio, separator, rate, device, overlapped):
     return separator.to_dict(estimates), time.time() - start_time
 
 
+def stream_blocks(audio, separator, block_samples: int, hop_slices: int = 1):
+    """``audio`` (nb_samples, 2, N) pushed through a ``Separator.stream`` session in blocks of ``block_samples``: (4, nb_samples, 2, N),
+    the returns of every ``feed`` and of ``flush`` joined."""
+    session = separator.stream(audio.shape[0], hop_slices)
+    parts = [session.feed(audio[..., p:p + block_samples]) for p in range(0, audio.shape[-1], block_samples)]
+    return torch.cat(parts + [session.flush()], dim=-1)
+
+
+def _stream_one(audio, separator, rate, device, block_samples, hop_slices):
+    """``separate`` through a streaming session: ({target: (nb_samples, 2, T)}, seconds)."""
+    if device:
+        audio = audio.to(device)
+    audio = xaudio.preprocess_audio(audio, rate, separator.sample_rate)
+    torch.cuda.synchronize(audio.device)
+    start_time = time.time()
+    estimates = stream_blocks(audio, separator, block_samples, hop_slices)
+    torch.cuda.synchronize(audio.device)
+    return separator.to_dict(estimates), time.time() - start_time
+
+
 def overlapped_option(args):
     """(segment, overlap) when --segment or --overlap was given (the other takes its default), else None."""
     if args.segment is None and args.overlap is None:
@@ -267,6 +287,23 @@ def parse_args(p: argparse.ArgumentParser, argv=None):
             p.error(f"--segment {args.segment}: a positive number of seconds")
         if args.overlap is not None and not 0 <= args.overlap < 1:
             p.error(f"--overlap {args.overlap}: a fraction of a second in [0, 1)")
+    if args.hop_slices is not None and args.stream is None:
+        p.error("--hop-slices counts the blocks of a --stream step; it needs --stream")
+    if args.stream is not None:
+        if args.stream < 1:
+            p.error(f"--stream {args.stream}: a positive number of samples per block")
+        if args.hop_slices is not None and args.hop_slices < 1:
+            p.error(f"--hop-slices {args.hop_slices}: at least one block per step")
+        if args.remix:
+            p.error("--stream returns the four stems block by block; gains are not built into the session (weight the stems instead of --remix)")
+        if args.segment is not None or args.overlap is not None:
+            p.error("--stream has no chunk joints to fade; --segment / --overlap are for whole tracks")
+        for opt in ("softmask", "residual"):
+            if getattr(args, opt):
+                p.error(f"--{opt} is an option of the Wiener filter, which cannot stream; --stream is mix-phase")
+        if not args.realtime and (args.niter is None or args.niter >= 1):
+            p.error("--stream is mix-phase: the Wiener-EM of the offline model (--niter >= 1, its default) spans 5000-frame windows and "
+                    "cannot stream; use --realtime or --niter 0")
     return args
 
 
@@ -299,6 +336,12 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--overlap", type=float, default=None, metavar="FRACTION",
                    help="overlap of consecutive segments as a fraction of a second, in [0, 1) (default 0.1 once --segment or "
                         "--overlap is given); not with --remix")
+    p.add_argument("--stream", type=int, default=None, metavar="BLOCK_SAMPLES",
+                   help="push each file through a streaming session (Separator.stream) in blocks of this many samples and write the "
+                        "four stems it returns; one track at a time; --realtime or --niter 0 only, not with --remix, --segment, "
+                        "--overlap, --softmask, --residual")
+    p.add_argument("--hop-slices", type=int, default=None, metavar="M",
+                   help="blocks of sllen / 2 samples per step of the --stream session (default 1)")
     return p
 
 
@@ -324,7 +367,7 @@ def inference_main(argv=None):
             p.error(str(e))
     out_dir = Path(args.output_dir)
     wavs = sorted(Path(args.input_dir).glob(f"*{args.ext}"))
-    if not args.serial:
+    if not args.serial and args.stream is None:
         t0 = time.time()
         done = demix_directory(separator, wavs, out_dir, device=args.device, remix=remix, overlapped=overlapped)
         wall = time.time() - t0
@@ -335,7 +378,9 @@ def inference_main(argv=None):
     tot, n = 0.0, 0
     for wav in wavs:
         sig, rate = xaudio.load_audio(str(wav))
-        if overlapped is not None:
+        if args.stream is not None:
+            estimates, dt = _stream_one(sig, separator, rate, args.device, args.stream, args.hop_slices or 1)
+        elif overlapped is not None:
             estimates, dt = _overlapped_one(sig, separator, rate, args.device, overlapped)
         elif remix is None:
             estimates, dt = separate(sig, separator, rate=rate, device=args.device)

@@ -12,6 +12,7 @@ import ctypes as C
 import json
 import os
 import sys
+import weakref
 from collections import namedtuple
 from pathlib import Path
 from typing import Optional, Tuple, Union
@@ -53,6 +54,10 @@ _ABSENT = object()
 # differs from the current call in ``invalidating`` is stale
 GraphKey = namedtuple("GraphKey", "device coexist invalidating")
 _Native = namedtuple("_Native", "dev model d main cs max_stack cap")      # ``Separator._native_call``
+# The dependency window of a mask in mix-phase mode, in slices (XSQ_STREAM_* of the C header): the mask of slice s
+# reads the coefficients of s - back .. s + ahead, back by the conv type -- the causal stack's first layer is left-padded.
+STREAM_BACK = {True: 3, False: 2}          # causal -> back
+STREAM_AHEAD = 2
 
 
 def switch(owner, name: str):
@@ -376,14 +381,18 @@ class Separator(nn.Module):
         self.xumx_model.wiener_options()
         if audio.dim() != 3 or audio.shape[1] != 2 or audio.device.type != "cuda" or audio.shape[-1] < 1:
             return None
-        if not (switch(self, "native") and switch(self, "batch_chunks") and switch(self, "pass_streams") == 1
-                and switch(self, "fuse_whiten") and switch(self, "fuse_phasemix")
-                and switch(self.xumx_model, "wiener_masked") and switch(self.xumx_model, "niter_method") == "auto"):
+        if not self._native_switches():
             return None
         modes = {bool(b.realtime) for b in self.xumx_model.sliced_umx}
         if len(modes) != 1:
             return None
         return 0 if modes.pop() else self.niter
+
+    def _native_switches(self) -> bool:
+        """Every A/B switch stands at its default: the native entry points serve the call."""
+        return bool(switch(self, "native") and switch(self, "batch_chunks") and switch(self, "pass_streams") == 1
+                    and switch(self, "fuse_whiten") and switch(self, "fuse_phasemix")
+                    and switch(self.xumx_model, "wiener_masked") and switch(self.xumx_model, "niter_method") == "auto")
 
     def _native_ws(self, dev: torch.device, stream_ptr: int, which: str, nbytes: int) -> Tensor:
         """Grow-only workspace of the native path per (device, stream, main | tail).  PyTorch owns the memory."""
@@ -593,6 +602,16 @@ class Separator(nn.Module):
                                                                ws.data_ptr(), ws.numel(), stream), "xsq_separator_forward_segments")
         return out
 
+    def stream(self, nb_samples: int = 1, hop_slices: int = 1) -> "StreamSession":
+        """A stateful session that demixes audio arriving in blocks: ``feed`` returns the samples that became final, ``flush``
+        the rest, and the concatenation is ``forward`` of the whole signal by a separator whose ``chunk_size`` holds it -- a
+        stream has no chunk joints.  Every ``hop_slices`` blocks of sllen / 2 samples one step runs, as soon as
+        the audio 2 * sllen samples past the first of them has arrived (``latency_samples``).  Mix-phase models only: the
+        realtime model, or the offline stack with ``niter = 0`` / without Wiener; ``XsqError`` naming the reason for Wiener-EM
+        (its statistics span 5000-frame windows from the start of a chunk), ``softmask``, ``residual``, mixed block modes and
+        ``hop_slices < 1``."""
+        return StreamSession(self, nb_samples, hop_slices)
+
     @torch.no_grad()
     def forward_aggregate(self, audio_big: Tensor, aggregate_dict: dict) -> dict:
         """``to_dict(forward(audio), aggregate_dict)`` (separator.py:235-259) through ``remix`` with 0/1 gain rows: one
@@ -674,6 +693,248 @@ def overlapped_loop(forward, audio: Tensor, chunk_len: int, ov: int) -> Tensor:
         if fo:
             out[..., start + n - fo:start + n] = w_out * est[..., n - fo:]
     return out
+
+
+def stream_steps(N: int, L: int, hop_slices: int, back: int, ahead: int = STREAM_AHEAD):
+    """[(first block, blocks, first slice inverted, first slice of the window, last slice of the window, samples fed when it
+    fires)] of a stream of N samples in all (xsq_stream_schedule: host arithmetic, the one statement of the rule that the
+    native session, ``streamed_loop`` and the tests share).  Block k = samples [k L / 2, (k + 1) L / 2)."""
+    import numpy as np
+    if hop_slices < 1:
+        raise ValueError(f"hop_slices must be >= 1 (got {hop_slices})")
+    buf = np.zeros((max(1, 2 * N // max(1, L * hop_slices) + 2), 6), dtype=np.int64)
+    n = _lib.lib.xsq_stream_schedule(int(N), int(L), int(hop_slices), int(back), int(ahead), buf.ctypes.data, len(buf))
+    if n < 0 or n > len(buf):
+        raise ValueError(f"xsq_stream_schedule({N}, {L}, {hop_slices}, {back}, {ahead}): {_lib.last_error() if n < 0 else n}")
+    return [tuple(r) for r in buf[:n].tolist()]
+
+
+def stream_trigger(step: int, L: int, hop_slices: int, ahead: int = STREAM_AHEAD) -> int:
+    """Samples that must have been fed before step ``step`` of an open stream runs: its last window slice is complete."""
+    return (2 * ((step + 1) * hop_slices + ahead) + 2) * (L // 4)
+
+
+def _loop_span(b0: int, w1: int, h: int, back: int, N: Optional[int]):
+    """(t0, t1) of the sub-signal whose ``forward`` gives the blocks from b0 on their full context: one slice more than the window
+    on each side, because a plain ``forward`` cuts its first and its last slice against zeros.  The window starts ``back`` slices
+    behind slice b0, whose second half opens block b0."""
+    t0 = 2 * h * max(0, max(0, b0 - back) - 1)
+    t1 = (2 * w1 + 2) * h
+    return t0, (t1 if N is None else min(N, t1))
+
+
+def streamed_loop(forward, audio: Tensor, L: int, hop_slices: int, back: int, ahead: int = STREAM_AHEAD) -> Tensor:
+    """The schedule of a streaming session spelled through any ``forward`` (a callable (nb, ch, n) -> (J, nb, ch, n)): one call
+    per step of ``stream_steps`` on the sub-signal that gives the step's blocks their context, the blocks copied out of its
+    result.  With ``back`` / ``ahead`` at least the dependency window of the model behind ``forward`` the result is
+    ``forward(audio)``; one slice short it is not (tests/test_stream_cpu.py holds both)."""
+    nb, ch, N = audio.shape
+    if N < 1:
+        raise ValueError("streamed_loop: no samples")
+    h = L // 4
+    out = None
+    for b0, blocks, _first, _w0, w1, _trigger in stream_steps(N, L, hop_slices, back, ahead):
+        t0, t1 = _loop_span(b0, w1, h, back, N)
+        est = forward(audio[..., t0:t1])
+        if out is None:
+            out = torch.empty((*est.shape[:-1], N), dtype=est.dtype, device=est.device)
+        lo, n = b0 * 2 * h, min(blocks * 2 * h, N - b0 * 2 * h)
+        out[..., lo:lo + n] = est[..., lo - t0:lo - t0 + n]
+    return out
+
+
+class StreamGrid:
+    """The host bookkeeping of a streaming session, no device: which steps of the absolute block grid a run of ``feed`` calls
+    and the final ``flush`` fire.  The steps depend on the samples fed in all and on ``hop_slices``, never on the partition."""
+
+    def __init__(self, L: int, hop_slices: int, back: int, ahead: int = STREAM_AHEAD):
+        self.L, self.hop_slices, self.back, self.ahead = int(L), int(hop_slices), int(back), int(ahead)
+        self.samples_in = self.steps = 0
+
+    def trigger(self) -> int:
+        return stream_trigger(self.steps, self.L, self.hop_slices, self.ahead)
+
+    def feed(self, n: int):
+        """[(count, step)]: ``count`` more samples enter, then step ``step`` runs (None: none does -- the last entry at most)."""
+        events = []
+        while n > 0:
+            count = min(n, self.trigger() - self.samples_in)
+            self.samples_in, n = self.samples_in + count, n - count
+            fires = self.samples_in == self.trigger()
+            events.append((count, self.steps if fires else None))
+            self.steps += int(fires)
+        return events
+
+    def flush(self):
+        """The ``stream_steps`` rows of the steps that only the end of the stream releases."""
+        steps = stream_steps(self.samples_in, self.L, self.hop_slices, self.back, self.ahead)[self.steps:]
+        self.steps += len(steps)
+        return steps
+
+
+class StreamSession:
+    """``Separator.stream``: see there.  ``feed`` / ``flush`` return (4, nb_samples, 2, k); every launch goes to the caller's
+    current stream and nothing waits on the host.  By default one native call per step (xsq_stream_step) on device state that
+    does not grow: an audio ring and the carried half slice per output channel.  When an A/B switch is off its default
+    (``native = False``, ...) the steps are ``streamed_loop``'s: ``forward`` on a kept tail of the input."""
+
+    def __init__(self, separator: Separator, nb_samples: int = 1, hop_slices: int = 1):
+        model = separator.xumx_model
+        if int(hop_slices) < 1:
+            raise _lib.XsqError(f"stream: hop_slices must be >= 1 (got {hop_slices})")
+        if int(nb_samples) < 1:
+            raise _lib.XsqError(f"stream: nb_samples must be >= 1 (got {nb_samples})")
+        modes = {bool(b.realtime) for b in model.sliced_umx}
+        causal = {bool(b.causal) for b in model.sliced_umx}
+        if len(modes) != 1 or len(causal) != 1:
+            raise _lib.XsqError("stream: mixed per-block modes (some mix-phase, some Wiener; some causal, some not) are not supported")
+        if separator.softmask or separator.residual:
+            which = " and ".join(n for n in ("softmask", "residual") if getattr(separator, n))
+            raise _lib.XsqError(f"stream: {which} belongs to the Wiener post-filter, which cannot stream; a session is mix-phase")
+        if not modes.pop() and separator.niter >= 1:
+            raise _lib.XsqError(f"stream: Wiener-EM (niter = {separator.niter} on an offline model) cannot stream: its statistics span "
+                                "5000-frame windows counted from the start of a chunk and the window maximum; use the realtime model, "
+                                "niter = 0 or wiener = False")
+        self.separator = separator
+        self.nb_samples, self.hop_slices = int(nb_samples), int(hop_slices)
+        self.back, self.ahead = STREAM_BACK[causal.pop()], STREAM_AHEAD
+        self.L = int(separator.nsgt.nsgt.sllen)
+        self.h = self.L // 4
+        self._grid = StreamGrid(self.L, self.hop_slices, self.back, self.ahead)
+        self.samples_out = 0
+        self._closed = False
+        self._native = separator._native_switches()
+        self._handle = self._state = self._hist = None
+        self._hist0 = 0
+        self._ws_bytes = {}
+        if self._native:
+            dev = torch.device(separator.device)
+            if dev.type != "cuda":
+                raise _lib.XsqError(f"stream: a session lives on a ROCm device (the separator's is '{dev}')")
+            c = separator._native_call(dev)
+            handle = C.c_void_p()
+            _lib.check(_lib.lib.xsq_stream_create(C.byref(handle), c.d, c.model, self.nb_samples, self.hop_slices, self.back, self.ahead),
+                       "xsq_stream_create")
+            self._handle = handle
+            self._finalizer = weakref.finalize(self, _lib.lib.xsq_stream_destroy, handle)
+            with torch.cuda.device(c.dev):
+                self._state = torch.empty(int(_lib.lib.xsq_stream_state_bytes(handle)), dtype=torch.uint8, device=c.dev)
+            self._dev = c.dev
+
+    latency_samples = property(lambda self: (2 * self.ahead + 4) * self.h,
+                               doc="samples from the first of a block to the one that releases it at hop_slices = 1: 2 * sllen")
+
+    samples_in = property(lambda self: self._grid.samples_in, doc="samples fed so far")
+
+    @property
+    def state_bytes(self) -> int:
+        """Device memory the session holds between calls (the shared, grow-only step workspace of the separator is not its own)."""
+        if self._native:
+            return int(self._state.numel())
+        return 0 if self._hist is None else int(self._hist.numel() * self._hist.element_size())
+
+    def _empty(self, device, k: int) -> Tensor:
+        return torch.empty(4, self.nb_samples, 2, k, dtype=torch.float32, device=device)
+
+    def _check(self, block: Tensor) -> Tensor:
+        if self._closed:
+            raise _lib.XsqError("stream: the session was flushed; open a new one with Separator.stream()")
+        if not isinstance(block, Tensor) or block.dim() != 3 or tuple(block.shape[:2]) != (self.nb_samples, 2):
+            raise ValueError(f"feed wants ({self.nb_samples}, 2, n) audio; got {tuple(getattr(block, 'shape', ()))}")
+        if block.device.type != "cuda":
+            raise ValueError("feed needs the audio on a ROCm device (as forward)")
+        # a view along the samples of a longer (nb_samples, 2, N) tensor is read where it lies: rows one row stride apart
+        if block.dtype == torch.float32 and block.shape[-1] > 0 and block.stride(-1) == 1 and block.stride(1) >= block.shape[-1] \
+                and (self.nb_samples == 1 or block.stride(0) == 2 * block.stride(1)):
+            return block
+        return _fp32(block)
+
+    def _step_native(self, c: _Native, ws: Tensor, total: int, out: Tensor, col: int, length: int, new=(None, 0, 0)):
+        """``new`` = (address, row stride, count) of the samples that release the step: they ride on its first kernel."""
+        _lib.check(_lib.lib.xsq_stream_step(self._handle, c.model, self._state.data_ptr(), *new, total, out.data_ptr() + 4 * col,
+                                            out.shape[-1], length, ws.data_ptr(), ws.numel(), c.main.cuda_stream), "xsq_stream_step")
+
+    def _native_setup(self):
+        sep = self.separator
+        c = sep._native_call(self._dev)
+        key = sep._handle_key()
+        if key not in self._ws_bytes:
+            nbytes = _lib.lib.xsq_stream_workspace(self._handle, c.model)
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_stream_workspace: " + _lib.last_error())
+            self._ws_bytes = {key: nbytes}
+        return c, sep._native_ws(c.dev, c.main.cuda_stream, "stream", self._ws_bytes[key])
+
+    def _step_py(self, total: Optional[int], b0: int, blocks: int, w1: int, out: Tensor, col: int, length: int):
+        """One step of ``streamed_loop`` on the kept tail of the input, which then drops what no later step reads."""
+        t0, t1 = _loop_span(b0, w1, self.h, self.back, total)
+        est = self.separator.forward(self._hist[..., t0 - self._hist0:t1 - self._hist0])
+        lo = b0 * 2 * self.h - t0
+        out[..., col:col + length] = est[..., lo:lo + length]
+        keep = _loop_span(b0 + self.hop_slices, 0, self.h, self.back, None)[0]
+        self._hist, self._hist0 = self._hist[..., keep - self._hist0:], keep
+
+    @torch.no_grad()
+    def feed(self, block: Tensor) -> Tensor:
+        """``block`` (nb_samples, 2, n) fp32 on the device, any n >= 0 -> (4, nb_samples, 2, k): the samples that became final
+        with it, k a multiple of hop_slices * sllen / 2 (possibly 0)."""
+        block = self._check(block)
+        n, per = block.shape[-1], 2 * self.h * self.hop_slices
+        events = self._grid.feed(n)
+        fired = [step for _, step in events if step is not None]
+        out = self._empty(block.device, len(fired) * per)
+        if n == 0:
+            return out
+        if not self._native:
+            self._hist = block.clone() if self._hist is None else torch.cat([self._hist, block], dim=-1)
+            for i, step in enumerate(fired):
+                b0 = step * self.hop_slices
+                self._step_py(None, b0, self.hop_slices, b0 + self.hop_slices + self.ahead, out, i * per, per)
+            self.samples_out += len(fired) * per
+            return out
+        self.separator._packed_fft()
+        c, ws = self._native_setup()
+        with torch.cuda.device(c.dev):
+            pos = col = 0
+            for count, step in events:
+                if step is not None:
+                    self._step_native(c, ws, -1, out, col, per, new=(block.data_ptr() + 4 * pos, block.stride(1), count))
+                    col += per
+                else:
+                    _lib.check(_lib.lib.xsq_stream_push(self._handle, self._state.data_ptr(), block.data_ptr() + 4 * pos, block.stride(1), count,
+                                                        c.main.cuda_stream), "xsq_stream_push")
+                pos += count
+        self.samples_out += col
+        return out
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The rest: the blocks no later sample can change any more, the last one cut at the samples fed.  Closes the session."""
+        if self._closed:
+            raise _lib.XsqError("stream: the session was flushed already")
+        self._closed = True
+        N = self.samples_in
+        dev = self._dev if self._native else (self._hist.device if self._hist is not None else torch.device(self.separator.device))
+        out = self._empty(dev, N - self.samples_out)
+        steps = self._grid.flush()
+        if not steps:
+            return out
+        if self._native:
+            self.separator._packed_fft()
+            c, ws = self._native_setup()
+        col = 0
+        for b0, blocks, _first, _w0, w1, _trigger in steps:
+            length = min(blocks * 2 * self.h, N - b0 * 2 * self.h)
+            if self._native:
+                with torch.cuda.device(c.dev):
+                    self._step_native(c, ws, N, out, col, length)
+            else:
+                self._step_py(N, b0, blocks, w1, out, col, length)
+            col += length
+        self.samples_out += col
+        assert self.samples_out == N, (self.samples_out, N)
+        self._hist = None
+        return out
 
 
 def _gain_row(d: dict) -> list:
