@@ -1,7 +1,10 @@
 """The streaming session without a GPU: the step schedule on the absolute block grid (xsq_stream_schedule, ``StreamGrid``), the
 schedule spelled through the CPU oracle (``streamed_loop`` over ``oracle.separator.separate`` equals one ``separate`` of the whole
 signal, and does not when the window is one slice short), the dependency window of a mask that the constants of the code and
-DESIGN.md 4.11 state, and what ``Separator.stream`` and the CLI refuse.  The GPU half is tests/test_stream_gpu.py.
+DESIGN.md 4.11 state, and what ``Separator.stream`` and the CLI refuse.  The GPU half is tests/test_stream_gpu.py.  For the product
+plan, Bark-262: the same window in every one of its 70 blocks and the same loop over the oracle; for the stage tests of
+tests/test_stream_stages_gpu.py: the slice-shift property of the float64 transforms their references rest on, and the rule behind
+their bounds on the committed table.
 """
 import os
 import re
@@ -171,6 +174,130 @@ def test_the_dependency_window_is_what_the_constants_and_the_design_say(plan, sd
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("### 4.11"):]
     assert f"`s - {back} .. s + {ahead}`" in section
+
+
+# ---- Bark-262: the product plan, the only one with frequency taps --------------------------------------------------------------
+BARK_L = 18060
+BARK_N = 100000             # S = 13 slices, 12 blocks, the last one 670 samples
+
+
+def bark_track():
+    return 2 * torch.rand(1, 2, BARK_N, generator=torch.Generator().manual_seed(20261020)) - 1
+
+
+@pytest.mark.parametrize("causal", [True, False])
+def test_the_dependency_window_on_bark_holds_in_every_block(oracle_plan, seeded_sd, causal):
+    """The perturbation of the Mel test on the 70 blocks of Bark-262 (kernels of 3 and 5 bands in frequency): slice k moves the
+    masks of the slices k - 2 .. k + back in EVERY block, not only in their union -- no block has a shorter or a longer reach."""
+    from xumx_slicq_amd.separator import STREAM_AHEAD, STREAM_BACK
+    k = 6
+    assert oracle_plan.L == BARK_L and oracle_plan.nslices(BARK_N) == 13 and len(oracle_plan.blocks) == 70
+    want = set(range(k - STREAM_AHEAD, k + STREAM_BACK[causal] + 1))
+    with one_thread(), torch.no_grad():
+        X = O.forward(oracle_plan, bark_track())
+        touched, odd = set(), []
+        for b, Xb in enumerate(X):
+            mag = omodel.abs_of_real_complex(Xb)
+            assert mag.shape[3] == 13
+            base = omodel.cdae_masks(seeded_sd, b, mag, causal)
+            mag2 = mag.clone()
+            mag2[:, :, :, k] *= 1.5
+            moved = (omodel.cdae_masks(seeded_sd, b, mag2, causal) != base).any(-1).flatten(0, 3).any(0)
+            mine = {s for s in range(13) if bool(moved[s])}
+            touched |= mine
+            if mine != want:
+                odd.append((b, sorted(mine)))
+    assert not odd, odd
+    assert touched == want, sorted(touched)
+
+
+@pytest.fixture(scope="module")
+def bark_whole(oracle_plan, seeded_sd):
+    x = bark_track()
+    with one_thread():
+        return x, {causal: osep.separate(oracle_plan, seeded_sd, x, causal=causal, wiener=False) for causal in (True, False)}
+
+
+@pytest.mark.parametrize("causal", [True, False])
+def test_streamed_loop_over_the_oracle_on_bark(oracle_plan, seeded_sd, bark_whole, causal):
+    """m = 3: four steps over the 12 blocks, the last clipped at the signal.  The bounds are those of the Mel test."""
+    from xumx_slicq_amd.separator import STREAM_BACK, streamed_loop
+    x, ref = bark_whole
+    back, m, h = STREAM_BACK[causal], 3, BARK_L // 4
+    calls = []
+
+    def forward(a):
+        calls.append(a.shape[-1])
+        return osep.separate(oracle_plan, seeded_sd, a, causal=causal, wiener=False)
+
+    with one_thread():
+        full = streamed_loop(forward, x, BARK_L, m, back)
+        ncalls = len(calls)
+        short = streamed_loop(forward, x, BARK_L, m, back - 1)
+    assert ncalls == 4 and max(calls[:ncalls]) <= (2 * (m + back + 2 + 2) + 2) * h
+    assert full.shape == ref[causal].shape == (4, 1, 2, BARK_N)
+    e_full, e_short = float((full - ref[causal]).abs().max()), float((short - ref[causal]).abs().max())
+    print(f"bark causal={causal} m={m}: max error full window {e_full:.3g}, one slice short {e_short:.3g}")
+    assert e_full <= 1e-6
+    assert e_short > 1e-3
+
+
+# ---- what the stage tests of tests/test_stream_stages_gpu.py rest on ------------------------------------------------------------
+@pytest.mark.parametrize("which", ["mel", "bark"])
+def test_slices_of_the_float64_transforms_do_not_depend_on_where_the_signal_starts(plan, oracle_plan, which):
+    """A slice is a function of its own 4h samples, and an inverted slice adds to its own 4h samples: (a) the slices 1 .. S of
+    ``ref64.forward(v)``, v of (2S + 2)h samples, are the slices k + 1 .. k + S of any signal that holds v from sample 2hk on;
+    (b) the overlap-add of ``ref64.inverse`` over consecutive slice ranges is ``ref64.inverse`` of all the slices, and the blocks
+    a range closes on its own are that span of the whole.  Float64: 1e-13 of the RMS."""
+    from oracle import ref64
+    p = plan if which == "mel" else oracle_plan
+    h, S, gen = p.h, 3, torch.Generator().manual_seed(p.L)
+    v = 2 * torch.rand(2, (2 * S + 2) * h, generator=gen, dtype=torch.float64) - 1
+    own = ref64.forward(p, v)
+    assert own[0].shape[-3] == S + 2
+    for k, tail in ((1, 0), (2, 3 * h + 5)):
+        w = torch.cat([torch.randn(2, 2 * h * k, generator=gen, dtype=torch.float64), v,
+                       torch.randn(2, tail, generator=gen, dtype=torch.float64)], dim=-1)
+        for a, b in zip(own, ref64.forward(p, w)):
+            a, b = a[..., 1:S + 1, :, :], b[..., k + 1:k + S + 1, :, :]
+            assert float((a - b).abs().max()) <= 1e-13 * float(b.pow(2).mean().sqrt()), (which, k)
+    S_tot = 9
+    X = [torch.randn(2, F, S_tot, T, 2, generator=gen, dtype=torch.float64) for (_, F, T) in p.blocks]
+    length = 2 * S_tot * h
+    whole = ref64.inverse(p, X, length)
+    rms = float(whole.pow(2).mean().sqrt())
+    for parts in ((9,), (4, 3, 2), (2, 7), (2, 1, 1, 1, 1, 1, 1, 1)):
+        pad, a = torch.zeros(2, (2 * S_tot + 2) * h, dtype=torch.float64), 0
+        for n in parts:
+            # a zero slice in front: the range's own first half is then part of what inverse returns
+            seg = ref64.inverse(p, [torch.cat([torch.zeros_like(x[..., :1, :, :]), x[..., a:a + n, :, :]], dim=-3) for x in X], (2 * n + 2) * h)
+            pad[:, 2 * a * h:(2 * a + 2 * n + 2) * h] += seg
+            if n >= 2:       # the blocks a .. a + n - 2 lie inside the range
+                alone = ref64.inverse(p, [x[..., a:a + n, :, :] for x in X], 2 * (n - 1) * h)
+                assert float((alone - whole[:, 2 * a * h:2 * (a + n - 1) * h]).abs().max()) <= 1e-13 * rms, (which, parts, a)
+            a += n
+        assert a == S_tot and float((pad[:, 2 * h:2 * h + length] - whole).abs().max()) <= 1e-13 * rms, (which, parts)
+
+
+def test_every_stage_bound_follows_the_rule_from_the_committed_table():
+    """M of tests/test_stream_stages_gpu.py = the smallest power of two that is at least twice the worst e_gpu / E of
+    profiles/stream_stage_parity.json (measured on MI355X), at most M_CAP; the table covers both plans and every partition."""
+    import json
+    from oracle.parity import M_CAP
+    from test_stream_stages_gpu import M, PARTITIONS, PLANS
+    table = json.load(open(os.path.join(ROOT, "profiles", "stream_stage_parity.json")))
+    for stage, bound in M.items():
+        worst = table["M"][stage]["worst_ratio"]
+        want = 1
+        while want < 2 * worst:
+            want *= 2
+        assert 0 < worst and bound == min(want, M_CAP) and table["M"][stage]["M"] == bound, (stage, worst, bound)
+        cases = table["tables"][stage]
+        assert all(any(c.startswith(name) for c in cases) for name in PLANS)
+        assert max(rec["worst_ratio"] for rec in cases.values()) == worst
+    for name in PLANS:
+        for B in (1, 2):
+            assert all(f"{name} B={B} partition {parts}" in table["tables"]["inverse_carry"] for parts in PARTITIONS)
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------

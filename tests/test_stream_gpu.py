@@ -6,6 +6,10 @@ e_str <= 2 * e_fwd for both.  The two are fp32 evaluations of the same sums unde
 starts at another slice parity than the whole call's arena, which moves individual roundings of the F(2, 2) / Winograd kernels, not
 their scale); a window one slice short sits near 1e-3 RMS, four orders above (tests/test_stream_cpu.py).  Every case prints both
 figures; DESIGN.md 4.11 holds the measured ones.
+
+Sections 9 to 11 hold the fused L = 18060 kernels of Bark-262 where a step inverts several new slices onto a carried half (m >= 2),
+the offline stack, two items and the short signals, long Mel-32 sessions, and what the header promises of the state and the
+workspace; the two transform halves of a step are judged per band and per block in tests/test_stream_stages_gpu.py.
 """
 import numpy as np
 import pytest
@@ -32,10 +36,15 @@ def mel_seps():
 
 
 @pytest.fixture(scope="module")
-def mel_ref():
-    """float64 stems of (model, nb, N), computed once and shared by the cases that differ in hop_slices or in the arm."""
+def mel_tables():
     plan = make_mel_plan()
-    sd = make_mel_sd(plan)
+    return plan, make_mel_sd(plan)
+
+
+@pytest.fixture(scope="module")
+def mel_ref(mel_tables):
+    """float64 stems of (model, nb, N), computed once and shared by the cases that differ in hop_slices or in the arm."""
+    plan, sd = mel_tables
     cache = {}
 
     def get(name, nb, n):
@@ -50,13 +59,16 @@ def track(nb, n):
     return 2 * torch.rand(nb, 2, n, generator=torch.Generator().manual_seed(1000 * nb + n)) - 1
 
 
-def run_session(sep, x, hop_slices=1, feeds=FEED):
-    """The joined returns of a session over ``x``, fed in blocks of ``feeds`` samples (an int) or of the listed sizes."""
+def run_session(sep, x, hop_slices=1, feeds=FEED, prepare=None):
+    """The joined returns of a session over ``x``, fed in blocks of ``feeds`` samples (an int) or of the listed sizes; ``prepare`` is
+    called with the session before its first feed."""
     n = x.shape[-1]
     sizes = [min(feeds, n - p) for p in range(0, n, feeds)] if isinstance(feeds, int) else list(feeds)
     assert sum(sizes) == n
     session = sep.stream(x.shape[0], hop_slices)
     assert session._native == sep._native_switches()
+    if prepare is not None:
+        prepare(session)
     per, parts, p = 2 * session.h * hop_slices, [], 0
     for k in sizes:
         parts.append(session.feed(x[..., p:p + k]))
@@ -151,21 +163,32 @@ def test_steps_fire_on_the_grid_and_flush_closes_the_session(mel_seps, hop_slice
 
 
 # ---- 5. the state does not grow ---------------------------------------------------------------------------------------------
-def test_state_is_bounded_over_400_blocks(mel_seps):
+def test_state_is_bounded_over_400_blocks(mel_seps, mel_tables):
+    """... and the last block the session emits, block 399 of the stream, is still ``forward`` of the signal around it: against
+    float64 on the 13 blocks 390 .. 402 (the slices 396 .. 402 its masks read lie inside them, clear of the cut ends), under the
+    bound of ``judge``."""
     sep = mel_seps["realtime"]
     x = track(1, 2 * H * 40).cuda()
     s = sep.stream(1, 1)
     state, allocated = s.state_bytes, {}
     assert state == s._state.numel() and state >= 4 * (2 * (2 * (3 + 2 + 1) + 2) * H + 2 * 8 * 2 * H)
+    last = None
     for k in range(1, 404):
         out = s.feed(x[..., (k % 40) * 2 * H:(k % 40 + 1) * 2 * H])
         assert out.shape[-1] == (2 * H if k >= 4 else 0)
+        if k == 403:
+            last = out.cpu()                                      # block k - 4 = 399 of the stream (host memory)
         del out
         if k in (23, 403):                                        # after step 20 and after step 400
             assert s.samples_out == 2 * H * (k - 3)
             allocated[k] = torch.cuda.memory_allocated()
         assert s.state_bytes == state
     assert allocated[403] == allocated[23], allocated
+    plan, sd = mel_tables
+    around = torch.cat([x[..., (k % 40) * 2 * H:(k % 40 + 1) * 2 * H] for k in range(391, 404)], dim=-1)      # fed as blocks 390 .. 402
+    cut = slice(9 * 2 * H, 10 * 2 * H)
+    ref = ref64.separate(plan, sd, around.cpu(), causal=True, wiener=False)[..., cut]
+    judge("realtime block 399 of a 403-block session", last, sep.forward(around).cpu()[..., cut], ref)
 
 
 # ---- 6. the stream contract -------------------------------------------------------------------------------------------------
@@ -228,3 +251,146 @@ def test_cli_stream_writes_the_stems_of_the_session(mel_seps, tmp_path, monkeypa
         got, rate = xaudio.load_audio(str(tmp_path / "out" / "clip" / f"{target}.wav"))
         assert rate == 44100 and torch.equal(got, want[t, 0]), target
     assert np.isfinite(want.numpy()).all()
+
+
+# ---- 9. Bark-262, the fused L = 18060 slice kernels: several new slices per step, the offline stack, nb = 2 -----------------
+BARK_L = 18060
+BARK_H = BARK_L // 4
+BARK_N = 100000                 # 13 slices, 12 blocks, the last one 670 samples
+BARK_FEED = 30000
+
+
+@pytest.fixture(scope="module")
+def bark_seps():
+    from xumx_slicq_amd.separator import seeded_separator
+    return {"realtime": seeded_separator(realtime=True), "offline_phasemix": seeded_separator(realtime=False, wiener=False)}
+
+
+@pytest.fixture(scope="module")
+def bark_ref(oracle_plan, seeded_sd, bark_seps):
+    """(float64 stems, ``forward`` of the whole signal) of (model, nb, N) on ``track(nb, N)``, computed once per module."""
+    cache = {}
+
+    def get(name, nb, n):
+        key = (name, nb, n)
+        if key not in cache:
+            x = track(nb, n)
+            cache[key] = (ref64.separate(oracle_plan, seeded_sd, x, causal=MODELS[name], wiener=False), bark_seps[name].forward(x.cuda()).cpu())
+        return cache[key]
+    return get
+
+
+def bark_case(bark_seps, bark_ref, name, nb, n, hop_slices, feeds=BARK_FEED):
+    ref, fwd = bark_ref(name, nb, n)
+    judge(f"bark {name} nb={nb} n={n} m={hop_slices}", run_session(bark_seps[name], track(nb, n).cuda(), hop_slices, feeds).cpu(), fwd, ref)
+
+
+@pytest.mark.parametrize("hop_slices,steps", [(2, 6), (3, 4), (5, 3)])
+def test_bark_realtime_session_with_several_new_slices_per_step(oracle_plan, bark_seps, bark_ref, hop_slices, steps):
+    """Every step after the first inverts m >= 2 new slices onto the carried half: both launches of the fused inverse kernel run
+    beside a carry.  m = 2: the third feed of 30000 samples releases two steps at once and flush runs two clipped ones; m = 5:
+    one step in feed, two in flush, the last of 2 blocks cut at n."""
+    from xumx_slicq_amd.separator import stream_steps, stream_trigger
+    assert oracle_plan.nslices(BARK_N) == 13 and len(stream_steps(BARK_N, BARK_L, hop_slices, 3)) == steps
+    assert [stream_trigger(j, BARK_L, 2) for j in range(4)] == [45150, 63210, 81270, 99330]
+    bark_case(bark_seps, bark_ref, "realtime", 1, BARK_N, hop_slices)
+
+
+@pytest.mark.parametrize("hop_slices", [1, 3])
+def test_bark_offline_session_is_forward_of_the_whole(bark_seps, bark_ref, hop_slices):
+    bark_case(bark_seps, bark_ref, "offline_phasemix", 1, BARK_N, hop_slices)
+
+
+@pytest.mark.parametrize("hop_slices", [1, 2])
+def test_bark_session_of_two_items(bark_seps, bark_ref, hop_slices):
+    bark_case(bark_seps, bark_ref, "realtime", 2, 50000, hop_slices)
+
+
+@pytest.mark.parametrize("hop_slices", [1, 4])
+@pytest.mark.parametrize("n", [1, 9031, 18060, 18061])
+@pytest.mark.parametrize("name", list(MODELS))
+def test_bark_short_signals(bark_seps, bark_ref, name, n, hop_slices):
+    bark_case(bark_seps, bark_ref, name, 1, n, hop_slices)
+
+
+def test_bark_partition_of_the_feeds_does_not_change_a_bit(bark_seps):
+    sep, n = bark_seps["realtime"], BARK_N
+    x = track(1, n).cuda()
+    want = run_session(sep, x, 3, [n])
+    for feeds in ([1, n - 1], 9030, BARK_FEED, [50000, 0, n - 50000]):
+        got = run_session(sep, x, 3, feeds)
+        assert torch.equal(got, want), (feeds, float((got - want).abs().max()))
+    assert np.isfinite(want.cpu().numpy()).all()
+
+
+def test_bark_python_arm_meets_the_same_bound(bark_seps, bark_ref):
+    sep = bark_seps["realtime"]
+    ref, fwd = bark_ref("realtime", 1, BARK_N)
+    try:
+        sep.native = False
+        assert not sep.stream(1, 3)._native
+        est = run_session(sep, track(1, BARK_N).cuda(), 3, BARK_FEED).cpu()
+    finally:
+        del sep.native
+    judge("bark realtime native=False m=3", est, fwd, ref)
+
+
+# ---- 10. long Mel-32 sessions against float64 --------------------------------------------------------------------------------
+@pytest.mark.parametrize("hop_slices", [1, 7])
+def test_mel_long_session_is_forward_of_the_whole(mel_seps, mel_ref, hop_slices):
+    """n = 300000: 298 blocks; at m = 1 a step per block, and the ring of 14h = 7056 samples turns over 42 times."""
+    sep, n = mel_seps["realtime"], 300000
+    assert sep.stream(1, 1)._state is not None and (2 * (3 + 2 + 1) + 2) * H == 7056
+    x = track(1, n).cuda()
+    judge(f"realtime nb=1 n={n} m={hop_slices}", run_session(sep, x, hop_slices, 4096).cpu(), sep.forward(x).cpu(), mel_ref("realtime", 1, n))
+
+
+# ---- 11. the state needs no initialisation; nothing lives in the workspace between steps --------------------------------------
+@pytest.mark.parametrize("which", ["mel", "bark"])
+def test_state_needs_no_initialisation(mel_seps, bark_seps, which):
+    """The ring and both carry buffers filled with NaN, and with 1e30, before the first feed: the bits of an untouched session."""
+    sep, n, feeds = (mel_seps["realtime"], N_TRACK, FEED) if which == "mel" else (bark_seps["realtime"], BARK_N, BARK_FEED)
+    x = track(1, n).cuda()
+    want = run_session(sep, x, 2, feeds)
+    assert np.isfinite(want.cpu().numpy()).all()
+    for fill in (float("nan"), 1e30):
+        def prepare(session):
+            state = session._state.view(torch.float32)
+            assert state.numel() * 4 == session.state_bytes
+            state.fill_(fill)
+        got = run_session(sep, x, 2, feeds, prepare=prepare)
+        assert torch.equal(got, want), (which, fill)
+
+
+def test_two_sessions_and_a_forward_share_one_stream(mel_seps):
+    """Two sessions of different hop_slices fed in turn on ONE stream -- they share the separator's step workspace -- with a
+    ``forward`` of another length between their feeds: each returns the bits of its solo run."""
+    sep = mel_seps["realtime"]
+    xs = [track(1, N_TRACK).cuda(), track(1, N_TRACK + 3)[..., 3:].cuda()]
+    hops = [2, 1]
+    want = [run_session(sep, x, m) for x, m in zip(xs, hops)]
+    other = track(1, 7 * H + 11).cuda()
+    other_want = sep.forward(other).clone()
+    sessions, parts = [sep.stream(1, m) for m in hops], [[], []]
+    for p in range(0, N_TRACK, FEED):
+        for i in (0, 1):
+            parts[i].append(sessions[i].feed(xs[i][..., p:p + FEED]))
+            assert torch.equal(sep.forward(other), other_want)
+    for i in (0, 1):
+        parts[i].append(sessions[i].flush())
+        assert torch.equal(torch.cat(parts[i], dim=-1), want[i]), i
+    assert not torch.equal(want[0], want[1])
+
+
+def test_feed_converts_what_is_not_contiguous_fp32(mel_seps):
+    """A float64 block and a block with a sample stride of 2 are the fp32 contiguous feed, bit for bit."""
+    sep = mel_seps["realtime"]
+    x = track(1, N_TRACK).cuda()
+    want = run_session(sep, x, 2)
+    wide = torch.zeros(1, 2, 2 * N_TRACK, device="cuda")
+    wide[..., ::2] = x
+    wide[..., 1::2] = float("nan")
+    strided = wide[..., ::2]
+    assert strided.stride(-1) == 2 and torch.equal(strided, x)
+    assert torch.equal(run_session(sep, strided, 2), want)
+    assert torch.equal(run_session(sep, x.double(), 2), want)
