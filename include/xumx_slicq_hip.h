@@ -462,6 +462,45 @@ int64_t xsq_train_step_count(xsq_train* t, int64_t set);
  * operands (an A/B arm).                                                                                             */
 int xsq_train_set_precision(xsq_train* t, int mode);
 
+/* ---- SDR term of the training loss (loss.py:5-34: auraloss.time.SDSDRLoss over the 14 target combinations) ----------
+ * Waveforms pred / target (4, B, 2, n) on the device.  Per (b, ch) row and combination c (estimates p and targets t of
+ * the members summed, both centred over the n samples):
+ *   alpha = <p, t> / (<t, t> + 1e-8);   loss = -10 log10( |alpha t|^2 / (|p - t|^2 + 1e-8) + 1e-8 )
+ * and the criterion is the mean over rows and combinations.  out: DEVICE double[1 + 84 B]: the criterion, then the row
+ * losses it is the mean of, [b][ch][combination] (singles, pairs, triples in loss.py's order), then in the same layout the two
+ * scalars A and B of every combination's gradient  scale / (28 B) * d loss_row / d p = A t + B (p - t)  (p, t centred; scale = 1 in
+ * the forward call).  xsq_sdr_loss_backward also writes
+ * gy (4, B, 2, n) = scale * d criterion / d pred.  Two streaming passes with fp64 moments in fixed order (no atomics); a
+ * silent target gives row loss 80 and gradient 0.  XSQ_ERR_ARG on a null pointer, B or n <= 0, or a workspace below
+ * xsq_sdr_loss_workspace (0 on bad arguments).                                                                        */
+size_t xsq_sdr_loss_workspace(int B, int64_t n);
+int xsq_sdr_loss_forward(const float* pred, const float* target, int B, int64_t n, double* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int xsq_sdr_loss_backward(const float* pred, const float* target, int B, int64_t n, float scale, double* out, float* gy,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- adjoint of the inverse sliCQT: the gradient of a time-domain loss with respect to the coefficients -------------
+ * With y = xsq_slicqt_inverse(coef, BC, S, length) and gy (BC, length) = dLoss/dy, gcoef (arena of BC channels, S
+ * slices) = dLoss/dcoef; accumulate != 0 adds it to what gcoef holds.  It is the analysis with a slice window of ones
+ * and the window a' (xsq_slicqt_adjoint_window: host arithmetic, no device; out laid out like gd) in place of g, run
+ * on the analysis kernels of the plan's back end over tables built from a' on first use (a synchronous upload).        */
+int xsq_slicqt_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_t* c, const double* gd, double* out);
+size_t xsq_slicqt_inverse_adjoint_workspace(xsq_plan* plan, int BC, int S, int accumulate);
+int xsq_slicqt_inverse_adjoint(xsq_plan* plan, const float* gy, int BC, int S, int64_t length, float* gcoef, int accumulate,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the training step with the SDR term ---------------------------------------------------------------------------
+ * xsq_train_step plus  mcoef * SDR( inverse sliCQT of the estimates, y_targets ): the estimates' inverse transform, the two
+ * SDR passes and the adjoint added into the estimates' gradient run between the loss pass and the post-filter backward.
+ * plan: the transform the arenas came from; y_targets (4, B, 2, n) on the device; mcoef > 0.  loss_out: HOST double[3]
+ * (complex MSE, mask sum, SDR criterion unweighted); xsq_train_loss_sdr reads the same by ticket (third value 0 for a
+ * step issued without the term).  The transform and SDR kernels are fp32 under every precision mode.                  */
+size_t xsq_train_workspace_sdr(const xsq_train* t, xsq_plan* plan, int B, int S, int wiener, int64_t n);
+int xsq_train_step_sdr(xsq_train* t, xsq_plan* plan, const float* X, const float* Yt, const float* y_targets, int64_t n,
+                       float mcoef, int B, int S, int wiener, float lr, float weight_decay, int apply_update,
+                       double* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+int xsq_train_loss_sdr(xsq_train* t, int64_t ticket, double* loss_out);
+
 /* ---- the whole call: Separator.forward (separator.py:133-232) behind ONE entry point ----------------------------
  * The reference's chunk loop -- per chunk of <= chunk_size samples: zero-pad to sllen/2 + 1 (162-168), sliCQT (170),
  * Unmix with mix-phase or Wiener-EM (172-219), isliCQT to the chunk's length (221-227), hard concat (229-231) -- issued

@@ -18,11 +18,12 @@ ap.add_argument("--realtime", action="store_true")
 ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x6"])
 ap.add_argument("--no-profile", action="store_true", help="no per-kernel events: the clean wall time")
 ap.add_argument("--pipelined", action="store_true", help="look at a step's loss after the next step has been issued")
+ap.add_argument("--sdr-mcoef", type=float, default=-1.0, help="> 0: the step with the SDR loss term (training.py:94); its kernels are in the table")
 a = ap.parse_args()
 n = int(a.seq_dur * 44100)
 with redirect_stdout(sys.stderr):
     sep = seeded_separator(realtime=a.realtime)
-tr = Trainer(sep.xumx_model, (sep.nsgt, sep.insgt, sep.cnorm), precision=a.precision)
+tr = Trainer(sep.xumx_model, (sep.nsgt, sep.insgt, sep.cnorm), precision=a.precision, sdr_mcoef=a.sdr_mcoef)
 y_t = torch.stack([0.5 * synth_audio(n, seed=700 + j, nb_samples=a.batch) for j in range(4)]).cuda()
 x = y_t.sum(0)
 losses = []
@@ -48,6 +49,6 @@ prof = _lib.profile_read()
 _lib.profile_enable(False)
 kern = {k: round(ms / a.steps, 3) for k, (ms, cnt) in sorted(prof.items(), key=lambda kv: -kv[1][0])}
 print(json.dumps({"metric": "training steps/s", "value": 1.0 / dt, "ms_per_step": dt * 1e3, "chunks_per_s": a.batch / dt,
-                  "batch": a.batch, "seq_dur": a.seq_dur, "model": "realtime" if a.realtime else "offline",
+                  "batch": a.batch, "seq_dur": a.seq_dur, "sdr_mcoef": a.sdr_mcoef, "model": "realtime" if a.realtime else "offline",
                   "dtype": "f32" if a.precision == "fp32" else "f32 (GEMM contractions as bf16x6)", "losses": [round(l, 5) for l in losses], "kernels_ms": kern,
                   "hbm_peak_gb": torch.cuda.max_memory_allocated() / 2**30}))

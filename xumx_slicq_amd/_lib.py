@@ -88,6 +88,16 @@ _SIGS = {
     "xsq_train_write": (C.c_int, [_vp, C.c_int, _vp]),
     "xsq_train_step_count": (C.c_int64, [_vp, C.c_int64]),
     "xsq_train_set_precision": (C.c_int, [_vp, C.c_int]),
+    "xsq_sdr_loss_workspace": (C.c_size_t, [C.c_int, C.c_int64]),
+    "xsq_sdr_loss_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_sdr_loss_backward": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_slicqt_adjoint_window": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "xsq_slicqt_inverse_adjoint_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
+    "xsq_slicqt_inverse_adjoint": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "xsq_train_workspace_sdr": (C.c_size_t, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "xsq_train_step_sdr": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                     _vp, _vp, C.c_size_t, _vp]),
+    "xsq_train_loss_sdr": (C.c_int, [_vp, C.c_int64, _vp]),
     "xsq_place_rows": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp]),
     "xsq_resample": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "xsq_wiener_num_windows": (C.c_int64, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -101,5 +101,8 @@ int wiener_em_backward(int nblocks, const int32_t* F, const int32_t* T, const fl
 // loss forward (loss.hip), optionally with the gradients of both terms written in the same pass (gY / gM non-null)
 int loss_forward_backward(int nblocks, const int32_t* F, const int32_t* T, const float* pred, const float* target,
                           const float* masks, int Bn, int S, double* out, float* gY, float* gM, void* ws, hipStream_t stream);
+// SDR criterion on waveforms (sdr.hip): pred / target (4, R, n) -> out DEVICE double[1 + 42 R] (criterion, row losses, gradient scalars); gy (4, R, n) or null = scale * its
+// gradient with respect to pred.  ws: xsq_sdr_loss_workspace(R / 2, n) bytes.
+int sdr_loss(const float* pred, const float* target, int R, int64_t n, float scale, double* out, float* gy, void* ws, hipStream_t stream);
 
 }  // namespace xsq

@@ -117,6 +117,15 @@ struct xsq_plan {
     xsq::BandDev* d_bands = nullptr;
     int* d_cov_ptr = nullptr;       // (nbins+1) CSR over spectrum bins -> covering bands
     int* d_cov_band = nullptr;
+    // Adjoint of the inverse transform (xsq_slicqt_inverse_adjoint): the analysis tables rebuilt from the adjoint window a'
+    // (xsq_slicqt_adjoint_window) and a slice window of ones, on first use, from the host copies of the band table kept here.
+    std::vector<int32_t> h_Lg, h_c;
+    std::vector<double> h_gd;
+    size_t wf_floats = 0, pool4_floats = 0;   // sizes of d_Wf and d_pool4f as built: the adjoint's copies must have the same layout
+    bool adj_built = false;
+    float* d_adj_tw = nullptr;      // (L) ones
+    float* d_adj_Wf = nullptr;      // dense analysis matrices of a'
+    float* d_adj_pool4f = nullptr;  // radix-4 analysis pool with the windows a'
     // caches keyed by the call shape
     std::mutex mu;
     std::map<std::pair<int, int>, xsq::FftPlan> fft;              // (direction, batch)

@@ -505,12 +505,13 @@ struct PlanArgs {
     const double* gd;
     const float* tw;
     std::vector<int64_t> g_off;     // first sample of band j's windows inside g / gd (the bands' windows lie back to back)
+    const double* ga64 = nullptr;   // when set: the analysis window in double, in place of g (the adjoint tables, adjoint_tables())
 
     // (-1)^(c_j / 2), and sample q of the band's two windows with the sign and the transform's scale folded in.  The dense
     // matrices, the window pool of the radix-4 kernel and the short-band schedule all take them from here: the engines are
     // interchangeable per band only while these agree to the bit.
     double sign(int j) const { return ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0; }
-    double analysis_window(int j, int q) const { return (double)g[g_off[j] + q] * sign(j) / Lg[j]; }
+    double analysis_window(int j, int q) const { return (ga64 ? ga64[g_off[j] + q] : (double)g[g_off[j] + q]) * sign(j) / Lg[j]; }
     double synthesis_window(int j, int q) const { return gd[g_off[j] + q] * Lg[j] * sign(j) / L; }
 };
 
@@ -644,15 +645,16 @@ static bool build_slice_fft_tables(xsq_plan* P, std::vector<float2>& T, std::vec
 
 // Tables of the radix-4 band kernels (band_dft4.h, band_dft4s.h) over the bands with Lg >= the split point; the other bands
 // go to bands4_small (the dense engine, gemm_tile.h) and get their flag in is_short.
+// `commit` false: only the pools are wanted (the adjoint's windows over the band split the plan already has) -- the plan stays as it is.
 static void build_radix4_tables(xsq_plan* P, const PlanArgs& A, std::vector<Band4Dev>& b4, std::vector<float>& pf, std::vector<float>& pi,
-                                std::vector<char>& is_short) {
+                                std::vector<char>& is_short, bool commit = true) {
     const int d4_min_lg = switches().d4_min_lg;
     is_short.assign(A.nbands, 0);
     std::map<int, int64_t> doff, twoff, coff;
     auto alloc2 = [&](size_t n) { size_t o = pf.size(); pf.resize(o + n, 0.f); pi.resize(o + n, 0.f); return (int64_t)o; };    // analysis / synthesis pools
     for (int j = 0; j < A.nbands; ++j) {
         const BandDev& b = P->bands[j];
-        if (b.Lg < d4_min_lg || b.Lg > 4 * D4_MPAD) { P->bands4_small.push_back(j); is_short[j] = 1; continue; }
+        if (b.Lg < d4_min_lg || b.Lg > 4 * D4_MPAD) { if (commit) P->bands4_small.push_back(j); is_short[j] = 1; continue; }
         const int n = b.Lg, m = n / 4;
         Band4Dev d;
         memset(&d, 0, sizeof(d));
@@ -713,9 +715,11 @@ static void build_radix4_tables(xsq_plan* P, const PlanArgs& A, std::vector<Band
             pi[d.win_off + q] = (float)A.synthesis_window(j, q);
         }
         b4.push_back(d);
+        if (!commit) continue;
         P->bands4_m.push_back(m);
         P->d4_max_block = std::max<int64_t>(P->d4_max_block, (int64_t)b.F * b.Lg);
     }
+    if (!commit) return;
     P->nbands4 = (int)b4.size();
     P->bands4_host.assign(reinterpret_cast<const unsigned char*>(b4.data()),
                           reinterpret_cast<const unsigned char*>(b4.data()) + b4.size() * sizeof(Band4Dev));
@@ -803,6 +807,7 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
     std::vector<float> Wf, Wi;
     build_dense_matrices(P, A, Wf, Wi);
     if ((rc = upload(P->d_Wf, Wf))) return rc;
+    P->wf_floats = Wf.size();
     if ((rc = upload(P->d_Wi, Wi))) return rc;
 
     std::vector<int> cov_ptr, cov_band;
@@ -838,10 +843,14 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
         if (P->nbands4) {
             if ((rc = upload(P->d_bands4, b4))) return rc;
             if ((rc = upload(P->d_pool4f, pf))) return rc;
+            P->pool4_floats = pf.size();
             if ((rc = upload(P->d_pool4i, pi))) return rc;
         }
     }
     if ((rc = upload(P->d_tw, tw, (size_t)L))) return rc;
+    // what the adjoint tables are made from on first use (adjoint_tables)
+    P->h_Lg.assign(Lg, Lg + nbands); P->h_c.assign(c, c + nbands);
+    P->h_gd.assign(gd, gd + A.g_off[nbands - 1] + Lg[nbands - 1]);
 
     // (needs the LDS slice FFT's gather table, and both kinds of band)
     ShortTables H;
@@ -898,6 +907,7 @@ int xsq_plan_destroy(xsq_plan* P) {
     (void)hipFree(P->d_bands4); (void)hipFree(P->d_pool4f); (void)hipFree(P->d_pool4i);
     (void)hipFree(P->d_T); (void)hipFree(P->d_tgt); (void)hipFree(P->d_tgt16); (void)hipFree(P->d_tw); (void)hipFree(P->d_Wf); (void)hipFree(P->d_Wi); (void)hipFree(P->d_bands);
     (void)hipFree(P->d_cov_ptr); (void)hipFree(P->d_cov_band);
+    (void)hipFree(P->d_adj_tw); (void)hipFree(P->d_adj_Wf); (void)hipFree(P->d_adj_pool4f);
     (void)hipFree(P->d_s_item1); (void)hipFree(P->d_s_tw1); (void)hipFree(P->d_s_item2); (void)hipFree(P->d_s_tgt); (void)hipFree(P->d_s_wd);
     delete P;
     return XSQ_OK;
@@ -999,9 +1009,11 @@ int xsq_slicqt_forward_rows(xsq_plan* P, const float* x, const int64_t* x_rows, 
 
 // S slices per channel from absolute slice s0 on; ring > 0: x is the ring of a streaming session (k_slice_rfft, RING)
 struct RingNew { const float* x; int64_t first, stride; };       // the samples from `first` on, not yet in the ring (row bc at x + bc * stride)
+// the window-dependent tables of the analysis: the plan's own (null) or the adjoint's (adjoint_tables)
+struct AnalysisTables { const float *tw, *Wf, *pool4f; };
 static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n, int S, int64_t s0,
                         int ring, float* coef, float* xin, const float* mean, const float* scale, int split, void* ws, size_t ws_bytes,
-                        void* stream_, RingNew fresh = RingNew{nullptr, 0, 0});
+                        void* stream_, RingNew fresh = RingNew{nullptr, 0, 0}, const AnalysisTables* adj = nullptr);
 
 int xsq_slicqt_forward_rows_indirect(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n,
                                      int64_t n_pad, float* coef, float* xin, const float* mean, const float* scale, int split,
@@ -1034,8 +1046,11 @@ int xsq_slicqt_forward_ring(xsq_plan* P, float* ring, int ring_len, int BC, int6
 
 static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n, int S, int64_t s0,
                         int ring, float* coef, float* xin, const float* mean, const float* scale, int split, void* ws, size_t ws_bytes,
-                        void* stream_, RingNew fresh) {
+                        void* stream_, RingNew fresh, const AnalysisTables* adj) {
     XSQ_REQUIRE(!xin || (mean && scale), "xsq_slicqt_forward_xin: xin needs the mean / scale tables");
+    const float* d_tw = adj ? adj->tw : P->d_tw;
+    const float* d_Wf = adj ? adj->Wf : P->d_Wf;
+    const float* d_pool4f = adj ? adj->pool4f : P->d_pool4f;
     hipStream_t stream = (hipStream_t)stream_;
     const int rows = BC * S;
     XSQ_REQUIRE(S >= 2, "xsq_slicqt_forward: signal too short");
@@ -1057,34 +1072,138 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
         return XSQ_ERR_WORKSPACE;
     }
     if (lds_fft(P)) {
-        XSQ_PROF("slice_rfft", stream);
+        XSQ_PROF(adj ? "adjoint_slice_rfft" : "slice_rfft", stream);
         auto kernel = k_slice_rfft<512>;
 #if XSQ_PACKED_FFT_KERNELS
         if (P->packed_fft) kernel = k_slice_rfft<512, true>;
 #endif
         if (ring) kernel = k_slice_rfft<512, false, true>;
-        hipLaunchKernelGGL(kernel, dim3(rows), dim3(512), 0, stream, x, P->d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot, s0, ring,
+        hipLaunchKernelGGL(kernel, dim3(rows), dim3(512), 0, stream, x, d_tw, fft_tables(P), (float2*)U, S, n, P->h, x_rows, x_slot, s0, ring,
                            const_cast<float*>(x), fresh.x, fresh.first, fresh.stride);
     } else {
-        { XSQ_PROF("slice_window", stream);
-        hipLaunchKernelGGL(k_slice_window, dim3((P->L + 255) / 256, rows), dim3(256), 0, stream, x, P->d_tw, seg,
+        { XSQ_PROF(adj ? "adjoint_slice_window" : "slice_window", stream);
+        hipLaunchKernelGGL(k_slice_window, dim3((P->L + 255) / 256, rows), dim3(256), 0, stream, x, d_tw, seg,
                            S, n, P->L, P->h, x_rows, x_slot, s0, ring, const_cast<float*>(x), fresh.x, fresh.first, fresh.stride); }
-        { XSQ_PROF("rfft_L", stream); rc = run_fft(f, seg, U, fwork, stream); }
+        { XSQ_PROF(adj ? "adjoint_rfft_L" : "rfft_L", stream); rc = run_fft(f, seg, U, fwork, stream); }
         if (rc) return rc;
     }
     TileTable tt;
     rc = get_band_tiles(P, rows, &tt);
     if (rc) return rc;
-    BandFwdOp op{U, coef, P->d_bands, P->d_Wf, BC, S, P->nbins, P->L, xin, mean, scale, split};
+    BandFwdOp op{U, coef, P->d_bands, d_Wf, BC, S, P->nbins, P->L, xin, mean, scale, split};
     if (P->band_radix4 && P->nbands4) {
-        Band4Args a4{(const Band4Dev*)P->d_bands4, P->d_pool4f, U, coef, BC, S, P->nbins, P->L, 0, nullptr, 0, xin, mean, scale, split};
-        XSQ_PROF("band_analysis_dft4", stream);
+        Band4Args a4{(const Band4Dev*)P->d_bands4, d_pool4f, U, coef, BC, S, P->nbins, P->L, 0, nullptr, 0, xin, mean, scale, split};
+        XSQ_PROF(adj ? "adjoint_band_dft4" : "band_analysis_dft4", stream);
         if ((rc = launch_dft4<true>(P, a4, rows, 0, stream))) return rc;
     }
-    if (tt.ntiles) { XSQ_PROF("band_analysis_gemm", stream);
+    if (tt.ntiles) { XSQ_PROF(adj ? "adjoint_band_gemm" : "band_analysis_gemm", stream);
     hipLaunchKernelGGL((grouped_gemm_kernel<BandFwdOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
     XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
+}
+
+// ---- adjoint of the inverse transform: gy (BC, length) -> gradient arena ----
+// With y = xsq_slicqt_inverse(coef) and gy = dLoss/dy (zero outside [0, length)):
+//   gcoef[bc,j,s,:] = (-1)^(c_j/2) IFFT_Lg( a'_j[q] V[bc,s, c_j + sq(q)] ),  V[bc,s,:] = rfft_L( gypad[(2s-2)h : (2s+2)h] )
+//   a'_j[q] = [0 <= c_j + sq(q) <= L/2] w_k Lg_j^2 gd_j[q] / L,  w_0 = w_{L/2} = 1, w_k = 2 otherwise
+// -- the analysis with a slice window of ones and a' in place of g_j, so it runs on the analysis kernels over tables built
+// from a'.  a' is zero on the mirrored entries of the DC and Nyquist bands: what the kernels load there is multiplied away.
+int xsq_slicqt_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_t* c, const double* gd, double* out) {
+    XSQ_REQUIRE(Lg && c && gd && out, "xsq_slicqt_adjoint_window: null argument");
+    XSQ_REQUIRE(L > 0 && L % 4 == 0 && nbands >= 1, "xsq_slicqt_adjoint_window: L=%d nbands=%d", L, nbands);
+    int64_t off = 0;
+    for (int j = 0; j < nbands; ++j) {
+        const int n = Lg[j];
+        XSQ_REQUIRE(n > 0 && n % 2 == 0, "xsq_slicqt_adjoint_window: band %d has Lg=%d", j, n);
+        for (int q = 0; q < n; ++q) {
+            const int k = c[j] + (q < n / 2 ? q : q - n);
+            const double w = (k < 0 || k > L / 2) ? 0.0 : ((k == 0 || k == L / 2) ? 1.0 : 2.0);
+            out[off + q] = w * (double)n * (double)n * gd[off + q] / (double)L;
+        }
+        off += n;
+    }
+    return XSQ_OK;
+}
+
+namespace xsq {
+// the analysis tables of a', built and uploaded on first use (a synchronous upload: warm a plan up before capturing it)
+static int adjoint_tables(xsq_plan* P, AnalysisTables* out) {
+    std::lock_guard<std::mutex> lk(P->mu);
+    if (!P->adj_built) {
+        const int nbands = P->nbands;
+        std::vector<double> a(P->h_gd.size());
+        if (int rc = xsq_slicqt_adjoint_window(P->L, nbands, P->h_Lg.data(), P->h_c.data(), P->h_gd.data(), a.data())) return rc;
+        PlanArgs A{P->L, P->tr, nbands, P->h_Lg.data(), P->h_c.data(), nullptr, P->h_gd.data(), nullptr, std::vector<int64_t>(nbands, 0), a.data()};
+        for (int j = 1; j < nbands; ++j) A.g_off[j] = A.g_off[j - 1] + P->h_Lg[j - 1];
+        std::vector<float> Wf, Wi, pf, pi;
+        build_dense_matrices(P, A, Wf, Wi);
+        std::vector<Band4Dev> b4;
+        std::vector<char> is_short;
+        build_radix4_tables(P, A, b4, pf, pi, is_short, false);
+        // The kernels reach both pools through the offsets of the plan's ONE band table (d_bands: w_off; d_bands4: d_off, c_off,
+        // tw_off, win_off), so the adjoint's pools must be laid out exactly like the plan's: same builders, same band split (the
+        // process switches are read once, switches()), only the window entries differ.  The synthesis halves (Wi, pi) the
+        // builders also fill are dropped.  Held here rather than assumed:
+        XSQ_REQUIRE(Wf.size() == P->wf_floats && (int)b4.size() == P->nbands4 && (!P->nbands4 || pf.size() == P->pool4_floats),
+                    "xsq_slicqt_inverse_adjoint: the adjoint tables (%zu / %zu floats, %zu radix-4 bands) do not match the plan's (%zu / %zu, %d)",
+                    Wf.size(), pf.size(), b4.size(), P->wf_floats, P->pool4_floats, P->nbands4);
+        const std::vector<float> ones((size_t)P->L, 1.f);
+        float *tw = nullptr, *dWf = nullptr, *dpf = nullptr;
+        int rc = upload(tw, ones);
+        if (!rc) rc = upload(dWf, Wf);
+        if (!rc && P->nbands4) rc = upload(dpf, pf);
+        if (rc) { (void)hipFree(tw); (void)hipFree(dWf); (void)hipFree(dpf); return rc; }
+        P->d_adj_tw = tw; P->d_adj_Wf = dWf; P->d_adj_pool4f = dpf;
+        P->adj_built = true;
+    }
+    *out = AnalysisTables{P->d_adj_tw, P->d_adj_Wf, P->d_adj_pool4f};
+    return XSQ_OK;
+}
+
+// dst[i] += src[i], four floats per thread (arenas are multiples of four floats: T % 4 == 0)
+__global__ __launch_bounds__(256) void k_arena_add(float* __restrict__ dst, const float* __restrict__ src, int64_t quads) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= quads) return;
+    const float4 a = reinterpret_cast<const float4*>(src)[q];
+    float4 d = reinterpret_cast<float4*>(dst)[q];
+    d.x += a.x; d.y += a.y; d.z += a.z; d.w += a.w;
+    reinterpret_cast<float4*>(dst)[q] = d;
+}
+}  // namespace xsq
+
+// workspace: [scratch arena when accumulating |] seg | U | fft work
+size_t xsq_slicqt_inverse_adjoint_workspace(xsq_plan* P, int BC, int S, int accumulate) {
+    if (!P || BC <= 0 || S < 2) return 0;
+    const size_t rows = (size_t)BC * S;
+    FftPlan f;
+    if (!lds_fft(P) && get_fft(P, 0, (int)rows, &f)) return 0;
+    return (accumulate ? al256(rows * P->sumFT * 8) : 0) + al256(rows * P->L * 4) + al256(rows * P->nbins * 8) + al256(f.work_bytes) + 256;
+}
+
+int xsq_slicqt_inverse_adjoint(xsq_plan* P, const float* gy, int BC, int S, int64_t length, float* gcoef, int accumulate, void* ws,
+                               size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(P && gy && gcoef && ws, "xsq_slicqt_inverse_adjoint: null argument");
+    XSQ_REQUIRE(BC > 0 && S >= 2 && length > 0 && length <= (int64_t)2 * S * P->h, "xsq_slicqt_inverse_adjoint: BC=%d S=%d length=%lld", BC, S,
+                (long long)length);
+    const size_t need = xsq_slicqt_inverse_adjoint_workspace(P, BC, S, accumulate);
+    XSQ_REQUIRE(need && need <= ws_bytes, "xsq_slicqt_inverse_adjoint: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    AnalysisTables adj;
+    if (int rc = adjoint_tables(P, &adj)) return rc;
+    const size_t arena_bytes = (size_t)BC * S * P->sumFT * 8;
+    char* w = (char*)ws;
+    float* dst = gcoef;
+    if (accumulate) { dst = (float*)w; w += al256(arena_bytes); }
+    if (int rc = forward_impl(P, gy, nullptr, nullptr, BC, length, S, 0, 0, dst, nullptr, nullptr, nullptr, 0, w, ws_bytes - (size_t)(w - (char*)ws),
+                              stream_, RingNew{nullptr, 0, 0}, &adj))
+        return rc;
+    if (accumulate) {
+        hipStream_t stream = (hipStream_t)stream_;
+        const int64_t quads = (int64_t)(arena_bytes / 16);
+        XSQ_PROF("adjoint_accumulate", stream);
+        hipLaunchKernelGGL(k_arena_add, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, gcoef, dst, quads);
+        XSQ_HIP(hipGetLastError());
+    }
     return XSQ_OK;
 }
 

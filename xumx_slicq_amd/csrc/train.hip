@@ -616,7 +616,8 @@ struct xsq_train {
     // loss read-back without stalling the stream (xsq_train_step with loss_out == NULL): the per-block terms of the
     // last LOSS_RING steps land in pinned host memory behind an event each; xsq_train_loss waits for one of them
     static const int LOSS_RING = 4;
-    double* h_loss = nullptr;
+    double* h_loss = nullptr;               // LOSS_RING x nblocks x 2 per-block terms, then LOSS_RING SDR values (steps with the SDR term)
+    bool has_sdr[LOSS_RING] = {false, false, false, false};
     hipEvent_t ev_loss[LOSS_RING] = {nullptr, nullptr, nullptr, nullptr};
     int64_t seq = 0;                        // steps issued so far (the ticket of the next one)
 };
@@ -887,7 +888,7 @@ int xsq_train_create(xsq_train** out, int nblocks, const int32_t* F, const int32
     for (hipEvent_t& e : Tr->ev_fork) if (!rc && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = XSQ_ERR_HIP;
     if (!rc && hipEventCreateWithFlags(&Tr->ev_join, hipEventDisableTiming) != hipSuccess) rc = XSQ_ERR_HIP;
     for (hipEvent_t& e : Tr->ev_loss) if (!rc && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = XSQ_ERR_HIP;
-    if (!rc && hipHostMalloc((void**)&Tr->h_loss, (size_t)xsq_train::LOSS_RING * nblocks * 16, hipHostMallocDefault) != hipSuccess) rc = XSQ_ERR_HIP;
+    if (!rc && hipHostMalloc((void**)&Tr->h_loss, (size_t)xsq_train::LOSS_RING * (nblocks * 16 + 8), hipHostMallocDefault) != hipSuccess) rc = XSQ_ERR_HIP;
     if (rc == XSQ_ERR_HIP) set_error("xsq_train_create: side stream / events / pinned loss buffer");
     if (rc) { xsq_train_destroy(Tr); return rc; }
     *out = Tr;
@@ -937,6 +938,18 @@ size_t xsq_train_workspace(const xsq_train* Tr, int Bn, int S, int wiener) {
     return b;
 }
 
+// The SDR term of a step (xsq_train_step_sdr): the plan whose inverse turns the estimate arena into waveforms, the target
+// waveforms (4, B, 2, n), the weight of the term and the workspace behind the step's own.
+struct SdrStep { xsq_plan* plan; const float* yt; int64_t n; float mcoef; void* ws; size_t ws_bytes; };
+// region sizes of that workspace: waveforms (estimates, gradient) | criterion value | sdr.hip | inverse / adjoint transform
+static size_t sdr_transform_ws(xsq_plan* P, int Bn, int S) {
+    const size_t a = xsq_slicqt_inverse_workspace(P, 8 * Bn, S), b = xsq_slicqt_inverse_adjoint_workspace(P, 8 * Bn, S, 1);
+    return (a && b) ? std::max(a, b) : 0;
+}
+
+static int train_step_impl(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
+                           int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_, const SdrStep* sdr);
+
 // One step.  X: mix arena (2B ch), Yt: target arena (8B ch).  apply_update = 0 leaves the parameters untouched
 // (gradients stay readable through xsq_train_read).  loss_out: HOST double[2] (complex MSE, mask sum).
 int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
@@ -944,6 +957,36 @@ int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S
     XSQ_REQUIRE(Tr && X && Yt && ws, "xsq_train_step: null argument");
     XSQ_REQUIRE(Bn > 0 && S >= 3, "xsq_train_step: B=%d S=%d", Bn, S);
     XSQ_REQUIRE(ws_bytes >= xsq_train_workspace(Tr, Bn, S, wiener), "xsq_train_step: workspace too small");
+    return train_step_impl(Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, ws_bytes, stream_, nullptr);
+}
+
+size_t xsq_train_workspace_sdr(const xsq_train* Tr, xsq_plan* P, int Bn, int S, int wiener, int64_t n) {
+    const size_t base = xsq_train_workspace(Tr, Bn, S, wiener);
+    if (!base || !P || n <= 0) return 0;
+    const size_t sdr = xsq_sdr_loss_workspace(Bn, n), tr = sdr_transform_ws(P, Bn, S);
+    if (!sdr || !tr) return 0;
+    return al256(base) + 2 * al256((size_t)8 * Bn * n * 4) + al256((size_t)(1 + 84 * Bn) * 8) + al256(sdr) + tr;
+}
+
+// The step with the SDR term: loss = complex MSE + mask sum + mcoef * SDR(inverse sliCQT of the estimates, y_targets).
+// loss_out: HOST double[3] (complex MSE, mask sum, SDR criterion unweighted).
+int xsq_train_step_sdr(xsq_train* Tr, xsq_plan* P, const float* X, const float* Yt, const float* y_targets, int64_t n, float mcoef,
+                       int Bn, int S, int wiener, float lr, float wd, int apply_update, double* loss_out, void* ws, size_t ws_bytes,
+                       void* stream_) {
+    XSQ_REQUIRE(Tr && P && X && Yt && y_targets && ws, "xsq_train_step_sdr: null argument");
+    XSQ_REQUIRE(Bn > 0 && S >= 3 && n > 0 && xsq_plan_num_slices(P, n) == S, "xsq_train_step_sdr: B=%d S=%d n=%lld (S must be the plan's slice count of n)",
+                Bn, S, (long long)n);
+    XSQ_REQUIRE(mcoef > 0.f && std::isfinite(mcoef), "xsq_train_step_sdr: mcoef = %g (the term is on for mcoef > 0; use xsq_train_step without it)", (double)mcoef);
+    XSQ_REQUIRE(xsq_plan_num_blocks(P) == Tr->nblocks && xsq_plan_coefs_per_slice(P) == Tr->model->sumFT,
+                "xsq_train_step_sdr: the plan's block table is not the trainer's");
+    const size_t base = al256(xsq_train_workspace(Tr, Bn, S, wiener)), need = xsq_train_workspace_sdr(Tr, P, Bn, S, wiener, n);
+    XSQ_REQUIRE(need && ws_bytes >= need, "xsq_train_step_sdr: workspace too small");
+    const SdrStep sdr{P, y_targets, n, mcoef, (char*)ws + base, ws_bytes - base};
+    return train_step_impl(Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, base, stream_, &sdr);
+}
+
+static int train_step_impl(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
+                           int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_, const SdrStep* sdr) {
     hipStream_t stream = (hipStream_t)stream_;
     xsq_model* Mo = Tr->model;
     const int T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
@@ -1021,6 +1064,20 @@ int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S
         return rc;
     // ---- loss + its gradients (one pass) ------------------------------------------------------------
     if ((rc = loss_forward_backward(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Y, Yt, masks, Bn, S, d_loss, gY, gM, loss_ws, stream))) return rc;
+    // ---- SDR term: waveforms of the estimates, criterion + gradient on them, its adjoint added into gY --------------
+    double* d_sdr = nullptr;
+    if (sdr) {
+        char* sw = (char*)sdr->ws;
+        auto stake = [&](size_t bytes) { void* p = sw; sw += al256(bytes); return p; };
+        const size_t wave = (size_t)8 * Bn * sdr->n * 4;
+        float *yest = (float*)stake(wave), *gy = (float*)stake(wave);
+        d_sdr = (double*)stake((size_t)(1 + 84 * Bn) * 8);
+        void* sdr_ws = stake(xsq_sdr_loss_workspace(Bn, sdr->n));
+        const size_t tws = sdr->ws_bytes - (size_t)(sw - (char*)sdr->ws);
+        if ((rc = xsq_slicqt_inverse(sdr->plan, Y, 8 * Bn, S, sdr->n, yest, sw, tws, stream))) return rc;
+        if ((rc = sdr_loss(yest, sdr->yt, 2 * Bn, sdr->n, sdr->mcoef, d_sdr, gy, sdr_ws, stream))) return rc;
+        if ((rc = xsq_slicqt_inverse_adjoint(sdr->plan, gy, 8 * Bn, S, sdr->n, gY, 1, sw, tws, stream))) return rc;
+    }
     // (Wiener-EM: the last pass of its backward forms the mask gradient itself -- no gradient arena written and re-read)
     if (wiener && (rc = wiener_em_backward(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), X, nullptr, masks, gY, Bn, S, 5000, Bn, wst, wbst, stream, gM)))
         return rc;
@@ -1110,12 +1167,15 @@ int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S
     const int64_t ticket = Tr->seq++;
     const int slot = (int)(ticket % xsq_train::LOSS_RING);
     XSQ_HIP(hipMemcpyAsync(Tr->h_loss + (size_t)slot * Tr->nblocks * 2, d_loss, (size_t)Tr->nblocks * 16, hipMemcpyDeviceToHost, stream));
+    Tr->has_sdr[slot] = d_sdr != nullptr;
+    if (d_sdr) XSQ_HIP(hipMemcpyAsync(Tr->h_loss + (size_t)xsq_train::LOSS_RING * Tr->nblocks * 2 + slot, d_sdr, 8, hipMemcpyDeviceToHost, stream));
     XSQ_HIP(hipEventRecord(Tr->ev_loss[slot], stream));
     // the next step's weights in GEMM layout (see above): BEHIND the loss event, so that a caller who waits for the loss --
     // the step and its update are complete by then -- does not wait for them
     if (apply_update) gather_pools();
     // loss_out given: wait here, as loss.item() does every step in the reference (training.py:110)
-    return loss_out ? xsq_train_loss(Tr, ticket, loss_out) : XSQ_OK;
+    if (!loss_out) return XSQ_OK;
+    return sdr ? xsq_train_loss_sdr(Tr, ticket, loss_out) : xsq_train_loss(Tr, ticket, loss_out);
 }
 
 int64_t xsq_train_ticket(xsq_train* Tr) { return Tr ? Tr->seq - 1 : XSQ_ERR_ARG; }
@@ -1131,6 +1191,14 @@ int xsq_train_loss(xsq_train* Tr, int64_t ticket, double* loss_out) {
     loss_out[0] = loss_out[1] = 0.0;
     for (int b = 0; b < Tr->nblocks; ++b) { loss_out[0] += per[2 * b]; loss_out[1] += per[2 * b + 1]; }
     loss_out[0] /= Tr->nblocks; loss_out[1] /= Tr->nblocks;
+    return XSQ_OK;
+}
+
+// the same with the SDR criterion (unweighted) of that step in loss_out[2]; 0 for a step issued without the term
+int xsq_train_loss_sdr(xsq_train* Tr, int64_t ticket, double* loss_out) {
+    if (int rc = xsq_train_loss(Tr, ticket, loss_out)) return rc;
+    const int slot = (int)(ticket % xsq_train::LOSS_RING);
+    loss_out[2] = Tr->has_sdr[slot] ? Tr->h_loss[(size_t)xsq_train::LOSS_RING * Tr->nblocks * 2 + slot] : 0.0;
     return XSQ_OK;
 }
 

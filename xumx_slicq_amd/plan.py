@@ -102,6 +102,19 @@ class SliCQPlan:
     def block_shapes(self) -> List[Tuple[int, int]]:
         return [(F, T) for (_, F, T) in self.blocks]
 
+    def adjoint_window(self) -> np.ndarray:
+        """(sum Lg,) fp64, laid out like ``gd``: the window a' of the adjoint of the inverse transform
+        (xsq_slicqt_adjoint_window, host arithmetic: no device needed) -- the table the library builds the adjoint's
+        analysis matrices from."""
+        from . import _lib
+        Lg = np.ascontiguousarray(self.Lg, dtype=np.int32)
+        c = np.ascontiguousarray(self.c, dtype=np.int32)
+        gd = np.ascontiguousarray(self.gd, dtype=np.float64)
+        out = np.empty_like(gd)
+        _lib.check(_lib.lib.xsq_slicqt_adjoint_window(self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, gd.ctypes.data,
+                                                      out.ctypes.data), "xsq_slicqt_adjoint_window")
+        return out
+
 
 def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: float = 22050.0,
                fs: float = 44100.0, min_win: int = 16) -> SliCQPlan:

@@ -1,12 +1,15 @@
 """Mirror of the training half of /root/reference/xumx_slicq_v2/training.py:34-112 (``loop`` with
 ``train=True``) on the HIP library: one call = forward with BatchNorm on batch statistics, ComplexMSE +
-MaskSum loss, backward of every trainable tensor, AdamW update (training.py:391-393 defaults).
+MaskSum loss (+ ``sdr_mcoef`` x the SDR criterion on the estimates' waveforms when ``sdr_mcoef > 0``, training.py:94-103),
+backward of every trainable tensor, AdamW update (training.py:391-393 defaults).
 
 The reference hands the step to torch autograd + ``torch.optim.AdamW``; here the whole step is
 ``xsq_train_step`` (csrc/train.hip) over flat parameter / gradient / moment pools that keep the
 reference's state_dict order, so a checkpoint of the reference loads, trains and saves unchanged.
-The SDR term (auraloss, off by default: ``--sdr-mcoef -1``), the LSTM variant, the LR scheduler /
-early stopping / tensorboard logging around the loop are outside the hot path."""
+With the SDR term on the step is ``xsq_train_step_sdr``: the estimates' inverse sliCQT, the SD-SDR passes (csrc/sdr.hip) and
+the adjoint of the inverse transform into the estimates' gradient run inside it; with the term off (the default,
+``--sdr-mcoef -1``) the step is the one it was.  The LSTM variant, the LR scheduler / early stopping / tensorboard logging
+around the loop are outside the hot path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,10 +28,15 @@ class PendingLoss:
     """Loss of a step issued with ``wait=False``: ``result()`` (or indexing / iteration, like the tuple ``step``
     returns) blocks until THAT step has finished on the device.  Valid for the trainer's last four steps."""
 
-    def __init__(self, trainer: "Trainer", ticket: int):
-        self._trainer, self._ticket, self._value = trainer, int(ticket), None
+    def __init__(self, trainer: "Trainer", ticket: int, sdr_mcoef: float = -1.0):
+        self._trainer, self._ticket, self._value, self._sdr_mcoef = trainer, int(ticket), None, float(sdr_mcoef)
 
-    def result(self) -> Tuple[float, float, float]:
+    def result(self) -> Tuple[float, ...]:
+        if self._value is None and self._sdr_mcoef > 0:
+            out = (C.c_double * 3)()
+            _lib.check(_lib.lib.xsq_train_loss_sdr(self._trainer._h, self._ticket, out), "xsq_train_loss_sdr")
+            mse, mask, sdr = float(out[0]), float(out[1]), float(out[2])
+            self._value = (mse + mask + self._sdr_mcoef * sdr, mse, mask, sdr)
         if self._value is None:
             out = (C.c_double * 2)()
             _lib.check(_lib.lib.xsq_train_loss(self._trainer._h, self._ticket, out), "xsq_train_loss")
@@ -47,13 +55,16 @@ class Trainer:
     """Owns the device-side training state of one ``Unmix``.
 
     ``step(x, y_targets)`` = the body of ``for x, y in pbar`` (training.py:66-110) and returns
-    ``(loss, mse_loss, mask_loss)`` as python floats; ``gradients()`` exposes what
+    ``(loss, mse_loss, mask_loss)`` as python floats -- with ``sdr_mcoef > 0`` (training.py:94: the term is on)
+    ``(loss, mse_loss, mask_loss, sdr_loss)``, ``sdr_loss`` the unweighted criterion and
+    ``loss = mse_loss + mask_loss + sdr_mcoef * sdr_loss``; ``gradients()`` exposes what
     ``loss.backward()`` would have left in ``.grad``; ``state_dict()`` / ``sync_to(unmix)`` hand
     the trained tensors back in the reference's layout."""
 
     def __init__(self, unmix: Unmix, encoder, lr: float = 1e-3, weight_decay: float = 1e-5,
-                 device: str | torch.device = "cuda", precision: str = "fp32"):
+                 device: str | torch.device = "cuda", precision: str = "fp32", sdr_mcoef: float = -1.0):
         self.device = torch.device(device)
+        self.sdr_mcoef = float(sdr_mcoef)
         if self.device.type != "cuda":
             raise _lib.XsqError("training runs on a ROCm device only; there is no CPU fallback")
         self.nsgt, self.insgt, self.cnorm = encoder
@@ -101,34 +112,46 @@ class Trainer:
             pass
 
     # -- one step ------------------------------------------------------------------------
-    def step_arena(self, X: Tensor, Yt: Tensor, B: int, S: int, apply_update: bool = True, wait: bool = True):
-        """X: mix arena (2B channels), Yt: target arena (8B channels), both flat fp32 on the device.
-        ``wait=False``: returns a ``PendingLoss`` without waiting for the device (the next step can be issued before
-        this one's loss is looked at; the reference's ``loss.item()`` every step, training.py:110, is ``wait=True``)."""
+    def _issue(self, key, workspace, launch, keep, nterms: int, apply_update: bool, wait: bool):
+        """One step through either entry point: ``workspace()`` -> bytes (cached per ``key``), ``launch(out, ws)`` -> status with
+        ``out`` the HOST double[nterms] the step waits for or None, ``keep`` the tensors its kernels read."""
+        sdr = nterms == 3
+        name = "xsq_train_step_sdr" if sdr else "xsq_train_step"
         with torch.cuda.device(self.device):
-            need = self.__dict__.setdefault("_need", {}).get((B, S))
+            need = self.__dict__.setdefault("_need", {}).get(key)
             if need is None:
-                need = _lib.lib.xsq_train_workspace(self._h, B, S, 1 if self.wiener else 0)
+                need = workspace()
                 if need == 0:
-                    raise _lib.XsqError("xsq_train_workspace: bad shape")
-                self._need[(B, S)] = need
+                    raise _lib.XsqError(("xsq_train_workspace_sdr" if sdr else "xsq_train_workspace") + ": bad shape")
+                self._need[key] = need
             if self._ws is None or self._ws.numel() < need:
                 self._ws = None
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            out = (C.c_double * 2)() if wait else None
-            _lib.check(_lib.lib.xsq_train_step(self._h, X.data_ptr(), Yt.data_ptr(), B, S, 1 if self.wiener else 0,
-                                               self.lr, self.weight_decay, 1 if apply_update else 0, out,
-                                               self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr()),
-                       "xsq_train_step")
+            out = (C.c_double * nterms)() if wait else None
+            _lib.check(launch(out, self._ws), name)
             if not wait:     # the arenas must outlive the kernels that read them: hand them to the pending object
-                pending = PendingLoss(self, int(_lib.lib.xsq_train_ticket(self._h)))
-                pending._keep = (X, Yt)
+                pending = PendingLoss(self, int(_lib.lib.xsq_train_ticket(self._h)), self.sdr_mcoef if sdr else -1.0)
+                pending._keep = keep
         if apply_update:
             self.steps += 1
         if not wait:
             return pending
         mse, mask = float(out[0]), float(out[1])
-        return mse + mask, mse, mask
+        if not sdr:
+            return mse + mask, mse, mask
+        return mse + mask + self.sdr_mcoef * float(out[2]), mse, mask, float(out[2])
+
+    def step_arena(self, X: Tensor, Yt: Tensor, B: int, S: int, apply_update: bool = True, wait: bool = True):
+        """X: mix arena (2B channels), Yt: target arena (8B channels), both flat fp32 on the device.
+        ``wait=False``: returns a ``PendingLoss`` without waiting for the device (the next step can be issued before
+        this one's loss is looked at; the reference's ``loss.item()`` every step, training.py:110, is ``wait=True``)."""
+        if self.sdr_mcoef > 0:
+            raise _lib.XsqError("step_arena has no waveforms: the SDR term (sdr_mcoef > 0) needs step(x, y_targets)")
+        w = 1 if self.wiener else 0
+        return self._issue((B, S), lambda: _lib.lib.xsq_train_workspace(self._h, B, S, w),
+                           lambda out, ws: _lib.lib.xsq_train_step(self._h, X.data_ptr(), Yt.data_ptr(), B, S, w, self.lr, self.weight_decay,
+                                                                   1 if apply_update else 0, out, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                           (X, Yt), 2, apply_update, wait)
 
     @torch.no_grad()
     def step(self, x: Tensor, y_targets: Tensor, apply_update: bool = True, wait: bool = True):
@@ -152,7 +175,20 @@ class Trainer:
         Ytg.record_stream(main)
         if len(lead) != 2 or lead[1] != 2 or lead_t != (4, lead[0], 2) or S != S_t:
             raise ValueError(f"expected x (B, 2, N) and y_targets (4, B, 2, N); got arenas {lead} / {lead_t}")
+        if self.sdr_mcoef > 0:
+            return self._step_sdr(X, Ytg, y_targets.contiguous(), lead[0], S, apply_update, wait)
         return self.step_arena(X, Ytg, lead[0], S, apply_update, wait)
+
+    def _step_sdr(self, X: Tensor, Yt: Tensor, y_targets: Tensor, B: int, S: int, apply_update: bool, wait: bool):
+        """The step with the SDR term (xsq_train_step_sdr): the arenas of ``step`` plus the target waveforms."""
+        n, w = int(y_targets.shape[-1]), 1 if self.wiener else 0
+        plan = self.nsgt.nsgt.nsgt.handle(self.device)
+        return self._issue((B, S, n), lambda: _lib.lib.xsq_train_workspace_sdr(self._h, plan, B, S, w, n),
+                           lambda out, ws: _lib.lib.xsq_train_step_sdr(self._h, plan, X.data_ptr(), Yt.data_ptr(), y_targets.data_ptr(), n,
+                                                                       self.sdr_mcoef, B, S, w, self.lr, self.weight_decay,
+                                                                       1 if apply_update else 0, out, ws.data_ptr(), ws.numel(),
+                                                                       _lib.stream_ptr()),
+                           (X, Yt, y_targets), 3, apply_update, wait)
 
     # -- state ---------------------------------------------------------------------------
     def _read(self, what: int) -> "OrderedDict[str, Tensor]":

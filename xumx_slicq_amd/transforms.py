@@ -207,6 +207,24 @@ class SliCQEngine:
                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_rows")
         return y
 
+    def backward_adjoint(self, gy: Tensor, S: int, out: Tensor = None) -> Tensor:
+        """Adjoint of ``backward``: gy (BC, length) = dLoss/dy on a ROCm device -> the arena of dLoss/dcoef for BC channels
+        and S slices (xsq_slicqt_inverse_adjoint).  With ``out`` (an arena of that shape) the result is added to it."""
+        gy = gy.to(torch.float32).contiguous()
+        BC, length = gy.shape
+        h = self.handle(gy.device)
+        with torch.cuda.device(gy.device):
+            if out is not None:
+                assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == self.table.numel(BC, S)
+            arena = out if out is not None else torch.empty(self.table.numel(BC, S), dtype=torch.float32, device=gy.device)
+            nbytes = _lib.lib.xsq_slicqt_inverse_adjoint_workspace(h, BC, S, int(out is not None))
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_slicqt_inverse_adjoint_workspace: " + _lib.last_error())
+            ws = self.workspace(gy.device, nbytes)
+            _lib.check(_lib.lib.xsq_slicqt_inverse_adjoint(h, gy.data_ptr(), BC, S, length, arena.data_ptr(), int(out is not None),
+                                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_adjoint")
+        return arena
+
     def backward_masked(self, masks: Tensor, mix: Tensor, BC: int, BCx: int, S: int, length: int, out: Tensor,
                         row_offsets: Tensor) -> Tensor:
         """Inverse transform of masks[bc] * mix[bc % BCx] without materialising the product
