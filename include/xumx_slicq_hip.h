@@ -281,6 +281,30 @@ int xsq_place_rows(const float* src, float* dst, const int64_t* table, int nrows
 int xsq_resample(const float* x, int64_t x_stride, int rows, int64_t len_in, float* y, int64_t y_stride, int64_t len_out,
                  const float* table, const int32_t* first_tap, int o, int n, int span, int width, void* stream);
 
+/* ---- one training batch from the device-resident stems ---------------------------------------------------------------
+ * Replaces MUSDBDataset.__getitem__ with random_track_mix (data.py:316-390: per source a random track, an excerpt,
+ * `audio * g` of data.py:183-188, the channel flip of data.py:191-196, torch.stack + stems.sum(0) of data.py:362-364) and
+ * the DataLoader's collate of B items, for stems that stay on the device (xumx_slicq_amd/data.py).  ONE launch per step.
+ *   pool     DEVICE, 16-byte aligned; fp32 (XSQ_POOL_FP32) or the files' int16 (XSQ_POOL_PCM16, value / 32768).  A track is
+ *            8 rows of `len` samples, row (source column s, channel c) at element tracks[2t] + (2s + c) * round_up(len, 8):
+ *            every row starts 16-byte aligned in both dtypes.
+ *   tracks   DEVICE int64 [ntracks][2]: element offset of the track's first row (a multiple of 8), len in samples
+ *   draws    DEVICE int32 [nsteps][B][4 source columns][4]: track, start, gain (fp32 bits), swap (0 / 1); `step` picks
+ *            the B records of this launch.  The table is trusted, as row_offsets of xsq_crossfade_place is: the caller
+ *            guarantees 0 <= track < ntracks and 0 <= start, and start + n <= len unless the track is shorter than n.
+ *   target_of_column  DEVICE int32 [4]: the plane of y that source column s lands in
+ * With v = the pool sample of track t(b, s), channel c ^ swap(b, s), at start(b, s) + i (0 where start + i >= len: a short
+ * track is zero-padded at its tail; pcm16 converts exactly, float(int) * 2^-15):
+ *   y[target_of_column[s], b, c, i] = fl32(gain(b, s) * v)                     y (4, B, 2, n) contiguous fp32
+ *   x[b, c, i] = ((y_0 + y_1) + y_2) + y_3   in fp32, in source-column order   x (B, 2, n) contiguous fp32
+ * The product is rounded BEFORE the sums (no fused multiply-add), as torch rounds `audio * g` before `stems.sum(0)`.
+ * Every element of x and y is written exactly once; nothing is read at or past a row's len.  1 <= n < 2^31,
+ * 1 <= B <= 32767.  No allocation, no synchronisation: capturable into a graph.                                       */
+#define XSQ_POOL_FP32 0
+#define XSQ_POOL_PCM16 1
+int xsq_batch_assemble(const void* pool, int pool_dtype, const int64_t* tracks, int ntracks, const int32_t* draws,
+                       int64_t step, int B, int64_t n, const int32_t* target_of_column, float* x, float* y, void* stream);
+
 /* ---- in-place exchange of stems between the ranks of the sharded path (RCCL over xGMI) -------------------------------
  * The form of "the final waveform concat" (separator.py:229-231 across ranks) that needs no packing buffer and no
  * placement pass: every rank holds the SAME flat per-track layout, its kernels write the rows it owns in place

@@ -158,6 +158,7 @@ _SIGS = {
     "xsq_model_set_wiener_options": (C.c_int, [_vp, C.c_int, C.c_int]),
     "xsq_crossfade_place_sources": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                               C.c_int, _vp]),
+    "xsq_batch_assemble": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

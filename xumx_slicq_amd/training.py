@@ -8,13 +8,21 @@ The reference hands the step to torch autograd + ``torch.optim.AdamW``; here the
 reference's state_dict order, so a checkpoint of the reference loads, trains and saves unchanged.
 With the SDR term on the step is ``xsq_train_step_sdr``: the estimates' inverse sliCQT, the SD-SDR passes (csrc/sdr.hip) and
 the adjoint of the inverse transform into the estimates' gradient run inside it; with the term off (the default,
-``--sdr-mcoef -1``) the step is the one it was.  The LSTM variant, the LR scheduler / early stopping / tensorboard logging
-around the loop are outside the hot path."""
+``--sdr-mcoef -1``) the step is the one it was.
+
+``Trainer.fit`` (``fit`` below) is the loop ``training_main`` has around the step (training.py:478-556): per epoch a
+training pass over batches that ``data.DeviceDataset`` assembles on the device, a validation pass, the plateau LR
+schedule, early stopping and the reference's checkpoint files; ``python -m xumx_slicq_amd.training`` is its command line.
+The LSTM variant, ``PeripheryDataset``, tensorboard / torchinfo / tqdm output and data-parallel training are not mirrored."""
 from __future__ import annotations
 
 import ctypes as C
+import json
+import math
+import os
+import time
 from collections import OrderedDict
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -69,6 +77,7 @@ class Trainer:
             raise _lib.XsqError("training runs on a ROCm device only; there is no CPU fallback")
         self.nsgt, self.insgt, self.cnorm = encoder
         self.lr, self.weight_decay = float(lr), float(weight_decay)
+        self.unmix = unmix                       # fit() hands the trained tensors back to it for validation and checkpoints
         self.table = unmix.table
         self._F, self._T = unmix._F, unmix._T
         causal = {blk.causal for blk in unmix.sliced_umx}
@@ -300,3 +309,212 @@ class Trainer:
         unmix.load_state_dict(sd, strict=True)
         self._synced = self.steps
         return unmix
+
+    # -- the loop around the step (training.py:34-112, 478-556) -------------------------------------
+    def train_epoch(self, train, table) -> float:
+        """One training pass (training.py:34-112, train=True) over the batches of ``table``: every step is issued with
+        ``wait=False``, at most three are in flight, and losses are read as they resolve.  Returns the plain mean of the
+        batch losses (the reference's ``_AverageMeter`` weights every batch by ``x.size(1)``, a constant)."""
+        pending, losses = [], []
+        for k in range(len(table)):
+            x, y = train.batch(table, k)
+            pending.append(self.step(x, y, wait=False))
+            if len(pending) == 3:
+                losses.append(pending.pop(0)[0])
+        losses.extend(p[0] for p in pending)
+        return float(np.mean(losses))
+
+    def validate(self, valid, valid_chunk: int = 2621440) -> float:
+        """One validation pass (training.py:34-112, train=False): the unmix takes the current weights (``sync_to``) and
+        ``loss.validation_step`` runs over ``valid.pieces(i, valid_chunk)`` of every track; the mean over pieces.
+        A piece below the model's minimum length (half a slice + 1, separator.py:162) is zero-padded to it."""
+        from .loss import validation_step
+        unmix = self.sync_to(self.unmix).eval()
+        encoder = (self.nsgt, self.insgt, self.cnorm)
+        floor = self.nsgt.nsgt.plan.L // 2 + 1
+        losses = []
+        for i in range(len(valid)):
+            for x, y in valid.pieces(i, valid_chunk):
+                if x.shape[-1] < floor:
+                    pad = floor - x.shape[-1]
+                    x, y = torch.nn.functional.pad(x, (0, pad)), torch.nn.functional.pad(y, (0, pad))
+                losses.append(validation_step(unmix, encoder, x, y, sdr_mcoef=self.sdr_mcoef)[0])
+        return float(np.mean(losses))
+
+    def checkpoint_state(self) -> Tuple[dict, dict]:
+        """(``unmix.state_dict()`` with the current weights, ``optimizer.state_dict()``): training.py:524-526.  The tensors
+        go into a plain OrderedDict: the module's own carries a ``_metadata`` attribute whose "version" entry of the root is
+        the bound method ``Unmix._version`` -- pickling it would drag the whole module into the file, and
+        ``torch.load(weights_only=True)`` (load_target_models) refuses it."""
+        return OrderedDict(self.sync_to(self.unmix).state_dict()), self.optimizer_state_dict()
+
+    def load_checkpoint(self, state_dict: dict, optimizer: dict):
+        """training.py:419-420 (the reference loads with strict=False; every trained tensor must be there here)."""
+        self.load_state_dict({k: state_dict[k] for k, _ in self._spec})
+        self.load_optimizer_state_dict(optimizer)
+        self.unmix.load_state_dict(state_dict, strict=False)
+        self._synced = self.steps
+
+    def model_args(self) -> dict:
+        """The ``args`` of xumx_slicq_v2.json that ``separator.load_target_models`` reads (training.py:536)."""
+        plan = self.nsgt.nsgt.plan
+        return {"fscale": plan.scale, "fbins": int(plan.fbins), "fmin": float(plan.fmin), "sample_rate": float(plan.fs),
+                "nb_channels": 2, "realtime": not self.wiener, "lr": self.lr, "weight_decay": self.weight_decay,
+                "sdr_mcoef": self.sdr_mcoef, "precision": self.precision}
+
+    def fit(self, train, valid, epochs: int, **kwargs) -> dict:
+        """``fit(self, train, valid, epochs, ...)`` below."""
+        return fit(self, train, valid, epochs, **kwargs)
+
+
+class _EarlyStopping:
+    """training.py:590-630 (mode "min", min_delta 0): ``step`` returns True when training should stop -- after
+    ``patience`` epochs without a new best, and at once on a NaN loss."""
+
+    def __init__(self, patience: int = 10):
+        self.patience, self.best, self.num_bad_epochs = patience, None, 0
+
+    def step(self, metrics) -> bool:
+        if self.best is None:
+            self.best = metrics
+            return False
+        if math.isnan(metrics):
+            return True
+        if self.patience == 0 or metrics < self.best:
+            self.num_bad_epochs = 0
+            self.best = metrics
+        else:
+            self.num_bad_epochs += 1
+        return self.num_bad_epochs >= self.patience
+
+
+CHECKPOINT, WEIGHTS, RESULTS = "xumx_slicq_v2.chkpnt", "xumx_slicq_v2.pth", "xumx_slicq_v2.json"
+
+
+def fit(trainer, train, valid, epochs: int, batch_size: int = 32, seq_dur: float = 2.0, samples_per_track: int = 64,
+        seed: int = 42, patience: int = 1000, lr_decay_patience: int = 80, lr_decay_gamma: float = 0.3,
+        model_path: Optional[str] = None, valid_chunk: int = 2621440, quiet: bool = True) -> dict:
+    """The epoch loop of ``training_main`` (training.py:478-556) around ``trainer`` (a ``Trainer``): epochs 1 .. ``epochs``,
+    each ``train.draw_epoch(seed, epoch, ...)`` + ``trainer.train_epoch`` and ``trainer.validate(valid, valid_chunk)``;
+    ``torch.optim.lr_scheduler.ReduceLROnPlateau(factor=lr_decay_gamma, patience=lr_decay_patience, cooldown=10)`` on
+    the validation loss (training.py:401-406) -- it steps a one-parameter shim optimizer that carries ``trainer.lr``, so
+    its ``state_dict()`` is the reference's, and the shim's lr is copied back to ``trainer.lr`` after every step --;
+    ``_EarlyStopping(patience)``; and, with ``model_path``, per epoch the reference's files (training.py:521-546, 563-568):
+    ``xumx_slicq_v2.chkpnt`` {epoch, state_dict, best_loss, optimizer, scheduler}, ``xumx_slicq_v2.pth`` (the weights) on
+    a best epoch, ``xumx_slicq_v2.json`` (histories + the ``args`` ``load_target_models`` reads).  A ``model_path`` that
+    already holds a checkpoint is resumed (training.py:411-435).  Returns the history dict the json holds.
+
+    Departures from the reference: validation runs over pieces of ``valid_chunk`` samples (the Separator's chunk size)
+    instead of whole tracks, so that no kernel's 32-bit range depends on a track's length; a resumed run continues with
+    epoch ``epochs_trained + 1`` (the reference's ``trange`` starts at ``epochs_trained`` and repeats that epoch number);
+    an epoch's time is in the json that epoch writes (the reference appends it after writing); no tensorboard, torchinfo
+    or tqdm: ``quiet=False`` prints one line per epoch."""
+    shim = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=trainer.lr)
+    scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(shim, factor=lr_decay_gamma, patience=lr_decay_patience, cooldown=10)
+    es = _EarlyStopping(patience=patience)
+    hist = {"epochs_trained": 0, "best_loss": None, "best_epoch": 0, "train_loss_history": [], "valid_loss_history": [],
+            "train_time_history": [], "num_bad_epochs": 0}
+    if model_path is not None:
+        os.makedirs(model_path, exist_ok=True)
+        if os.path.exists(os.path.join(model_path, CHECKPOINT)):
+            with open(os.path.join(model_path, RESULTS), "r") as stream:
+                hist = {k: v for k, v in json.load(stream).items() if k in hist}
+            checkpoint = torch.load(os.path.join(model_path, CHECKPOINT), map_location="cpu", weights_only=False)
+            trainer.load_checkpoint(checkpoint["state_dict"], checkpoint["optimizer"])
+            scheduler.load_state_dict(checkpoint["scheduler"])
+            shim.param_groups[0]["lr"] = trainer.lr
+            es.best, es.num_bad_epochs = hist["best_loss"], hist["num_bad_epochs"]
+    for epoch in range(hist["epochs_trained"] + 1, epochs + 1):
+        end = time.time()
+        table = train.draw_epoch(seed, epoch, batch_size, seq_dur, samples_per_track)
+        train_loss = trainer.train_epoch(train, table)
+        valid_loss = trainer.validate(valid, valid_chunk)
+        scheduler.step(valid_loss)
+        trainer.lr = float(shim.param_groups[0]["lr"])
+        hist["train_loss_history"].append(train_loss)
+        hist["valid_loss_history"].append(valid_loss)
+        stop = es.step(valid_loss)
+        is_best = valid_loss == es.best
+        if is_best:
+            hist["best_epoch"] = epoch
+        hist["train_time_history"].append(time.time() - end)
+        hist.update(epochs_trained=epoch, best_loss=es.best, num_bad_epochs=es.num_bad_epochs)
+        if model_path is not None:
+            state_dict, optimizer = trainer.checkpoint_state()
+            torch.save({"epoch": epoch + 1, "state_dict": state_dict, "best_loss": es.best, "optimizer": optimizer,
+                        "scheduler": scheduler.state_dict()}, os.path.join(model_path, CHECKPOINT))
+            if is_best:
+                torch.save(state_dict, os.path.join(model_path, WEIGHTS))
+            args = dict(trainer.model_args(), seq_dur=seq_dur, batch_size=batch_size, samples_per_track=samples_per_track,
+                        seed=seed, epochs=epochs, patience=patience, lr_decay_patience=lr_decay_patience,
+                        lr_decay_gamma=lr_decay_gamma, model_path=str(model_path))
+            with open(os.path.join(model_path, RESULTS), "w") as outfile:
+                outfile.write(json.dumps(dict(hist, args=args), indent=4, sort_keys=True))
+        if not quiet:
+            print(f"epoch {epoch}: train_loss {train_loss:.6f} valid_loss {valid_loss:.6f} lr {trainer.lr:.3g} "
+                  f"({hist['train_time_history'][-1]:.1f} s){' best' if is_best else ''}", flush=True)
+        if stop:
+            if not quiet:
+                print("Apply Early Stopping")
+            break
+    return hist
+
+
+def main(argv=None) -> dict:
+    """``python -m xumx_slicq_amd.training``: ``training_main`` (training.py:157-556) for a directory of stems in the
+    MUSDB18-HQ layout.  The reference's flag names and defaults; ``--root`` replaces ``--musdb-root``, ``--valid`` names the
+    validation tracks (musdb's own train / valid split list is part of the musdb package, which is not a dependency),
+    ``--storage`` and ``--precision`` are additions."""
+    import argparse
+    from .data import DeviceDataset
+    from .model import Unmix
+    from .statistics import get_statistics
+    from .transforms import ComplexNorm, NSGTBase, make_filterbanks
+    ap = argparse.ArgumentParser(description="xumx-sliCQ-V2 Trainer (MI355X)")
+    ap.add_argument("--root", required=True, help="<root>/<track>/{vocals,drums,bass,other}.wav")
+    ap.add_argument("--valid", required=True, help="comma-separated names of the validation tracks")
+    ap.add_argument("--model-path", required=True)
+    ap.add_argument("--samples-per-track", type=int, default=64)
+    ap.add_argument("--epochs", type=int, default=1000)
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--lr", type=float, default=0.001)
+    ap.add_argument("--patience", type=int, default=1000)
+    ap.add_argument("--lr-decay-patience", type=int, default=80)
+    ap.add_argument("--lr-decay-gamma", type=float, default=0.3)
+    ap.add_argument("--weight-decay", type=float, default=0.00001)
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--sdr-mcoef", type=float, default=-1.0)
+    ap.add_argument("--realtime", action="store_true", default=False)
+    ap.add_argument("--seq-dur", type=float, default=2.0)
+    ap.add_argument("--fscale", choices=("bark", "mel"), default="bark")
+    ap.add_argument("--fbins", type=int, default=262)
+    ap.add_argument("--fmin", type=float, default=32.9)
+    ap.add_argument("--storage", choices=("pcm16", "fp32"), default="pcm16")
+    ap.add_argument("--precision", choices=("fp32", "bf16", "bf16x6"), default="fp32")
+    ap.add_argument("--quiet", action="store_true", default=False)
+    a = ap.parse_args(argv)
+    device = torch.device("cuda")
+    valid_names = [v for v in a.valid.split(",") if v]
+    names = sorted(d for d in os.listdir(a.root) if os.path.isdir(os.path.join(a.root, d)))
+    missing = [v for v in valid_names if v not in names]
+    if missing or not valid_names:
+        raise SystemExit(f"--valid: {missing or 'no track named'} (tracks under {a.root}: {len(names)})")
+    train = DeviceDataset.from_directory(a.root, [n for n in names if n not in valid_names], storage=a.storage, device=device)
+    valid = DeviceDataset.from_directory(a.root, valid_names, storage=a.storage, device=device)
+    nsgt_base = NSGTBase(a.fscale, a.fbins, a.fmin, fs=train.sample_rate, device=device)
+    nsgt, insgt = make_filterbanks(nsgt_base, sample_rate=train.sample_rate)
+    encoder = (nsgt.to(device), insgt.to(device), ComplexNorm().to(device))
+    jagged, _ = nsgt_base.predict_input_size(a.batch_size, 2, a.seq_dur)
+    means = stds = None
+    if not os.path.exists(os.path.join(a.model_path, CHECKPOINT)):          # data whitening (training.py:371-375)
+        means, stds = get_statistics(encoder, (x[0] for i in range(len(train)) for x, _ in train.pieces(i, int(train.lengths[i]))))
+    unmix = Unmix(encoder[2](jagged), realtime=a.realtime, input_means=means, input_scales=stds).to(device)
+    trainer = Trainer(unmix, encoder, lr=a.lr, weight_decay=a.weight_decay, device=device, precision=a.precision,
+                      sdr_mcoef=a.sdr_mcoef)
+    return trainer.fit(train, valid, a.epochs, batch_size=a.batch_size, seq_dur=a.seq_dur, samples_per_track=a.samples_per_track,
+                       seed=a.seed, patience=a.patience, lr_decay_patience=a.lr_decay_patience, lr_decay_gamma=a.lr_decay_gamma,
+                       model_path=a.model_path, quiet=a.quiet)
+
+
+if __name__ == "__main__":
+    main()
