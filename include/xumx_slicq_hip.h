@@ -513,6 +513,23 @@ size_t xsq_slicqt_inverse_adjoint_workspace(xsq_plan* plan, int BC, int S, int a
 int xsq_slicqt_inverse_adjoint(xsq_plan* plan, const float* gy, int BC, int S, int64_t length, float* gcoef, int accumulate,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- adjoint of the forward sliCQT: the gradient of a coefficient-domain loss with respect to the audio -------------
+ * The adjoint of nsgt/slicing.py:21-72 (slices, slice window), nsgt/nsgtf.py:40-81 (FFT_L, band windows, IFFT_Lg) and
+ * nsgt/slicq.py:13-33 (arrange).  With coef = xsq_slicqt_forward(x, BC, n) and gcoef (arena of BC channels,
+ * S = xsq_plan_num_slices(n) slices; the real view of the coefficients' cotangent) = dLoss/dcoef, gx (BC, n) = dLoss/dx:
+ *   V[s,j,q] = (-1)^(c_j/2) g_j[q] / Lg_j FFT_Lg(gcoef[s,j,:])[q],   k = (c_j + sq(q)) mod L,
+ *   fr_s[k] += V (k <= L/2),  fr_s[L-k] += conj V (k > L/2),   seg_s = tw . irfft_L(w fr_s), w_0 = w_{L/2} = L, w_k = L/2,
+ *   gx[m] = sum_s seg_s[m + 2h - 2sh].
+ * It runs on the synthesis kernels of the plan's back end over tables built on first use (a synchronous upload) from
+ * xsq_slicqt_forward_adjoint_window (host arithmetic, no device; out laid out like g: g_j[q] / Lg_j times the weight
+ * w / L of the bin the entry lands on), a pass that adds the conjugates of the mirrored entries, and an overlap-add that
+ * applies the slice window.  No atomics: two calls on the same input give the same bits.  XSQ_ERR_ARG on a null pointer,
+ * BC or n <= 0, or a workspace below xsq_slicqt_forward_adjoint_workspace (0 on bad arguments).                         */
+int xsq_slicqt_forward_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_t* c, const float* g, double* out);
+size_t xsq_slicqt_forward_adjoint_workspace(xsq_plan* plan, int BC, int64_t n);
+int xsq_slicqt_forward_adjoint(xsq_plan* plan, const float* gcoef, int BC, int64_t n, float* gx,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the training step with the SDR term ---------------------------------------------------------------------------
  * xsq_train_step plus  mcoef * SDR( inverse sliCQT of the estimates, y_targets ): the estimates' inverse transform, the two
  * SDR passes and the adjoint added into the estimates' gradient run between the loss pass and the post-filter backward.

@@ -94,6 +94,9 @@ _SIGS = {
     "xsq_slicqt_adjoint_window": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "xsq_slicqt_inverse_adjoint_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
     "xsq_slicqt_inverse_adjoint": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "xsq_slicqt_forward_adjoint_window": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "xsq_slicqt_forward_adjoint_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int64]),
+    "xsq_slicqt_forward_adjoint": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
     "xsq_train_workspace_sdr": (C.c_size_t, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "xsq_train_step_sdr": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                      _vp, _vp, C.c_size_t, _vp]),

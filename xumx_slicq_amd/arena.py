@@ -64,3 +64,19 @@ class BlockTable:
         else:
             arena = torch.cat([X.to(torch.float32).reshape(-1) for X in X_list])
         return arena, lead, S
+
+    def pack_grads(self, grads: Sequence, lead: Tuple[int, ...], S: int, device) -> Tensor:
+        """The gradient arena of a block list of cotangents (the backward of the forward transform): a block the loss never
+        touched arrives as ``None`` and counts as zeros.  Zero-copy when the cotangents already are a run of views of one
+        allocation (``as_arena``), else ONE arena-sized write: each block is copied (or zeroed) into its own range."""
+        if all(g is not None for g in grads):
+            arena, lead_g, S_g = self.as_arena(list(grads))
+            assert lead_g == tuple(lead) and S_g == S
+            return arena
+        arena = torch.empty(self.numel(int(np.prod(lead)) if len(lead) else 1, S), dtype=torch.float32, device=device)
+        for g, v in zip(grads, self.views(arena, tuple(lead), S)):
+            if g is None:
+                v.zero_()
+            else:
+                v.copy_(g)
+        return arena

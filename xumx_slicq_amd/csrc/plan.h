@@ -126,6 +126,16 @@ struct xsq_plan {
     float* d_adj_tw = nullptr;      // (L) ones
     float* d_adj_Wf = nullptr;      // dense analysis matrices of a'
     float* d_adj_pool4f = nullptr;  // radix-4 analysis pool with the windows a'
+    // Adjoint of the forward transform (xsq_slicqt_forward_adjoint): the synthesis tables rebuilt from the window
+    // xsq_slicqt_forward_adjoint_window makes of g, and the fold list (slicqt.hip: FoldDst / FoldSrc), on first use.
+    std::vector<float> h_g;
+    bool fadj_built = false;
+    float* d_fadj_Wi = nullptr;     // dense synthesis matrices of that window
+    float* d_fadj_pool4i = nullptr; // radix-4 synthesis pool with it
+    void *d_fold_dst = nullptr, *d_fold_src = nullptr;            // the rocFFT path's: a pass over Z (k_fold_mirrored)
+    int nfold_dst = 0;
+    void *d_fold_inl_dst = nullptr, *d_fold_inl_src = nullptr;    // the hand-written slice FFT's: inside k_slice_irfft (FoldSched)
+    int nfold_inl = 0;
     // caches keyed by the call shape
     std::mutex mu;
     std::map<std::pair<int, int>, xsq::FftPlan> fft;              // (direction, batch)

@@ -486,11 +486,26 @@ struct CarryArgs {
 // pushed the gather prologue of the default path over the 128-register cap: spilled loads, each waited for in turn).
 // FAST4: the four-phases-in-flight gather (see below); chosen by the host when the plan's phases fit.
 // CARRY: the overlap-add of a streaming step (CarryArgs) instead of the one of a whole call; a template parameter like the others.
-template <int NT, bool PK = false, bool SHORT = false, bool FAST4 = false, bool CARRY = false>
+// WINDOW: every slice is multiplied by the slice window `tw` before it is overlap-added (the adjoint of the forward transform,
+// xsq_slicqt_forward_adjoint: the adjoint of "window, then transform" is "transform back, then window"); the other
+// instantiations never read `tw`.
+// FOLD (with WINDOW only; the adjoint of the forward transform): the entries of the row whose bin lies outside [0, L/2] -- the
+// inverse drops them -- are added, conjugated, to the mirrored bin, behind the gather: one lane per destination bin, its
+// sources in table order (no atomics, same bits every run).  Measured against a pass over Z in front of this kernel
+// (slicqt.hip: k_fold_mirrored, what the rocFFT path runs): 3 to 5 % of the call faster, profiles/autograd_fold_ab.jsonl.
+struct FoldSched {
+    const int4* dst;       // (bin, first source, sources, -) per destination bin
+    const int* src;        // entry of the row per source
+    int ndst;
+};
+template <int NT, bool PK = false, bool SHORT = false, bool FAST4 = false, bool CARRY = false, bool WINDOW = false, bool FOLD = false>
 __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __restrict__ Zrow, const GatherSched G,
                                                       const FftTables T, const OlaArgs O, const ShortSched SS,
-                                                      const ShortIn SI, const CarryArgs C = CarryArgs{}) {
+                                                      const ShortIn SI, const CarryArgs C = CarryArgs{},
+                                                      const float* __restrict__ tw = nullptr, const FoldSched FS = FoldSched{}) {
 #pragma clang fp contract(off)          // fused multiply-adds only where written (fmaf): same bits from every instantiation
+    static_assert(!WINDOW || (!CARRY && !SHORT), "the windowed overlap-add is the whole-call path's");
+    static_assert(!FOLD || WINDOW, "the fold belongs to the adjoint of the forward transform");
     __shared__ float2 Z[FFT_N + 1];        // bins 0..N while gathering, then the complex sequence
     __shared__ float2 w2s[FFT_R2 * FFT_R3];
     const int tid = threadIdx.x;
@@ -714,6 +729,15 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __re
             }
         }
     }
+    if constexpr (FOLD) {       // (every gather path ends on a barrier)
+        for (int i = tid; i < FS.ndst; i += NT) {
+            const int4 d = FS.dst[i];
+            float2 acc = Z[d.x];
+            for (int e = d.y; e < d.y + d.z; ++e) { const float2 z = zr[FS.src[e]]; acc.x += z.x; acc.y -= z.y; }
+            Z[d.x] = acc;
+        }
+        __syncthreads();
+    }
     XSQ_STAMP(1);
     // real pre-processing in place: Zin[k] = E + i O, Zin[N-k] = conj(E) + i conj(O),
     // E = U[k] + conj U[N-k], O = (U[k] - conj U[N-k]) * conj(W_L^k)   (no 1/2: output = L * irfft)
@@ -823,6 +847,7 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __re
             const int nn = tid + NT * it;
             if (nn >= FFT_N) break;
             float2 v = Z[fft_pos(nn)];
+            if constexpr (WINDOW) { const float2 w = *reinterpret_cast<const float2*>(tw + 2 * nn); v.x *= w.x; v.y *= w.y; }
             if (O.parity) { v.x += prev[it].x; v.y += prev[it].y; }
             y2[nn] = v;
         }
@@ -831,7 +856,8 @@ __global__ __launch_bounds__(NT, NT / 128) void k_slice_irfft(const float2* __re
     }
     // edge slices (first / last of a channel) and odd row offsets: per-sample bounds, 4-byte accesses
     for (int nn = tid; nn < FFT_N; nn += NT) {
-        const float2 v = Z[fft_pos(nn)];
+        float2 v = Z[fft_pos(nn)];
+        if constexpr (WINDOW) { const float2 w = *reinterpret_cast<const float2*>(tw + 2 * nn); v.x *= w.x; v.y *= w.y; }
         const bool add = 2 * nn < 2 * O.h ? add_lo : add_hi;     // 2h is even: both samples of nn lie in the same half
         const int64_t ia = i0 + 2 * nn, ib = ia + 1;
         if (ia >= 0 && ia < O.length) yr[ia] = add ? yr[ia] + v.x : v.x;

@@ -107,6 +107,56 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float* __restrict__ s
     y[(row_off ? row_off[bc] : (int64_t)bc * length) + i] = v;
 }
 
+// k_overlap_add with every slice multiplied by the slice window first (the adjoint of the forward transform on the rocFFT
+// path; the hand-written slice FFT does the same in its WINDOW instantiation).  Same grid, same order of the two terms.
+__global__ __launch_bounds__(256) void k_overlap_add_windowed(const float* __restrict__ seg, const float* __restrict__ tw,
+                                                               float* __restrict__ y, int S, int64_t length, int L, int h) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= length) return;
+    const int bc = blockIdx.y;
+    const int s0 = (int)(i / (2 * h));
+    const int p1 = (int)(i - (int64_t)2 * h * s0);
+    const float* base = seg + (int64_t)bc * S * L;
+    float v = tw[p1 + 2 * h] * base[(int64_t)s0 * L + p1 + 2 * h];
+    if (s0 + 1 < S) v += tw[p1] * base[(int64_t)(s0 + 1) * L + p1];
+    y[(int64_t)bc * length + i] = v;
+}
+
+// The fold of the adjoint of the forward transform (xsq_slicqt_forward_adjoint).  The analysis reads the bins outside
+// [0, L/2] of a band next to DC or Nyquist from the Hermitian mirror, conjugated; its adjoint therefore adds the conjugate
+// of what the synthesis kernels left on such an entry of Z (the inverse transform drops it) to the mirrored bin.  Here it is
+// added onto an entry of Z that the gather sums into that bin anyway, so the gather schedule -- and the disjointness of the
+// bands of a phase it rests on -- stays as it is.  One lane per destination entry, its sources in table order: no atomics,
+// the same bits every run.  No source is a destination.  grid (rows), Z in the arena's layout (the rocFFT path's; the
+// hand-written slice FFT folds inside its own kernel, slice_fft.h: FOLD -- measured 3 to 5 % of the call faster than this pass in
+// front of it, profiles/autograd_fold_ab.jsonl).
+struct FoldDst { int jd, pd, first, count; };     // band and spectrum position (bin = bin0 + p) of the destination; its sources
+struct FoldSrc { int js, ps; };
+__global__ __launch_bounds__(256) void k_fold_mirrored(float* __restrict__ Z, const BandDev* __restrict__ bands,
+                                                        const FoldDst* __restrict__ dst, const FoldSrc* __restrict__ src, int ndst,
+                                                        int BC, int S) {
+    const int row = blockIdx.x;
+    const int bc = row / S, s = row - bc * S;
+    const int64_t BCS = (int64_t)BC * S;
+    auto at = [&](int j, int p) {
+        const BandDev b = bands[j];
+        const int64_t e = BCS * b.cum + (((int64_t)bc * b.F + b.f) * S + s) * b.Lg + p;
+        return reinterpret_cast<float2*>(Z) + e;
+    };
+    for (int i = threadIdx.x; i < ndst; i += 256) {
+        const FoldDst d = dst[i];
+        float2* const zd = at(d.jd, d.pd);
+        float2 acc = *zd;
+        for (int e = d.first; e < d.first + d.count; ++e) {
+            const float2 z = *at(src[e].js, src[e].ps);
+            acc.x += z.x;
+            acc.y -= z.y;
+        }
+        *zd = acc;
+    }
+}
+
 // The overlap-add of a streaming step over the S new slices of the step (CarryArgs, slice_fft.h): grid (ceil((nblk + 1) * 2h
 // / 256), BC).  Block b of the step = second half of position b (slice b - shift, or the carried half when there is none) +
 // first half of position b + 1, summed in the order of k_overlap_add; block nblk is the new carry.
@@ -506,13 +556,14 @@ struct PlanArgs {
     const float* tw;
     std::vector<int64_t> g_off;     // first sample of band j's windows inside g / gd (the bands' windows lie back to back)
     const double* ga64 = nullptr;   // when set: the analysis window in double, in place of g (the adjoint tables, adjoint_tables())
+    const double* gs64 = nullptr;   // when set: the synthesis window without its sign, in place of gd Lg / L (forward_adjoint_tables())
 
     // (-1)^(c_j / 2), and sample q of the band's two windows with the sign and the transform's scale folded in.  The dense
     // matrices, the window pool of the radix-4 kernel and the short-band schedule all take them from here: the engines are
     // interchangeable per band only while these agree to the bit.
     double sign(int j) const { return ((c[j] / 2) % 2 == 0) ? 1.0 : -1.0; }
     double analysis_window(int j, int q) const { return (ga64 ? ga64[g_off[j] + q] : (double)g[g_off[j] + q]) * sign(j) / Lg[j]; }
-    double synthesis_window(int j, int q) const { return gd[g_off[j] + q] * Lg[j] * sign(j) / L; }
+    double synthesis_window(int j, int q) const { return gs64 ? gs64[g_off[j] + q] * sign(j) : gd[g_off[j] + q] * Lg[j] * sign(j) / L; }
 };
 
 // blocks = runs of equal band length (nsgt/nsgtf.py:66-78), and the band table (without .ent: build_slice_fft_tables)
@@ -851,6 +902,7 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
     // what the adjoint tables are made from on first use (adjoint_tables)
     P->h_Lg.assign(Lg, Lg + nbands); P->h_c.assign(c, c + nbands);
     P->h_gd.assign(gd, gd + A.g_off[nbands - 1] + Lg[nbands - 1]);
+    P->h_g.assign(g, g + A.g_off[nbands - 1] + Lg[nbands - 1]);
 
     // (needs the LDS slice FFT's gather table, and both kinds of band)
     ShortTables H;
@@ -908,6 +960,8 @@ int xsq_plan_destroy(xsq_plan* P) {
     (void)hipFree(P->d_T); (void)hipFree(P->d_tgt); (void)hipFree(P->d_tgt16); (void)hipFree(P->d_tw); (void)hipFree(P->d_Wf); (void)hipFree(P->d_Wi); (void)hipFree(P->d_bands);
     (void)hipFree(P->d_cov_ptr); (void)hipFree(P->d_cov_band);
     (void)hipFree(P->d_adj_tw); (void)hipFree(P->d_adj_Wf); (void)hipFree(P->d_adj_pool4f);
+    (void)hipFree(P->d_fadj_Wi); (void)hipFree(P->d_fadj_pool4i); (void)hipFree(P->d_fold_dst); (void)hipFree(P->d_fold_src);
+    (void)hipFree(P->d_fold_inl_dst); (void)hipFree(P->d_fold_inl_src);
     (void)hipFree(P->d_s_item1); (void)hipFree(P->d_s_tw1); (void)hipFree(P->d_s_item2); (void)hipFree(P->d_s_tgt); (void)hipFree(P->d_s_wd);
     delete P;
     return XSQ_OK;
@@ -1223,8 +1277,12 @@ int xsq_slicqt_inverse(xsq_plan* P, const float* coef, int BC, int S, int64_t le
 }
 
 // carry != nullptr: the S slices are the new ones of a streaming step and `y` takes its blocks (CarryArgs, slice_fft.h)
+// adj != nullptr: the adjoint of the forward transform (xsq_slicqt_forward_adjoint) -- the synthesis over the tables of its
+// window, the fold of the mirrored entries, and slices multiplied by the slice window before the overlap-add
+struct AdjointSynthesis { const float *Wi, *pool4i, *tw; const FoldDst* dst; const FoldSrc* src; int ndst; FoldSched inl; };
 static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int BCx, int BC, int S, int64_t length, float* y,
-                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry = nullptr);
+                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry = nullptr,
+                        const AdjointSynthesis* adj = nullptr);
 
 int xsq_slicqt_inverse_rows(xsq_plan* P, const float* coef, int BC, int S, int64_t length, float* y,
                             const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_) {
@@ -1239,7 +1297,8 @@ int xsq_slicqt_inverse_masked(xsq_plan* P, const float* masks, const float* mix,
 }
 
 static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int BCx, int BC, int S, int64_t length, float* y,
-                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry) {
+                        const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry,
+                        const AdjointSynthesis* adj) {
     XSQ_REQUIRE(P && coef && y && ws, "xsq_slicqt_inverse: null argument");
     XSQ_REQUIRE(BC > 0 && S >= (carry ? 1 : 2) && length > 0, "xsq_slicqt_inverse: BC=%d S=%d length=%lld", BC, S,
                 (long long)length);
@@ -1268,21 +1327,24 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
     TileTable tt;
     rc = get_band_tiles(P, rows, &tt);
     if (rc) return rc;
-    BandInvOp op{coef, Z, P->d_bands, P->d_Wi, BC, S, lds_fft(P) ? (int)P->sumFT : 0, mask, BCx};
+    BandInvOp op{coef, Z, P->d_bands, adj ? adj->Wi : P->d_Wi, BC, S, lds_fft(P) ? (int)P->sumFT : 0, mask, BCx};
     if (P->band_radix4 && P->nbands4) {
-        Band4Args a4{(const Band4Dev*)P->d_bands4, P->d_pool4i, coef, Z, BC, S, P->nbins, P->L,
+        Band4Args a4{(const Band4Dev*)P->d_bands4, adj ? adj->pool4i : P->d_pool4i, coef, Z, BC, S, P->nbins, P->L,
                      lds_fft(P) ? (int)P->sumFT : 0, mask, BCx, nullptr, nullptr, nullptr, 0};
-        XSQ_PROF("band_synthesis_dft4", stream);
+        XSQ_PROF(adj ? "fwd_adjoint_band_dft4" : "band_synthesis_dft4", stream);
         if ((rc = launch_dft4<false>(P, a4, rows, mask ? BCx * S : 0, stream))) return rc;
     }
     // short bands: inside k_slice_irfft when the plan allows it, else dense GEMM + Z round trip
-    const bool inl = lds_fft(P) && P->band_radix4 && P->short_inline && P->short_n1 > 0 && !carry;
-    if (tt.ntiles && !inl) { XSQ_PROF("band_synthesis_gemm", stream);
+    const bool inl = lds_fft(P) && P->band_radix4 && P->short_inline && P->short_n1 > 0 && !carry && !adj;
+    if (tt.ntiles && !inl) { XSQ_PROF(adj ? "fwd_adjoint_band_gemm" : "band_synthesis_gemm", stream);
     hipLaunchKernelGGL((grouped_gemm_kernel<BandInvOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
+    // the fold: inside the hand-written slice FFT (FOLD, slice_fft.h), or a pass over Z in front of the rocFFT path's gather
+    if (adj && adj->ndst && !lds_fft(P)) { XSQ_PROF("fwd_adjoint_fold", stream);
+    hipLaunchKernelGGL(k_fold_mirrored, dim3(rows), dim3(256), 0, stream, Z, P->d_bands, adj->dst, adj->src, adj->ndst, BC, S); }
     if (lds_fft(P)) {
         // inverse slice FFT with the overlap-add fused in: even slices store, odd slices add (slice_fft.h)
-        XSQ_PROF("slice_irfft_ola", stream);
+        XSQ_PROF(adj ? "fwd_adjoint_slice_irfft_ola" : "slice_irfft_ola", stream);
         GatherSched G;
         G.tgt = P->d_tgt; G.tgt16 = P->d_tgt16; G.row_len = (int)P->sumFT;
         for (int i = 0; i < 5; ++i) G.begin[i] = P->phase_begin[i];
@@ -1304,20 +1366,29 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
         if (P->packed_fft && !inl) kernel = fast4 ? k_slice_irfft<512, true, false, true> : k_slice_irfft<512, true>;
 #endif
         if (carry) kernel = fast4 ? k_slice_irfft<512, false, false, true, true> : k_slice_irfft<512, false, false, false, true>;
+        if (adj) kernel = fast4 ? k_slice_irfft<512, false, false, true, false, true, true> : k_slice_irfft<512, false, false, false, false, true, true>;
         for (int parity = 0; parity < 2; ++parity) {
             const int nsl = (S + 1 - parity) / 2;
             if (!nsl) continue;                   // (a step of one slice has no odd one)
             OlaArgs O{y, row_offsets, S, P->h, parity, length};
-            hipLaunchKernelGGL(kernel, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI, carry ? *carry : CarryArgs{});
+            hipLaunchKernelGGL(kernel, dim3(BC * nsl), dim3(512), 0, stream, (const float2*)Z, G, fft_tables(P), O, SS, SI, carry ? *carry : CarryArgs{},
+                               adj ? adj->tw : (const float*)nullptr, adj ? adj->inl : FoldSched{});
         }
         XSQ_HIP(hipGetLastError());
         return XSQ_OK;
     } else {
-        { XSQ_PROF("spectrum_gather", stream);
+        { XSQ_PROF(adj ? "fwd_adjoint_spectrum_gather" : "spectrum_gather", stream);
         hipLaunchKernelGGL(k_spectrum_gather, dim3((P->nbins + 255) / 256, rows), dim3(256), 0, stream, Z,
                            P->d_bands, P->d_cov_ptr, P->d_cov_band, fr, BC, S, P->nbins); }
-        { XSQ_PROF("irfft_L", stream); rc = run_fft(f, fr, seg, fwork, stream); }
+        { XSQ_PROF(adj ? "fwd_adjoint_irfft_L" : "irfft_L", stream); rc = run_fft(f, fr, seg, fwork, stream); }
         if (rc) return rc;
+    }
+    if (adj) {
+        XSQ_PROF("fwd_adjoint_overlap_add", stream);
+        hipLaunchKernelGGL(k_overlap_add_windowed, dim3((unsigned)((length + 255) / 256), BC), dim3(256), 0, stream, seg, adj->tw, y, S,
+                           length, P->L, P->h);
+        XSQ_HIP(hipGetLastError());
+        return XSQ_OK;
     }
     if (carry) { XSQ_PROF("overlap_add_carry", stream);
     hipLaunchKernelGGL(k_overlap_add_carry, dim3((unsigned)(((carry->nblk + 1) * 2 * P->h + 255) / 256), BC), dim3(256), 0, stream, seg, y,
@@ -1327,6 +1398,122 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
                        row_offsets, S, length, P->L, P->h); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
+}
+
+// ---- adjoint of the forward transform: gcoef (gradient arena) -> gx (BC, n) ----
+// With coef = xsq_slicqt_forward(x) and G = dLoss/dcoef (real view, arena layout):
+//   V[s,j,q] = (-1)^(c_j/2) g_j[q] / Lg_j FFT_Lg( G[s,j,:] )[q],  k = (c_j + sq(q)) mod L
+//   fr_s[k] += V[s,j,q] (k <= L/2),  fr_s[L - k] += conj V[s,j,q] (k > L/2: the fold),
+//   seg_s = tw . irfft_L( w fr_s ),  w_0 = w_{L/2} = L, w_k = L/2 otherwise,   gx[m] = sum_s seg_s[m + 2h - 2sh]
+// -- the synthesis with b_j[q] = g_j[q] / Lg_j w'(bin the entry lands on) in place of gd_j[q] Lg_j / L (w' = w / L: the slice
+// transform of the inverse is unnormalised), the fold (k_fold_mirrored) between the band kernels and the gather, and the slice
+// window on the way into the overlap-add.  A folded entry lands on a bin strictly inside (0, L/2): its weight is 1/2.
+int xsq_slicqt_forward_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_t* c, const float* g, double* out) {
+    XSQ_REQUIRE(Lg && c && g && out, "xsq_slicqt_forward_adjoint_window: null argument");
+    XSQ_REQUIRE(L > 0 && L % 4 == 0 && nbands >= 1, "xsq_slicqt_forward_adjoint_window: L=%d nbands=%d", L, nbands);
+    int64_t off = 0;
+    for (int j = 0; j < nbands; ++j) {
+        const int n = Lg[j];
+        XSQ_REQUIRE(n > 0 && n % 2 == 0 && n <= L / 2 && c[j] >= 0 && c[j] <= L / 2, "xsq_slicqt_forward_adjoint_window: band %d has Lg=%d c=%d",
+                    j, n, c[j]);
+        for (int q = 0; q < n; ++q) {
+            int k = c[j] + (q < n / 2 ? q : q - n);
+            if (k < 0) k = -k; else if (k > L / 2) k = L - k;
+            const double w = (k == 0 || k == L / 2) ? 1.0 : 0.5;
+            out[off + q] = w * (double)g[off + q] / (double)n;
+        }
+        off += n;
+    }
+    return XSQ_OK;
+}
+
+namespace xsq {
+// the synthesis tables of that window and the fold list, built and uploaded on first use (a synchronous upload: warm a plan
+// up before capturing it)
+static int forward_adjoint_tables(xsq_plan* P, AdjointSynthesis* out) {
+    std::lock_guard<std::mutex> lk(P->mu);
+    if (!P->fadj_built) {
+        const int nbands = P->nbands, L = P->L;
+        std::vector<double> b(P->h_g.size());
+        if (int rc = xsq_slicqt_forward_adjoint_window(L, nbands, P->h_Lg.data(), P->h_c.data(), P->h_g.data(), b.data())) return rc;
+        // (the builders fill both directions: the analysis halves are made from b as well and dropped)
+        PlanArgs A{L, P->tr, nbands, P->h_Lg.data(), P->h_c.data(), nullptr, P->h_gd.data(), nullptr, std::vector<int64_t>(nbands, 0), b.data(), b.data()};
+        for (int j = 1; j < nbands; ++j) A.g_off[j] = A.g_off[j - 1] + P->h_Lg[j - 1];
+        std::vector<float> Wf, Wi, pf, pi;
+        build_dense_matrices(P, A, Wf, Wi);
+        std::vector<Band4Dev> b4;
+        std::vector<char> is_short;
+        build_radix4_tables(P, A, b4, pf, pi, is_short, false);
+        // same layout as the plan's own pools: the kernels reach them through the plan's ONE band table (see adjoint_tables)
+        XSQ_REQUIRE(Wi.size() == P->wf_floats && (int)b4.size() == P->nbands4 && (!P->nbands4 || pi.size() == P->pool4_floats),
+                    "xsq_slicqt_forward_adjoint: the adjoint tables (%zu / %zu floats, %zu radix-4 bands) do not match the plan's (%zu / %zu, %d)",
+                    Wi.size(), pi.size(), b4.size(), P->wf_floats, P->pool4_floats, P->nbands4);
+        // the fold list: every entry whose bin lies outside [0, L/2], onto an entry that lands on the mirrored bin -- of its own
+        // band when there is one, else of the first band that covers the bin
+        std::map<std::pair<int, int>, std::vector<FoldSrc>> by_dst;
+        for (int j = 0; j < nbands; ++j) {
+            const BandDev& bj = P->bands[j];
+            for (int p = 0; p < bj.Lg; ++p) {
+                const int k = bj.bin0 + p;
+                if (k >= 0 && k <= L / 2) continue;
+                const int m = k < 0 ? -k : L - k;
+                int jd = -1;
+                if (m >= bj.bin0 && m < bj.bin0 + bj.Lg) jd = j;
+                for (int i = 0; jd < 0 && i < nbands; ++i)
+                    if (m >= P->bands[i].bin0 && m < P->bands[i].bin0 + P->bands[i].Lg) jd = i;
+                XSQ_REQUIRE(jd >= 0 && m >= 0 && m <= L / 2, "xsq_slicqt_forward_adjoint: no band covers bin %d, the mirror of band %d's bin %d", m, j, k);
+                by_dst[{jd, m - P->bands[jd].bin0}].push_back(FoldSrc{j, p});
+            }
+        }
+        std::vector<FoldDst> fd;
+        std::vector<FoldSrc> fs;
+        for (auto& kv : by_dst) {
+            fd.push_back(FoldDst{kv.first.first, kv.first.second, (int)fs.size(), (int)kv.second.size()});
+            fs.insert(fs.end(), kv.second.begin(), kv.second.end());
+        }
+        // the same list for the hand-written slice FFT (FoldSched): per mirrored bin, the entries of a row of Z that fold onto it
+        std::map<int, std::vector<int>> by_bin;
+        if (P->d_tgt)
+            for (auto& kv : by_dst)
+                for (const FoldSrc& sr : kv.second) by_bin[P->bands[kv.first.first].bin0 + kv.first.second].push_back(P->bands[sr.js].ent + sr.ps);
+        std::vector<int4> id;
+        std::vector<int> is;
+        for (auto& kv : by_bin) { id.push_back(make_int4(kv.first, (int)is.size(), (int)kv.second.size(), 0)); is.insert(is.end(), kv.second.begin(), kv.second.end()); }
+        float *dWi = nullptr, *dpi = nullptr;
+        void *dd = nullptr, *ds = nullptr, *did = nullptr, *dis = nullptr;
+        int rc = upload(dWi, Wi);
+        if (!rc && P->nbands4) rc = upload(dpi, pi);
+        if (!rc) rc = upload(dd, fd);
+        if (!rc) rc = upload(ds, fs);
+        if (!rc) rc = upload(did, id);
+        if (!rc) rc = upload(dis, is);
+        if (rc) { (void)hipFree(dWi); (void)hipFree(dpi); (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(did); (void)hipFree(dis); return rc; }
+        P->d_fadj_Wi = dWi; P->d_fadj_pool4i = dpi; P->d_fold_dst = dd; P->d_fold_src = ds; P->nfold_dst = (int)fd.size();
+        P->d_fold_inl_dst = did; P->d_fold_inl_src = dis; P->nfold_inl = (int)id.size();
+        P->fadj_built = true;
+    }
+    *out = AdjointSynthesis{P->d_fadj_Wi, P->d_fadj_pool4i, P->d_tw, (const FoldDst*)P->d_fold_dst, (const FoldSrc*)P->d_fold_src, P->nfold_dst,
+                            FoldSched{(const int4*)P->d_fold_inl_dst, (const int*)P->d_fold_inl_src, P->nfold_inl}};
+    return XSQ_OK;
+}
+}  // namespace xsq
+
+// workspace: that of the inverse transform over the same rows (Z | fr | seg | fft work)
+size_t xsq_slicqt_forward_adjoint_workspace(xsq_plan* P, int BC, int64_t n) {
+    if (!P || BC <= 0 || n <= 0) return 0;
+    return xsq_slicqt_inverse_workspace(P, BC, xsq_plan_num_slices(P, n));
+}
+
+int xsq_slicqt_forward_adjoint(xsq_plan* P, const float* gcoef, int BC, int64_t n, float* gx, void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(P && gcoef && gx && ws, "xsq_slicqt_forward_adjoint: null argument");
+    XSQ_REQUIRE(BC > 0 && n > 0, "xsq_slicqt_forward_adjoint: BC=%d n=%lld", BC, (long long)n);
+    const int S = xsq_plan_num_slices(P, n);
+    XSQ_REQUIRE(S >= 2, "xsq_slicqt_forward_adjoint: signal too short");
+    const size_t need = xsq_slicqt_forward_adjoint_workspace(P, BC, n);
+    XSQ_REQUIRE(need && need <= ws_bytes, "xsq_slicqt_forward_adjoint: workspace too small (%zu needed, %zu given)", need, ws_bytes);
+    AdjointSynthesis adj;
+    if (int rc = forward_adjoint_tables(P, &adj)) return rc;
+    return inverse_impl(P, gcoef, nullptr, 0, BC, S, n, gx, nullptr, ws, ws_bytes, stream_, nullptr, &adj);
 }
 
 // ---- the emission of a streaming step: masked inverse of the new slices only, overlap-added onto the carried half ----

@@ -115,6 +115,19 @@ class SliCQPlan:
                                                       out.ctypes.data), "xsq_slicqt_adjoint_window")
         return out
 
+    def forward_adjoint_window(self) -> np.ndarray:
+        """(sum Lg,) fp64, laid out like ``g``: the window of the adjoint of the forward transform
+        (xsq_slicqt_forward_adjoint_window, host arithmetic: no device needed) -- the table the library builds that
+        adjoint's synthesis matrices from."""
+        from . import _lib
+        Lg = np.ascontiguousarray(self.Lg, dtype=np.int32)
+        c = np.ascontiguousarray(self.c, dtype=np.int32)
+        g = np.ascontiguousarray(self.g, dtype=np.float32)
+        out = np.empty(g.shape, dtype=np.float64)
+        _lib.check(_lib.lib.xsq_slicqt_forward_adjoint_window(self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, g.ctypes.data,
+                                                              out.ctypes.data), "xsq_slicqt_forward_adjoint_window")
+        return out
+
 
 def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: float = 22050.0,
                fs: float = 44100.0, min_win: int = 16) -> SliCQPlan:

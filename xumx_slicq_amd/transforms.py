@@ -9,12 +9,14 @@ path: tensors must live on a ROCm device.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import List
 
 import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .arena import BlockTable
@@ -225,6 +227,27 @@ class SliCQEngine:
                                                            ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_adjoint")
         return arena
 
+    def forward_adjoint(self, garena: Tensor, lead, n: int) -> Tensor:
+        """Adjoint of ``forward``: garena = dLoss/dcoef (the real view of the coefficients' cotangent, arena layout for
+        prod(lead) channels and num_slices(n) slices) on a ROCm device -> dLoss/dx (*lead, n) fp32 (xsq_slicqt_forward_adjoint)."""
+        lead = tuple(lead)
+        n = int(n)
+        BC = int(np.prod(lead)) if len(lead) else 1
+        S = self.plan.num_slices(n)
+        h = self.handle(garena.device)
+        if garena.dtype != torch.float32 or not garena.is_contiguous() or garena.numel() != self.table.numel(BC, S):
+            raise ValueError(f"forward_adjoint: expected a contiguous fp32 arena of {self.table.numel(BC, S)} floats "
+                             f"({BC} channels, {S} slices), got {garena.dtype} x {garena.numel()}")
+        with torch.cuda.device(garena.device):
+            gx = torch.empty(BC, n, dtype=torch.float32, device=garena.device)
+            nbytes = _lib.lib.xsq_slicqt_forward_adjoint_workspace(h, BC, n)
+            if nbytes == 0:
+                raise _lib.XsqError("xsq_slicqt_forward_adjoint_workspace: " + _lib.last_error())
+            ws = self.workspace(garena.device, nbytes)
+            _lib.check(_lib.lib.xsq_slicqt_forward_adjoint(h, garena.data_ptr(), BC, n, gx.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                           _lib.stream_ptr()), "xsq_slicqt_forward_adjoint")
+        return gx.view(*lead, n)
+
     def backward_masked(self, masks: Tensor, mix: Tensor, BC: int, BCx: int, S: int, length: int, out: Tensor,
                         row_offsets: Tensor) -> Tensor:
         """Inverse transform of masks[bc] * mix[bc % BCx] without materialising the product
@@ -273,6 +296,68 @@ class NSGTBase(nn.Module):
         return jag, x
 
 
+def _first_order_only(name):
+    """Decorator of a ``Function.backward``: both transforms are linear maps whose adjoints are native calls outside
+    autograd, so the backward is once-differentiable; asking for a graph through it raises, naming the transform."""
+    def deco(fn):
+        once = once_differentiable(fn)
+
+        @functools.wraps(fn)
+        def backward(ctx, *grads):
+            if torch.is_grad_enabled() and any(g is not None and g.requires_grad for g in grads):
+                raise RuntimeError(f"{name}: double backward through the sliCQT is not supported "
+                                   f"(the gradient of {name} is a native call without a graph of its own)")
+            return once(ctx, *grads)
+        return backward
+    return deco
+
+
+class _SliCQForward(torch.autograd.Function):
+    """``NSGT_SL.forward`` as one node: the blocks are the zero-copy views of the arena ``SliCQEngine.forward`` fills; the
+    backward packs their cotangents into one gradient arena and calls ``SliCQEngine.forward_adjoint``.  The transform is
+    linear: nothing but n, lead and S is kept."""
+
+    @staticmethod
+    def forward(ctx, eng, x):
+        arena, lead, S = eng.forward(x)
+        ctx.eng, ctx.lead, ctx.S, ctx.n, ctx.dtype = eng, lead, S, x.shape[-1], x.dtype
+        ctx.set_materialize_grads(False)            # a block the loss never touched arrives as None
+        return tuple(eng.table.views(arena, lead, S))
+
+    @staticmethod
+    @_first_order_only("NSGT_SL")
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
+            return None, None
+        dev = next(g for g in grads if g is not None).device
+        garena = ctx.eng.table.pack_grads(grads, ctx.lead, ctx.S, dev)
+        return None, ctx.eng.forward_adjoint(garena, ctx.lead, ctx.n).to(ctx.dtype)
+
+
+class _SliCQInverse(torch.autograd.Function):
+    """``INSGT_SL.forward`` as one node over all blocks: the packing of ``BlockTable.as_arena`` (zero-copy for a run of views
+    of one arena, such as the untouched outputs of ``NSGT_SL``) happens inside the node, and the backward scatters the arena
+    of ``SliCQEngine.backward_adjoint`` back to the blocks as views."""
+
+    @staticmethod
+    def forward(ctx, eng, length, *blocks):
+        arena, lead, S = eng.table.as_arena(list(blocks))
+        BC = int(np.prod(lead)) if len(lead) else 1
+        ctx.eng, ctx.lead, ctx.S, ctx.BC, ctx.length = eng, lead, S, BC, length
+        ctx.dtypes = [b.dtype for b in blocks]
+        return eng.backward(arena, BC, S, length).view(*lead, -1)
+
+    @staticmethod
+    @_first_order_only("INSGT_SL")
+    def backward(ctx, gy):
+        if gy is None:
+            return (None, None) + (None,) * len(ctx.dtypes)
+        garena = ctx.eng.backward_adjoint(gy.reshape(ctx.BC, ctx.length), ctx.S)
+        views = ctx.eng.table.views(garena, ctx.lead, ctx.S)
+        return (None, None) + tuple(v.to(dt) if need else None
+                                    for v, dt, need in zip(views, ctx.dtypes, ctx.needs_input_grad[2:]))
+
+
 class NSGT_SL(nn.Module):
     """transforms.py:97-131."""
 
@@ -282,8 +367,11 @@ class NSGT_SL(nn.Module):
 
     def forward(self, x: Tensor) -> List[Tensor]:
         """(nb_samples, nb_channels, nb_timesteps) -> list over blocks of
-        (nb_samples, nb_channels, F_b, nb_slices, T_b, 2), views of one arena."""
+        (nb_samples, nb_channels, F_b, nb_slices, T_b, 2), views of one arena.  With grad mode on and ``x`` requiring
+        grad the blocks carry the gradient back to ``x`` (one autograd node, same arena, same views)."""
         eng = self.nsgt.nsgt
+        if torch.is_grad_enabled() and x.requires_grad:
+            return list(_SliCQForward.apply(eng, x))
         arena, lead, S = eng.forward(x)
         return eng.table.views(arena, lead, S)
 
@@ -297,7 +385,10 @@ class INSGT_SL(nn.Module):
 
     def forward(self, X_list, length: int) -> Tensor:
         eng = self.nsgt.nsgt
-        arena, lead, S = eng.table.as_arena(list(X_list))
+        X_list = list(X_list)
+        if torch.is_grad_enabled() and any(isinstance(X, Tensor) and X.requires_grad for X in X_list):
+            return _SliCQInverse.apply(eng, int(length), *X_list)
+        arena, lead, S = eng.table.as_arena(X_list)
         BC = int(np.prod(lead)) if len(lead) else 1
         y = eng.backward(arena, BC, S, int(length))
         return y.view(*lead, -1)
