@@ -64,6 +64,15 @@ const char* xsq_build_info(void);
  *   tw  slice (Tukey) window, L floats                                               */
 int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg,
                     const int32_t* c, const float* g, const double* gd, const float* tw);
+
+/* What the inverse transforms of this library leave out of the reference's (nsgt/nsigtf.py:57-99): the second synthesis of a
+ * band that reaches across DC (0 < c_j < Lg_j/2) through its negative-frequency mirror.  share[nbands] = the weight of that
+ * term relative to the band's kept synthesis (0 for a band that does not cross DC), *worst (may be null) the band of the
+ * largest.  Host arithmetic, no device.  xsq_plan_create returns XSQ_ERR_ARG, naming the band, for a plan with a share of
+ * XSQ_TWIN_SHARE_MAX or more: Bark-262 has no such band, Mel-32 one of 0.0084; `bark, 96, 32.9` (0.109) is refused.   */
+#define XSQ_TWIN_SHARE_MAX 0.03
+int xsq_slicqt_dropped_twin_share(int L, int nbands, const int32_t* Lg, const int32_t* c, const double* gd, double* share,
+                                  int* worst);
 int xsq_plan_destroy(xsq_plan* plan);
 int xsq_plan_num_blocks(const xsq_plan* plan);
 /* slice-FFT backend: 0 (default) = the hand-written LDS-resident transform when L == 18060

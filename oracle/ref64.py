@@ -85,15 +85,19 @@ def forward(plan: oslicqt.Plan, x: torch.Tensor) -> List[torch.Tensor]:
     return out
 
 
-def inverse(plan: oslicqt.Plan, X_list: List[torch.Tensor], length: int) -> torch.Tensor:
+def inverse(plan: oslicqt.Plan, X_list: List[torch.Tensor], length: int, twins=None) -> torch.Tensor:
     """list of (*lead, F_b, S, T_b, 2) -> (*lead, length) float64: the closed form of ``oslicqt.inverse``,
       fr_s[c_j+sq(q)] += (-1)^(c_j/2) Lg gd_j[q] FFT_Lg(coef_s,j)[q]  (bins 0..L/2);  seg_s = irfft_L(fr_s);
-      y[(2s-2)h + p] += seg_s[p]."""
+      y[(2s-2)h + p] += seg_s[p],
+    and for the bands that reach across DC (``plan.twins``) the kept part of the reference's mirrored synthesis,
+      fr_s[q - c_j] += (-1)^(c_j/2) (-1)^q (-i)^(+-1) Lg gd'_j[q] conj(FFT_Lg(coef_s,j)[q + 1])  (c_j <= q < Lg/2; -i on even
+    slices, +i on odd ones).  ``twins`` as in ``oslicqt.inverse``."""
     L, h = plan.L, plan.h
     lead = X_list[0].shape[:-4]
     S = X_list[0].shape[-3]
     BC = int(np.prod(lead)) if len(lead) else 1
     fr = torch.zeros(BC, S, L // 2 + 1, dtype=C128)
+    live = plan.live_twins() if twins is None else (plan.twins if twins else [])
     for (j0, F, T), Xb in zip(plan.blocks, X_list):
         cb = torch.view_as_complex(Xb.to(F64).reshape(BC, F, S, T, 2).contiguous())
         fc = torch.fft.fft(cb)
@@ -105,6 +109,12 @@ def inverse(plan: oslicqt.Plan, X_list: List[torch.Tensor], length: int) -> torc
             k = plan.c[j] + sq
             keep = (k >= 0) & (k <= L // 2)
             fr[:, :, torch.from_numpy(k[keep])] += (fc[:, f] * w)[:, :, torch.from_numpy(keep)]
+        for (j, q, k, gdm) in live:
+            if j0 <= j < j0 + F:
+                sign = 1.0 if (plan.c[j] // 2) % 2 == 0 else -1.0
+                w = torch.from_numpy(gdm * (T * sign) * np.where(q % 2 == 0, 1.0, -1.0)).to(C128)
+                rot = torch.tensor([-1j if s % 2 == 0 else 1j for s in range(S)], dtype=C128)
+                fr[:, :, torch.from_numpy(k)] += fc[:, j - j0][:, :, torch.from_numpy(q + 1)].conj() * w * rot[None, :, None]
     seg = torch.fft.irfft(fr, n=L)
     y = torch.zeros(BC, (2 * S + 2) * h, dtype=F64)
     for s in range(S):

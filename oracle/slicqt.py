@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 PI = math.pi
+TWIN_SHARE_MAX = 0.03       # xumx_slicq_amd.plan.TWIN_SHARE_MAX / XSQ_TWIN_SHARE_MAX; DESIGN.md section 2
 
 
 # --------------------------------------------------------------------------
@@ -118,10 +119,26 @@ class Plan:
     gd: List[np.ndarray]        # nbands x fp64   dual windows, peak at 0
     tw: np.ndarray              # (L,) fp32       slice window
     blocks: list = field(default_factory=list)  # [(first_band, F_b, T_b)]
+    twins: list = field(default_factory=list)   # [(band, q, bins, fp64 dual window of the mirrored band at q)], see ``inverse``
 
     @property
     def h(self):
         return self.L // 4
+
+    def twin_share(self) -> np.ndarray:
+        """(nbands,) weight of each band's mirrored synthesis (``twins``) relative to its kept one: what
+        xsq_slicqt_dropped_twin_share computes from gd alone, here from the mirrored band's own dual window."""
+        out = np.zeros(self.nbands)
+        for (j, q, k, gdm) in self.twins:
+            kk = self.c[j] + _sq(int(self.Lg[j]))
+            out[j] = math.sqrt(float(np.sum(gdm ** 2)) / float(np.sum(self.gd[j][(kk >= 0) & (kk <= self.L // 2)] ** 2)))
+        return out
+
+    def live_twins(self) -> list:
+        """The twins ``inverse`` synthesises by default: all of them on a plan the library refuses (a share of TWIN_SHARE_MAX or
+        more: there the oracle is the only implementation and equals the reference), none on a plan it accepts (there the
+        library drops the term by contract, Mel-32's 0.0084 for one, and the oracle is the operation the kernels are held to)."""
+        return self.twins if self.twins and float(self.twin_share().max()) >= TWIN_SHARE_MAX else []
 
     def nslices(self, n: int) -> int:
         """Slices produced for an n-sample signal (nsgt/slicing.py:47-72)."""
@@ -194,6 +211,19 @@ def make_plan(fscale="bark", fbins=262, fmin=32.9, fmax=22050.0, fs=44100.0,
     gd = [gi.to(torch.float64) / torch.fft.ifftshift(d[wi]) for gi, wi in zip(g, wins)]
 
     nb = len(g) // 2 + 1                 # slicq.py:123-131: sl = slice(0, len(g)//2+1)
+    # nsigtf.py:61-80: every band but DC and Nyquist is also synthesised through the window of its negative-frequency
+    # mirror, band len(g) - j, centred on bin L - c_j; what of that lands on the kept bins 0..L/2 stays in the output.
+    # Kept here for the bands that reach across DC (0 < c_j < Lg_j / 2).  At the Nyquist end the only plan found to have
+    # such a bin is ``bark, 400, 300`` (the bin L/2 itself, dual window 2.5e-11): no plan needs it, so it is not restated.
+    twins = []
+    for j in range(1, nb - 1):
+        sq = _sq(Mi[j])
+        k = (int(timepos[len(g) - j]) + sq) % nn
+        keep = (k <= nn // 2) & (sq >= 0)
+        if 0 < int(timepos[j]) < Mi[j] // 2:
+            assert keep.any() and int(timepos[len(g) - j]) == nn - int(timepos[j])
+            assert Mi[len(g) - j] == Mi[j]
+            twins.append((j, np.nonzero(keep)[0], k[keep], gd[len(g) - j].numpy()[keep].copy()))
     Lg = np.array(Mi[:nb], dtype=np.int64)
     c = np.array([int(t) for t in timepos[:nb]], dtype=np.int64)
     assert np.all(Lg % 4 == 0) and np.all(c % 2 == 0)
@@ -210,7 +240,7 @@ def make_plan(fscale="bark", fbins=262, fmin=32.9, fmax=22050.0, fs=44100.0,
         g=[gi.numpy().copy() for gi in g[:nb]],
         gd=[gi.numpy().copy() for gi in gd[:nb]],
         tw=tukey_slice_window(L, tr).numpy(),
-        blocks=blocks,
+        blocks=blocks, twins=twins,
     )
 
 
@@ -259,20 +289,28 @@ def forward(plan: Plan, x: torch.Tensor) -> List[torch.Tensor]:
 # --------------------------------------------------------------------------
 # inverse: INSGT_SL.forward
 # --------------------------------------------------------------------------
-def inverse(plan: Plan, X_list: List[torch.Tensor], length: int) -> torch.Tensor:
-    """list of (*lead, F_b, S, T_b, 2) -> (*lead, length).  Does NOT modify X_list.
+def inverse(plan: Plan, X_list: List[torch.Tensor], length: int, twins=None) -> torch.Tensor:
+    """list of (*lead, F_b, S, T_b, 2) -> (*lead, length).  Does NOT modify X_list.  ``twins``: True synthesises every mirrored
+    band of ``plan.twins`` (the reference's operation on any plan), False none, None ``plan.live_twins()``.
 
     transforms.py:154-178 -> nsgt/slicq.py:198-230 -> nsigtf_sl
     (nsgt/nsigtf.py:5-106) -> unslicing (nsgt/unslicing.py:33-69); closed form
     SURVEY.md 8(a) I2:
       fr_s[c_j+sq(q)] += (-1)^(c_j/2) Lg gd_j[q] FFT_Lg(coef_s,j)[q]   (bins 0..L/2)
-      seg_s = irfft_L(fr_s);  y[(2s-2)h + p] += seg_s[p].
+      seg_s = irfft_L(fr_s);  y[(2s-2)h + p] += seg_s[p],
+    plus, for a band that reaches across DC (``plan.twins``, 0 < c_j < Lg/2), the part of the reference's mirrored
+    synthesis (nsigtf.py:67-80, quirk A12) that lands on the kept bins: with gd' the dual window of the mirrored band,
+      fr_s[q - c_j] += (-1)^(c_j/2) (-1)^q (-i)^(+-1) Lg gd'_j[q] conj(FFT_Lg(coef_s,j)[q + 1])   (c_j <= q < Lg/2),
+    -i on even slices and +i on odd ones: the reference's ``conj(cat(t[1:], flip(t[1:])))`` read at the positions it uses (off
+    by one from a Hermitian mirror), under the ``arrange`` roll and the quarter rotation of ``unslicing``, which cancel on the
+    band's own synthesis and do not on the conjugated one.
     """
     L, h = plan.L, plan.h
     lead = X_list[0].shape[:-4]
     S = X_list[0].shape[-3]
     BC = int(np.prod(lead)) if len(lead) else 1
     fr = torch.zeros(BC, S, L // 2 + 1, dtype=torch.complex64)
+    live = plan.live_twins() if twins is None else (plan.twins if twins else [])
     for (j0, F, T), Xb in zip(plan.blocks, X_list):
         cb = torch.view_as_complex(Xb.reshape(BC, F, S, T, 2).contiguous())
         fc = torch.fft.fft(cb)                                   # nsigtf.py:29-32
@@ -284,6 +322,12 @@ def inverse(plan: Plan, X_list: List[torch.Tensor], length: int) -> torch.Tensor
             k = plan.c[j] + sq
             keep = (k >= 0) & (k <= L // 2)
             fr[:, :, torch.from_numpy(k[keep])] += (fc[:, f] * w)[:, :, torch.from_numpy(keep)]
+        for (j, q, k, gdm) in live:                              # nsigtf.py:67-80
+            if j0 <= j < j0 + F:
+                sign = 1.0 if (plan.c[j] // 2) % 2 == 0 else -1.0
+                w = torch.from_numpy(gdm * (T * sign) * np.where(q % 2 == 0, 1.0, -1.0)).to(torch.complex64)
+                rot = torch.tensor([-1j if s % 2 == 0 else 1j for s in range(S)], dtype=torch.complex64)
+                fr[:, :, torch.from_numpy(k)] += fc[:, j - j0][:, :, torch.from_numpy(q + 1)].conj() * w * rot[None, :, None]
     seg = torch.fft.irfft(fr, n=L)                               # nsigtf.py:99-103
     y = torch.zeros(BC, (2 * S + 2) * h, dtype=torch.float32)
     for s in range(S):                                           # unslicing.py:59-66

@@ -92,6 +92,7 @@ _SIGS = {
     "xsq_sdr_loss_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
     "xsq_sdr_loss_backward": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xsq_slicqt_adjoint_window": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "xsq_slicqt_dropped_twin_share": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "xsq_slicqt_inverse_adjoint_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int, C.c_int]),
     "xsq_slicqt_inverse_adjoint": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "xsq_slicqt_forward_adjoint_window": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),

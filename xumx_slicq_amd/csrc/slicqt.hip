@@ -282,6 +282,62 @@ struct BandFwdOp {
     }
 };
 
+// The analysis of the bands above the radix-4 kernels' Lg = 320 (4 * D4_MPAD; none in Bark-262 or Mel-32): BandFwdOp's
+// product with the sum over K = 2 Lg carried in float64 on the vector ALU.  On the tile engine one fp32 MFMA accumulator
+// chain takes all K products of an output; a DC band is a plateau of ones, and where the phases of the slice spectrum
+// align its terms add with one sign: measured on `bark, 400, 300` (Lg 376, K = 752) that chain is off by 7e-6 of the
+// coefficient, 22 times the fp32 FFT of the same band.  A product of two floats is exact in float64 and 752 of them sum
+// there to 1e-13, so the result is the float64 sum rounded once.  Tile = 32 rows x 64 columns, K-step 16, thread (ty, tx)
+// = rows ty and ty + 16, columns 4 tx .. 4 tx + 3 (two complex coefficients, so the whitened magnitude needs no
+// exchange); operands, loaders, arena layout and the xin epilogue are BandFwdOp's.  Fixed order: the same bits every run.
+constexpr int LONG_LG = 4 * D4_MPAD, LONG_BM = 32;
+__global__ __launch_bounds__(256) void k_band_fwd_long(const BandFwdOp op, const TileDev* __restrict__ tiles) {
+    __shared__ __attribute__((aligned(16))) float As[LONG_BM][20];
+    __shared__ __attribute__((aligned(16))) float Bs[16][68];
+    const TileDev t = tiles[blockIdx.x];
+    const BandGroup g = op.group(t.group);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int s_row = tid >> 2, s_kq = (tid & 3) * 4;
+    const BandFwdOp::RowA ra = op.row_a(g, s_row < LONG_BM ? t.m0 + s_row : g.M);
+    const float* bt = g.B + (int64_t)(t.n0 + s_row) * g.ldb + s_kq;      // Wt[n][k], padded to whole tiles with zeros
+    double acc[2][4] = {{0., 0., 0., 0.}, {0., 0., 0., 0.}};
+    for (int k0 = 0; k0 < g.K; k0 += 16) {
+        const float4 b = *reinterpret_cast<const float4*>(bt + k0);
+        if (s_row < LONG_BM) *reinterpret_cast<float4*>(&As[s_row][s_kq]) = op.load_a4(g, ra, k0 + s_kq);
+        Bs[s_kq][s_row] = b.x; Bs[s_kq + 1][s_row] = b.y; Bs[s_kq + 2][s_row] = b.z; Bs[s_kq + 3][s_row] = b.w;
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const float4 w = *reinterpret_cast<const float4*>(&Bs[kk][4 * tx]);
+            const double wd[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const double a = As[ty + 16 * r][kk];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] = fma(a, wd[c], acc[r][c]);
+            }
+        }
+        __syncthreads();
+    }
+    const int n = t.n0 + 4 * tx;
+    if (n >= g.N) return;                                                // N = 2 Lg is a multiple of 8
+    const float mu = op.xin ? op.mean[g.j] : 0.f, sc = op.xin ? op.scale[g.j] : 1.f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int m = t.m0 + ty + 16 * r;
+        if (m >= g.M) continue;
+        const int bc = m / op.S, s = m - bc * op.S;
+        const float4 v = make_float4((float)acc[r][0], (float)acc[r][1], (float)acc[r][2], (float)acc[r][3]);
+        float* d = op.coef + g.base + ((int64_t)bc * g.F * op.S + s) * (2 * g.Lg) + n;
+        *reinterpret_cast<float4*>(d) = v;                               // 16-byte aligned: Lg % 4 == 0, n % 4 == 0
+        if (op.xin) {
+            float x0 = whiten_mag(v.x, v.y, mu, sc), x1 = whiten_mag(v.z, v.w, mu, sc);
+            if (op.split) { x0 = bf3_word(x0); x1 = bf3_word(x1); }
+            *reinterpret_cast<float2*>(op.xin + ((d - op.coef) >> 1)) = make_float2(x0, x1);
+        }
+    }
+}
+
 // Z = coef x Wi   (dense rows in, dense rows out, same arena layout)
 struct BandInvOp {
     typedef BandGroup Group;
@@ -396,15 +452,27 @@ __global__ __launch_bounds__(256) void k_remix_combine(RemixArgs a) {
 // host side
 // ------------------------------------------------------------------------------------------
 // dense-GEMM tiles: all bands, or only the short ones when the radix-4 kernel takes the rest
-static int get_band_tiles(xsq_plan* P, int rows, TileTable* out) {
+// part (the table's `sub`): 0 every such band (the synthesis; the analysis of a plan with no band above LONG_LG, so such a
+// plan keeps its one table), 1 the analysis' bands up to LONG_LG, 2 the tiles of k_band_fwd_long over the bands above it
+static int get_band_tiles(xsq_plan* P, int rows, TileTable* out, int part = 0) {
     const bool r4 = P->band_radix4 && P->nbands4 > 0;
-    return cached_tiles<TileDev>(P->mu, P->tiles, TileKey{TileKind::BandGemm, rows, 0, 0, r4 ? 1 : 0}, out, [&](std::vector<TileDev>& t) {
+    const auto is_long = [&](int j) { return P->bands[j].Lg > LONG_LG; };
+    bool any_long = false;
+    for (int j = 0; j < P->nbands; ++j) any_long = any_long || is_long(j);
+    if (!any_long) {
+        if (part == 2) { *out = TileTable{}; return XSQ_OK; }
+        part = 0;
+    }
+    return cached_tiles<TileDev>(P->mu, P->tiles, TileKey{TileKind::BandGemm, rows, 0, part, r4 ? 1 : 0}, out, [&](std::vector<TileDev>& t) {
         // longest tiles first (K = 2*Lg grows along the band table): the launch ends on short tiles
+        const auto push = [&](int j) {
+            if (part == 2) { if (is_long(j)) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg, LONG_BM); }
+            else if (part == 0 || !is_long(j)) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg);
+        };
         if (r4) {
-            for (int i = (int)P->bands4_small.size() - 1; i >= 0; --i)
-                push_group_tiles(t, P->bands4_small[i], rows, 2 * P->bands[P->bands4_small[i]].Lg);
+            for (int i = (int)P->bands4_small.size() - 1; i >= 0; --i) push(P->bands4_small[i]);
         } else {
-            for (int j = P->nbands - 1; j >= 0; --j) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg);
+            for (int j = P->nbands - 1; j >= 0; --j) push(j);
         }
     });
 }
@@ -695,7 +763,8 @@ static bool build_slice_fft_tables(xsq_plan* P, std::vector<float2>& T, std::vec
 }
 
 // Tables of the radix-4 band kernels (band_dft4.h, band_dft4s.h) over the bands with Lg >= the split point; the other bands
-// go to bands4_small (the dense engine, gemm_tile.h) and get their flag in is_short.
+// go to bands4_small (the dense engine, gemm_tile.h; the analysis of those above LONG_LG to k_band_fwd_long) and get their
+// flag in is_short.
 // `commit` false: only the pools are wanted (the adjoint's windows over the band split the plan already has) -- the plan stays as it is.
 static void build_radix4_tables(xsq_plan* P, const PlanArgs& A, std::vector<Band4Dev>& b4, std::vector<float>& pf, std::vector<float>& pi,
                                 std::vector<char>& is_short, bool commit = true) {
@@ -939,6 +1008,15 @@ int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg
                     const float* g, const double* gd, const float* tw) {
     XSQ_REQUIRE(out && Lg && c && g && gd && tw, "xsq_plan_create: null argument");
     XSQ_REQUIRE(L > 0 && L % 4 == 0 && tr % 2 == 0 && nbands >= 2, "xsq_plan_create: bad L/tr/nbands");
+    {   // no silently different audio: a plan whose dropped mirrored synthesis is not negligible is refused
+        std::vector<double> share(nbands);
+        int worst = 0;
+        if (int rc = xsq_slicqt_dropped_twin_share(L, nbands, Lg, c, gd, share.data(), &worst)) return rc;
+        XSQ_REQUIRE(share[worst] < XSQ_TWIN_SHARE_MAX,
+                    "xsq_plan_create: band %d (centre bin %d, Lg %d) reaches across DC and the reference's mirrored synthesis of it, "
+                    "which this library does not compute, is %.3g of the band's own (limit %.3g): plan refused",
+                    worst, (int)c[worst], (int)Lg[worst], share[worst], (double)XSQ_TWIN_SHARE_MAX);
+    }
     xsq_plan* P = new xsq_plan();
     const int rc = plan_build(P, L, tr, nbands, Lg, c, g, gd, tw);
     if (rc != XSQ_OK) {          // frees whatever was allocated before the failure
@@ -1141,9 +1219,10 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
         { XSQ_PROF(adj ? "adjoint_rfft_L" : "rfft_L", stream); rc = run_fft(f, seg, U, fwork, stream); }
         if (rc) return rc;
     }
-    TileTable tt;
-    rc = get_band_tiles(P, rows, &tt);
+    TileTable tt, tl;
+    rc = get_band_tiles(P, rows, &tt, 1);
     if (rc) return rc;
+    if ((rc = get_band_tiles(P, rows, &tl, 2))) return rc;
     BandFwdOp op{U, coef, P->d_bands, d_Wf, BC, S, P->nbins, P->L, xin, mean, scale, split};
     if (P->band_radix4 && P->nbands4) {
         Band4Args a4{(const Band4Dev*)P->d_bands4, d_pool4f, U, coef, BC, S, P->nbins, P->L, 0, nullptr, 0, xin, mean, scale, split};
@@ -1153,6 +1232,8 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
     if (tt.ntiles) { XSQ_PROF(adj ? "adjoint_band_gemm" : "band_analysis_gemm", stream);
     hipLaunchKernelGGL((grouped_gemm_kernel<BandFwdOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
+    if (tl.ntiles) { XSQ_PROF(adj ? "adjoint_band_long" : "band_analysis_long", stream);
+    hipLaunchKernelGGL(k_band_fwd_long, dim3(tl.ntiles), dim3(256), 0, stream, op, (const TileDev*)tl.d_tiles); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
 }
@@ -1177,6 +1258,40 @@ int xsq_slicqt_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_
         }
         off += n;
     }
+    return XSQ_OK;
+}
+
+// ---- the part of the reference's inverse that this library does not compute ----
+// The reference synthesises every band 1 .. nbands-2 a second time through the dual window of its negative-frequency
+// mirror (centre L - c_j), from conj(cat(t[1:], flip(t[1:]))) of the band's spectrum t, and keeps bins 0..L/2 of the sum
+// (nsgt/nsigtf.py:57-99).  For a band that reaches across DC (0 < c_j < Lg_j/2) that second synthesis lands on the kept
+// bins  q - c_j,  c_j <= q < Lg_j/2,  with weight Lg_j gd'_j[q], gd' the mirrored band's dual window = gd_j[Lg_j - q]
+// (the windows and the frame diagonal are even).  The kernels drop it.  share[j] = its weight relative to the kept
+// synthesis of the band,  sqrt( sum_q gd_j[Lg_j - q]^2 / sum_{0 <= c_j + sq(q) <= L/2} gd_j[q]^2 ),  0 for every other band.
+// Host arithmetic, no device.  Returns the band of the largest share in *worst (may be null).
+int xsq_slicqt_dropped_twin_share(int L, int nbands, const int32_t* Lg, const int32_t* c, const double* gd, double* share,
+                                  int* worst) {
+    XSQ_REQUIRE(Lg && c && gd && share, "xsq_slicqt_dropped_twin_share: null argument");
+    XSQ_REQUIRE(L > 0 && L % 4 == 0 && nbands >= 1, "xsq_slicqt_dropped_twin_share: L=%d nbands=%d", L, nbands);
+    int64_t off = 0;
+    int w = 0;
+    for (int j = 0; j < nbands; ++j) {
+        const int n = Lg[j];
+        XSQ_REQUIRE(n > 0 && n % 2 == 0, "xsq_slicqt_dropped_twin_share: band %d has Lg=%d", j, n);
+        share[j] = 0.0;
+        if (j > 0 && j < nbands - 1 && c[j] > 0 && c[j] < n / 2) {
+            double kept = 0.0, dropped = 0.0;
+            for (int q = 0; q < n; ++q) {
+                const int k = c[j] + (q < n / 2 ? q : q - n);
+                if (k >= 0 && k <= L / 2) kept += gd[off + q] * gd[off + q];
+            }
+            for (int q = c[j]; q < n / 2; ++q) dropped += gd[off + n - q] * gd[off + n - q];
+            share[j] = kept > 0.0 ? std::sqrt(dropped / kept) : 1.0;
+        }
+        if (share[j] > share[w]) w = j;
+        off += n;
+    }
+    if (worst) *worst = w;
     return XSQ_OK;
 }
 

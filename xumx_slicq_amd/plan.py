@@ -62,6 +62,27 @@ def _hann0(n: int) -> torch.Tensor:
     return 0.5 * (torch.cos(torch.arange(n, dtype=torch.float64) * (TWO_PI / n)) + 1.0)
 
 
+TWIN_SHARE_MAX = 0.03        # XSQ_TWIN_SHARE_MAX of include/xumx_slicq_hip.h
+
+
+def dropped_twin_share(L: int, Lg: np.ndarray, c: np.ndarray, gd: np.ndarray) -> np.ndarray:
+    """(nbands,) fp64: xsq_slicqt_dropped_twin_share restated.  The reference's inverse synthesises every inner band a second
+    time through the dual window of its negative-frequency mirror (nsgt/nsigtf.py:57-99); for a band that reaches across DC
+    (0 < c_j < Lg_j/2) that lands on the kept bins q - c_j, c_j <= q < Lg_j/2, with the weight gd_j[Lg_j - q].  The kernels do
+    not compute it.  The share of a band is that weight relative to the band's kept synthesis, 0 where no band crosses DC."""
+    out = np.zeros(len(Lg), dtype=np.float64)
+    off = np.concatenate(([0], np.cumsum(Lg)))
+    for j in range(1, len(Lg) - 1):
+        n, cj = int(Lg[j]), int(c[j])
+        if 0 < cj < n // 2:
+            w = gd[off[j]: off[j + 1]]
+            q = np.arange(n)
+            k = cj + np.where(q < n // 2, q, q - n)
+            kept = float(np.sum(w[(k >= 0) & (k <= L // 2)] ** 2))
+            out[j] = np.sqrt(float(np.sum(w[n - np.arange(cj, n // 2)] ** 2)) / kept) if kept > 0 else 1.0
+    return out
+
+
 @dataclass
 class SliCQPlan:
     """Tables of one sliCQT configuration (bands DC..Nyquist of the real transform)."""
@@ -211,8 +232,15 @@ def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: 
             k += 1
         blocks.append((j, k - j + 1, int(Lg[j])))
         j = k + 1
+    gd_used = torch.cat(gd[:used]).numpy().astype(np.float64)
+    share = dropped_twin_share(L, Lg, c, gd_used)
+    worst = int(np.argmax(share))
+    if share[worst] >= TWIN_SHARE_MAX:             # xsq_plan_create refuses the same plans
+        raise ValueError(f"plan ({scale}, {fbins}, {fmin}): band {worst} (centre bin {int(c[worst])}, Lg {int(Lg[worst])}) reaches across DC "
+                         f"and the reference's mirrored synthesis of it, which the kernels do not compute, is {share[worst]:.3g} of the "
+                         f"band's own (limit {TWIN_SHARE_MAX}): the stems would differ from the reference's")
     return SliCQPlan(
         scale=scale, fbins=fbins, fmin=fmin, fmax=fmax, fs=fs, L=L, tr=tr, Lg=Lg, c=c,
         g=torch.cat(g[:used]).numpy().astype(np.float32),
-        gd=torch.cat(gd[:used]).numpy().astype(np.float64),
+        gd=gd_used,
         tw=tw.numpy(), blocks=blocks)
