@@ -491,8 +491,8 @@ int64_t xsq_train_step_count(xsq_train* t, int64_t set);
  * accumulates one v_mfma_f32_32x32x16_bf16 product per pair in fp32; activations between the layers, BatchNorm, the
  * Wiener-EM, the loss, the master weights and AdamW stay fp32 -- fewer rounding points than autocast, which also keeps
  * BatchNorm / ReLU / sigmoid outputs in bf16 (tests/golden/training_step_bf16.npz holds the reference's own
- * fp32-vs-autocast spread; the arm is held inside it).  XSQ_TRAIN_WGRAD_FP32=1 keeps the weight gradients on fp32
- * operands (an A/B arm).                                                                                             */
+ * fp32-vs-autocast spread; the arm is held inside it).  The weight gradients always follow this mode (keeping them on
+ * fp32 operands under mode 1 measured slower, DESIGN.md section 7, and is no longer offered).                        */
 int xsq_train_set_precision(xsq_train* t, int mode);
 
 /* ---- SDR term of the training loss (loss.py:5-34: auraloss.time.SDSDRLoss over the 14 target combinations) ----------

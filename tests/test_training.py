@@ -493,3 +493,38 @@ def test_packed_bf16_weight_gradient_kernel_is_bitwise_the_lane_converting_one()
         assert res["1"][0] == res["0"][0]
         bad = [k for k in res["1"][1] if not torch.equal(res["1"][1][k], res["0"][1][k])]
         assert not bad, (len(bad), bad[:5])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sdr_mcoef", [-1.0, 1.0], ids=["xsq_train_step", "xsq_train_step_sdr"])
+def test_step_refuses_a_short_workspace_and_launches_nothing(sdr_mcoef):
+    """The step carves its workspace with the layout code that `xsq_train_workspace` / `xsq_train_workspace_sdr` add up, and
+    requires the carve to fit before it launches anything.  At B = 1, n = 9031 (S = 3, the smallest shape the step accepts) a
+    workspace one 256-byte block short is refused with XSQ_ERR_ARG (-1) and "workspace too small", by either entry point; the
+    next step on the SAME trainer with the right size returns what a fresh trainer's first step returns and leaves the same
+    parameters behind: the refused call launched nothing and left the state (pools, step counter, running statistics) alone."""
+    from xumx_slicq_amd import _lib
+    from xumx_slicq_amd.separator import seeded_separator
+    from xumx_slicq_amd.training import Trainer
+    n = 9031
+    y_t = torch.stack([0.5 * synth_audio(n, seed=700 + j, nb_samples=1) for j in range(4)]).cuda()
+    x = y_t.sum(0)
+    sep = seeded_separator(realtime=False)
+    fresh = lambda: Trainer(sep.xumx_model, (sep.nsgt, sep.insgt, sep.cnorm), sdr_mcoef=sdr_mcoef)
+    ref = fresh()
+    want = ref.step(x, y_t)
+    (key, need), = ref._need.items()
+    assert key[:2] == (1, 3) and need > 256, (key, need)
+    name = "xsq_train_step_sdr" if sdr_mcoef > 0 else "xsq_train_step"
+    tr = fresh()
+    tr._need[key] = need - 256
+    with pytest.raises(_lib.XsqError) as err:
+        tr.step(x, y_t)
+    assert f"{name} failed (-1)" in str(err.value) and f"{name}: workspace too small" in str(err.value), str(err.value)
+    assert tr.steps == 0 and tr._ws.numel() == need - 256
+    tr._need[key] = need
+    got = tr.step(x, y_t)
+    print("refused:", str(err.value), "| then", got, "fresh", want)
+    assert got == want
+    a, b = tr.state_dict(), ref.state_dict()
+    assert all(torch.equal(a[k], b[k]) for k in a)

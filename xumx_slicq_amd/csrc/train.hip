@@ -3,15 +3,23 @@
 //   forward   |X| whitening -> L1..L3 (MFMA engine of cdae.hip, raw outputs) each followed by BatchNorm on
 //             BATCH statistics + ReLU -> L4 + sigmoid -> masks, Y = mask * X [-> Wiener-EM, wiener.hip]
 //   loss      ComplexMSE over the 14 target combinations + MaskSum (loss.hip), and their gradients
-//   backward  direct-form kernels for every layer (weight, bias, BatchNorm affine, input whitening and
-//             data gradients) -- correctness first: one thread per output element, no tiling; the MFMA
-//             forms (the data gradients are the forward operators of the mirrored layers) are the next step
+//             [+ SDR term: inverse sliCQT of the estimates, sdr.hip, and the inverse's adjoint added into the gradient]
+//   backward  data gradients: the forward MFMA operators of the MIRRORED layers (d/d a3 of layer 4 is the layer-1
+//             operator on w4, ... cdae_api.h) over a second GEMM pool gathered in that arrangement;
+//             weight gradients: tiled MFMA contractions over row chunks (wgrad.h; the two operand shapes are WgL23Op and
+//             WgL14Op below) on a side stream, chunk sums reduced in a fixed order into the canonical layout;
+//             BatchNorm, layer-4 bias and input whitening: two-stage reductions with double partial sums in a fixed
+//             order (bitwise reproducible, no atomics)
 //   update    AdamW (training.py:391-393: lr 1e-3, weight decay 1e-5) on the canonical parameter pool
 //
 // Parameters, gradients and optimizer moments live in ONE flat fp32 pool each, in the reference's
 // state_dict order (the order xsq_model_create consumes), so gradients compare key by key with the
-// reference's autograd and a checkpoint is a single copy.  The GEMM-layout weights the MFMA forward
-// needs are re-gathered from the pool on the device every step through an index map.
+// reference's autograd and a checkpoint is a single copy.  The GEMM-layout weights of both pools are
+// re-gathered from the canonical pool on the device behind every update through two index maps.
+//
+// Host side, in file order: the kernels; xsq_train; the per-(B, S) tile tables and their closed-form counts
+// (group_chunks -> shape_counts / shape_tables); train_build (offsets, gather maps); the two workspace layouts
+// (train_layout, sdr_layout: the size functions and the step carve from the same code); train_step_impl.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -66,7 +74,16 @@ __global__ void k_gather(const float* __restrict__ src, const int* __restrict__ 
 
 // ---- BatchNorm (train mode) -----------------------------------------------------------------------
 // stats layout per (group, layer): mean[64] | invstd[64] | sum_g[64] | sum_gz[64]
-__device__ __forceinline__ float* bn_slot(float* stats, int group, int layer) { return stats + ((int64_t)group * 3 + layer) * 256; }
+template <class F>
+__device__ __forceinline__ F* bn_slot(F* stats, int group, int layer) { return stats + ((int64_t)group * 3 + layer) * 256; }
+// per layer (0, 1, 2 = the BatchNorm behind layer 1, 2, 3): its four vectors in the pool, its channels, the rows it normalises over.
+// (bn_pool_off serves the two apply kernels, which read the group in place; the three kernels that hold a COPY of the group --
+// k_bn_stats_final, k_bn_bwd_partial, k_bn_bwd_final -- spell the offset out: through the helper the copy goes to scratch, 152 bytes)
+__device__ __forceinline__ int64_t bn_pool_off(const TrainGroup& g, int layer) { return layer == 0 ? g.p_bn1 : (layer == 1 ? g.p_bn2 : g.p_bn3); }
+__device__ __forceinline__ int bn_channels(const TrainGroup& g, int layer) { return layer == 1 ? g.C2 : g.C1; }
+__device__ __forceinline__ int64_t bn_rows(const TrainGroup& g, const TrainDims& d, int layer) {
+    return (int64_t)d.Bn * (layer == 1 ? g.F2 : g.F1) * (layer == 1 ? d.T2 : d.T1);
+}
 
 // Reductions over the rows of a group run in two deterministic stages: row tiles of BN_ROWS rows write double partial
 // sums (fixed-order tree inside the workgroup), one small workgroup per group adds its tiles in order.
@@ -147,8 +164,8 @@ __global__ __launch_bounds__(64 * BN_FL) void k_bn_stats_final(const double* __r
                                                         const BnInfo* __restrict__ info, TrainDims d, int layer,
                                                         float* __restrict__ stats, float* __restrict__ pool, int update_running) {
     const TrainGroup g = groups[blockIdx.x];
-    const int64_t M = (int64_t)d.Bn * (layer == 1 ? g.F2 : g.F1) * (layer == 1 ? d.T2 : d.T1);
-    const int C = layer == 1 ? g.C2 : g.C1;
+    const int64_t M = bn_rows(g, d, layer);
+    const int C = bn_channels(g, layer);
     const int c = threadIdx.x & 63, ty = threadIdx.x >> 6;
     double a, b;
     bn_final_sum(part, info[blockIdx.x], c, ty, a, b);
@@ -178,15 +195,15 @@ __global__ __launch_bounds__(64 * BN_FL) void k_bn_stats_final(const double* __r
 constexpr int BN_AROWS = 19;         // rows per trip: 13 * 19 = 247 of 256 threads
 __global__ __launch_bounds__(256) void k_bn_relu_apply(const float4* __restrict__ z, float4* __restrict__ a,
                                                         const TrainGroup* __restrict__ groups, const int* __restrict__ frow,
-                                                        int rows_per_f, int64_t nquads, int layer,
+                                                        int rows_per_f, int layer,
                                                         const float* __restrict__ stats, const float* __restrict__ pool) {
     const int r0 = threadIdx.x / 13, q = threadIdx.x - 13 * r0;
     if (r0 >= BN_AROWS) return;
     const int gid = frow[blockIdx.x];
     const TrainGroup& g = groups[gid];
-    const int C = layer == 1 ? g.C2 : g.C1;
-    const int64_t pb = layer == 0 ? g.p_bn1 : (layer == 1 ? g.p_bn2 : g.p_bn3);
-    const float* st = stats + ((int64_t)gid * 3 + layer) * 256;
+    const int C = bn_channels(g, layer);
+    const int64_t pb = bn_pool_off(g, layer);
+    const float* st = bn_slot(stats, gid, layer);
     float mean[4], inv[4], gam[4], bet[4];
     bool on[4];
 #pragma unroll
@@ -225,8 +242,8 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
     const float4* z4 = reinterpret_cast<const float4*>(z + off);
     const float4* g4 = reinterpret_cast<const float4*>(ga + off);
     const int tid = threadIdx.x, rl = tid / BN_Q, q = tid - rl * BN_Q;
-    const float* st = stats + ((int64_t)t.group * 3 + layer) * 256;
-    const int C = layer == 1 ? g.C2 : g.C1;
+    const float* st = bn_slot(stats, t.group, layer);
+    const int C = bn_channels(g, layer);
     const int64_t pb = layer == 0 ? g.p_bn1 : (layer == 1 ? g.p_bn2 : g.p_bn3);
     double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
     if (tid < BN_RL * BN_Q) {
@@ -259,8 +276,8 @@ __global__ __launch_bounds__(64 * BN_FL) void k_bn_bwd_final(const double* __res
                                                       const BnInfo* __restrict__ info, TrainDims d, int layer,
                                                       float* __restrict__ stats, float* __restrict__ gpool) {
     const TrainGroup g = groups[blockIdx.x];
-    const int64_t M = (int64_t)d.Bn * (layer == 1 ? g.F2 : g.F1) * (layer == 1 ? d.T2 : d.T1);
-    const int C = layer == 1 ? g.C2 : g.C1;
+    const int64_t M = bn_rows(g, d, layer);
+    const int C = bn_channels(g, layer);
     const int c = threadIdx.x & 63, ty = threadIdx.x >> 6;
     double sg, sgz;
     bn_final_sum(part, info[blockIdx.x], c, ty, sg, sgz);
@@ -276,15 +293,15 @@ __global__ __launch_bounds__(64 * BN_FL) void k_bn_bwd_final(const double* __res
 // backward, step 2 (in place on ga; same workgroup shape as k_bn_relu_apply): g_z = gamma * invstd * (g_bn - mean(g_bn) - zhat * mean(g_bn * zhat))
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float4* __restrict__ z,
                                                        float4* __restrict__ ga, const TrainGroup* __restrict__ groups,
-                                                       const int* __restrict__ frow, int rows_per_f, int64_t nquads, int layer,
+                                                       const int* __restrict__ frow, int rows_per_f, int layer,
                                                        const float* __restrict__ stats, const float* __restrict__ pool) {
     const int r0 = threadIdx.x / 13, q = threadIdx.x - 13 * r0;
     if (r0 >= BN_AROWS) return;
     const int gid = frow[blockIdx.x];
     const TrainGroup& g = groups[gid];
-    const int C = layer == 1 ? g.C2 : g.C1;
-    const int64_t pb = layer == 0 ? g.p_bn1 : (layer == 1 ? g.p_bn2 : g.p_bn3);
-    const float* st = stats + ((int64_t)gid * 3 + layer) * 256;
+    const int C = bn_channels(g, layer);
+    const int64_t pb = bn_pool_off(g, layer);
+    const float* st = bn_slot(stats, gid, layer);
     float mean[4], inv[4], gam[4], bet[4], mg[4], mgz[4];
     bool on[4];
 #pragma unroll
@@ -319,7 +336,6 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float4* __restrict__
 // ---- loss gradients ---------------------------------------------------------------------------------
 // gY_j = (8 e_j + 6 s1) / (14 * n_b * nblocks) and the mask-sum gradient 2 (sum_j m_j - 1) / (n'_b * nblocks) (the same
 // for the 4 targets) come out of the loss pass itself (loss.hip: k_loss_partial<true>).
-struct BlockGeo { int F, T; int64_t cum; };
 
 // g_p4 = (Re(conj(X) * gY0) + gM) * m * (1 - m), in place on gM.  grid (ceil(per-target reals/256), groups)
 __global__ __launch_bounds__(256) void k_mask_bwd(const float2* __restrict__ X, const float2* __restrict__ gY0,
@@ -381,12 +397,7 @@ struct WgL23Op {
         return Group{Aarr + act2_off(g, d), Barr + act1_off(g, d), g.F1, g.F2};
     }
     __device__ const float* a_row(const Group& g, int k) const { return g.A + (int64_t)k * CS; }
-    __device__ Row row(const Group& g, int k, int df) const {
-        const int per = g.F2 * d.T2;
-        const int b = k / per, r = k - b * per;
-        const int f2 = r / d.T2, t2 = r - f2 * d.T2;
-        return Row{g.B + ((int64_t)(b * g.F1 + f2 + df) * d.T1 + t2) * CS};
-    }
+    __device__ Row row(const Group& g, int k, int df) const { return row_of(row_it(g, k, df)); }
     __device__ Cols cols(const Group&, int, int n) const { return Cols{n}; }
     __device__ float4 load_b4(const Group&, const Row& r, const Cols& c) const {
         return c.n < 4 * CS ? *reinterpret_cast<const float4*>(r.p + c.n) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -431,13 +442,7 @@ struct WgL14Op {
         return o;
     }
     __device__ const float* a_row(const Group& g, int k) const { return g.A + (int64_t)k * CS; }
-    __device__ Row row(const Group& g, int k, int) const {
-        const int per = g.F1 * d.T1;
-        const int b = k / per, r = k - b * per;
-        const int f1 = r / d.T1, t1 = r - f1 * d.T1;
-        const int64_t tau0 = (int64_t)t1 * g.hop - g.pad;
-        return Row{g.R + ((int64_t)b * 2 * g.F + f1) * g.ST + tau0, tau0};
-    }
+    __device__ Row row(const Group& g, int k, int df) const { return row_of(row_it(g, k, df)); }
     __device__ Cols cols(const Group& g, int ntile, int n) const {
         const int ng = ntile * NTL + n;
         Cols c; c.valid = ng < g.K1 && n < NTL; c.off = 0; c.dt = 0;
@@ -589,25 +594,29 @@ struct xsq_train {
     int64_t nparams = 0, pool_floats = 0, sumF = 0;
     std::vector<xsq::TrainGroup> groups;
     xsq::TrainGroup* d_groups = nullptr;
-    xsq::BlockGeo* d_geo = nullptr;
     int2* d_rows = nullptr;                 // (first group, f) per whitening row
     float *d_params = nullptr, *d_grads = nullptr, *d_m = nullptr, *d_v = nullptr;
     unsigned char* d_trainable = nullptr;
     int *d_map_pool = nullptr, *d_map_mean = nullptr, *d_map_scale = nullptr;
     int* d_map_bwd = nullptr;               // canonical pool -> weights of the data-gradient operators (same slots as the forward pool)
     bool pools_valid = false;               // the two GEMM pools hold the current parameters (re-gathered behind every update)
-    mutable std::mutex size_mu;
-    mutable std::map<std::pair<int, int>, std::pair<size_t, size_t>> size_cache;   // (B, S) -> (reduction scratch doubles, weight-gradient partial floats)
     float* d_pool_bwd = nullptr;
     int64_t step = 0;
     std::vector<int32_t> Fv, Tv;
-    struct WgTables {
-        xsq::WgTile *d_t23 = nullptr, *d_t14 = nullptr; xsq::WgGroupInfo *d_i23 = nullptr, *d_i14 = nullptr; int n23 = 0, n14 = 0;
-        xsq::BnTile *d_bt1 = nullptr, *d_bt2 = nullptr; xsq::BnInfo *d_bi1 = nullptr, *d_bi2 = nullptr; int nbt1 = 0, nbt2 = 0;   // act1-like / act2-like row tiles
+    // The activation arrays come in two shapes: act1-like (z1 a1 g1, z3 a3 g3: F1 x T1 rows per sample) and act2-like
+    // (z2 a2 g2: F2 x T2).  Everything that walks their rows is kept per shape, index 0 / 1.
+    int* d_frow[2] = {nullptr, nullptr};    // frequency-row index of the array -> group
+    struct RowTables {                      // tile lists over the rows of one shape at one (B, S)
+        xsq::BnTile* d_bt = nullptr; xsq::BnInfo* d_bi = nullptr;        // BatchNorm row tiles + per-group range
+        xsq::WgTile* d_wt = nullptr; xsq::WgGroupInfo* d_wi = nullptr;   // weight-gradient tiles (0: layers 1 / 4, 1: layers 2 / 3) + per-group range
+        int nbt = 0, nwg = 0;
     };
-    int *d_frow1 = nullptr, *d_frow2 = nullptr;    // frequency-row index of the act1-like / act2-like arrays -> group
+    struct ShapeTables {
+        RowTables act[2];
+        void free_device() { for (RowTables& r : act) for (void* p : {(void*)r.d_bt, (void*)r.d_bi, (void*)r.d_wt, (void*)r.d_wi}) (void)hipFree(p); }
+    };
     std::mutex mu;
-    std::map<std::pair<int, int>, WgTables> wg;     // (B, S) -> weight-gradient tile tables
+    std::map<std::pair<int, int>, ShapeTables> shapes;     // (B, S) -> tile tables
     // The weight gradient of a layer and the data gradient that continues the chain both start from the same g and
     // are independent of each other; at B = 16 x S = 11 each is a 0.2 ms launch with a long tail, so the weight
     // gradients go to a side stream (forked / joined with events: capturable into a HIP graph).
@@ -626,88 +635,97 @@ using namespace xsq;
 
 static const int WG_KC = 512;      // rows of one weight-gradient chunk
 
-// tiles of the two weight-gradient launches: (group, column tile, row chunk); chunks of one (group, column tile) consecutive
-static void wg_build(const xsq_train* Tr, int Bn, int S, std::vector<WgTile>* t23, std::vector<WgGroupInfo>* i23,
-                     std::vector<WgTile>* t14, std::vector<WgGroupInfo>* i14) {
-    const int T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    for (int gi = 0; gi < Tr->ngroups; ++gi) {
-        const TrainGroup& g = Tr->groups[gi];
-        const int M2 = Bn * g.F2 * T2, M1 = Bn * g.F1 * T1;
-        const int nch2 = (M2 + WG_KC - 1) / WG_KC, nch1 = (M1 + WG_KC - 1) / WG_KC;
-        i23->push_back(WgGroupInfo{(int)t23->size(), nch2});
-        for (int nt = 0; nt < g.kf; ++nt)
-            for (int ch = 0; ch < nch2; ++ch) t23->push_back(WgTile{gi, nt, ch * WG_KC, std::min(M2, (ch + 1) * WG_KC)});
-        i14->push_back(WgGroupInfo{(int)t14->size(), nch1});
-        const int ntiles = (2 * g.kf * g.T + WgL14Op::NTL - 1) / WgL14Op::NTL;
-        for (int nt = 0; nt < ntiles; ++nt)
-            for (int ch = 0; ch < nch1; ++ch) t14->push_back(WgTile{gi, nt, ch * WG_KC, std::min(M1, (ch + 1) * WG_KC)});
-    }
+static TrainDims train_dims(const xsq_train* Tr, int Bn, int S) {
+    const int T1 = Tr->causal ? 2 * S : 2 * S - 1;
+    return TrainDims{Bn, S, T1, T1 - 3, Tr->causal};
 }
 
-static void bn_build(const xsq_train* Tr, int Bn, int S, int kind, std::vector<BnTile>* t, std::vector<BnInfo>* info) {
-    const int T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    for (int gi = 0; gi < Tr->ngroups; ++gi) {
-        const TrainGroup& g = Tr->groups[gi];
-        const int M = kind == 0 ? Bn * g.F1 * T1 : Bn * g.F2 * T2;
-        const int n = (M + BN_ROWS - 1) / BN_ROWS;
-        info->push_back(BnInfo{(int)t->size(), n});
-        for (int k = 0; k < n; ++k) t->push_back(BnTile{gi, k * BN_ROWS, std::min(M, (k + 1) * BN_ROWS)});
-    }
+// How the rows of one group's array of shape `act` (0 act1-like, 1 act2-like) are cut: BatchNorm tiles of BN_ROWS rows, and the
+// weight gradient whose k runs over these rows (0: layers 1 / 4, 1: layers 2 / 3) as column tiles x chunks of WG_KC rows.  The
+// tile lists (shape_tables) and their lengths (shape_counts, which size the workspace) both come from here.
+struct GroupChunks { int M, nbn, nch, ncol; };
+static GroupChunks group_chunks(const TrainGroup& g, const TrainDims& d, int act) {
+    const int M = act == 0 ? d.Bn * g.F1 * d.T1 : d.Bn * g.F2 * d.T2;
+    const int ncol = act == 0 ? (2 * g.kf * g.T + WgL14Op::NTL - 1) / WgL14Op::NTL : g.kf;
+    return GroupChunks{M, (M + BN_ROWS - 1) / BN_ROWS, (M + WG_KC - 1) / WG_KC, ncol};
 }
 
-// doubles of the reduction scratch: BatchNorm row tiles, bias planes, whitening planes
-static size_t part_doubles(const xsq_train* Tr, int Bn, int S) {
-    std::vector<BnTile> a, b; std::vector<BnInfo> ia, ib;
-    bn_build(Tr, Bn, S, 0, &a, &ia); bn_build(Tr, Bn, S, 1, &b, &ib);
-    return std::max({a.size() * 128, b.size() * 128, (size_t)Tr->ngroups * 2 * Bn, (size_t)Tr->sumF * 4 * Bn * 2});
+struct ShapeCounts {
+    size_t nbt[2] = {0, 0}, nwg[2] = {0, 0};    // BatchNorm tiles / weight-gradient tiles per shape
+    size_t part_doubles, wpart_floats;          // reduction scratch (BatchNorm row tiles, bias planes, whitening planes); chunk sums
+};
+static ShapeCounts shape_counts(const xsq_train* Tr, const TrainDims& d) {
+    ShapeCounts n;
+    for (const TrainGroup& g : Tr->groups)
+        for (int act = 0; act < 2; ++act) {
+            const GroupChunks c = group_chunks(g, d, act);
+            n.nbt[act] += c.nbn;
+            n.nwg[act] += (size_t)c.ncol * c.nch;
+        }
+    n.part_doubles = std::max({n.nbt[0] * 128, n.nbt[1] * 128, (size_t)Tr->ngroups * 2 * d.Bn, (size_t)Tr->sumF * 4 * d.Bn * 2});
+    n.wpart_floats = std::max(n.nwg[1] * 64 * WgL23Op::NTL, n.nwg[0] * 64 * WgL14Op::NTL);
+    return n;
 }
 
-static size_t wg_partial_floats(const xsq_train* Tr, int Bn, int S) {
-    std::vector<WgTile> a, b; std::vector<WgGroupInfo> ia, ib;
-    wg_build(Tr, Bn, S, &a, &ia, &b, &ib);
-    return std::max(a.size() * 64 * WgL23Op::NTL, b.size() * 64 * WgL14Op::NTL);
-}
+// The regions of a workspace in order, each 256-byte aligned.  On a null base it only adds up sizes: the size functions and
+// the step run the same layout code.
+struct Carver {
+    char* base; size_t used;
+    template <class T = void>
+    T* take(size_t bytes) { T* p = base ? reinterpret_cast<T*>(base + used) : nullptr; used += al256(bytes); return p; }
+};
 
-// both sizes walk every group's tile list on the host (~0.1 ms): once per shape, not three times per step
-static std::pair<size_t, size_t> train_sizes(const xsq_train* Tr, int Bn, int S) {
-    std::lock_guard<std::mutex> lk(Tr->size_mu);
-    auto it = Tr->size_cache.find({Bn, S});
-    if (it != Tr->size_cache.end()) return it->second;
-    const std::pair<size_t, size_t> v{part_doubles(Tr, Bn, S), wg_partial_floats(Tr, Bn, S)};
-    Tr->size_cache[{Bn, S}] = v;
-    return v;
-}
+template <class K, class... A>
+static void launch(hipStream_t s, K kernel, dim3 grid, int threads, A... args) { hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, args...); }
 
-static int wg_tables(xsq_train* Tr, int Bn, int S, xsq_train::WgTables* out) {
+// Process switches of the step.
+// XSQ_TRAIN_WGRAD_PACKED=1: the bf16 weight gradients on wgrad_bf16p_kernel (operands rounded once at staging time, k-pair-packed
+// in LDS, one 16-byte fragment read per MFMA operand) -- an A/B arm, bitwise the default's gradients and measured SLOWER
+// (0.30-0.34 ms per launch against 0.24, step 3.19 against 3.02 on one box: its 8-byte staging writes land 16 lanes on four
+// banks and it holds four rows of loads per thread; profiles/r11_ab_runs.txt r11wg).  Default: round 5's kernel.
+// (Built per step, not once per process: tests/test_training.py flips the variable inside one process.)
+struct TrainSwitches {
+    bool wgrad_packed = false;
+    TrainSwitches() { if (const char* e = getenv("XSQ_TRAIN_WGRAD_PACKED")) wgrad_packed = atoi(e) != 0; }
+};
+
+// the weight-gradient kernel of a step: fp32 operands, or with the bf16 arm bf16 operands as well
+template <class Op>
+static auto wgrad_kernel_of(bool bf16, bool packed) {
+    return !bf16 ? wgrad_kernel<Op> : packed ? wgrad_bf16p_kernel<Op> : wgrad_kernel<Op, true>;
+}
+typedef void (*WgradReduce)(const float*, const WgGroupInfo*, const TrainGroup*, int, float*);
+
+// The tables of (B, S) from the cache, or built, uploaded and inserted.  Weight-gradient tiles: (group, column tile, row chunk),
+// the chunks of one (group, column tile) consecutive.
+static int shape_tables(xsq_train* Tr, const TrainDims& d, xsq_train::ShapeTables* out) {
     std::lock_guard<std::mutex> lk(Tr->mu);
-    auto it = Tr->wg.find({Bn, S});
-    if (it != Tr->wg.end()) { *out = it->second; return XSQ_OK; }
-    std::vector<WgTile> a, b; std::vector<WgGroupInfo> ia, ib;
-    wg_build(Tr, Bn, S, &a, &ia, &b, &ib);
-    xsq_train::WgTables w;
-    w.n23 = (int)a.size(); w.n14 = (int)b.size();
-    std::vector<BnTile> b1, b2; std::vector<BnInfo> j1, j2;
-    bn_build(Tr, Bn, S, 0, &b1, &j1); bn_build(Tr, Bn, S, 1, &b2, &j2);
-    w.nbt1 = (int)b1.size(); w.nbt2 = (int)b2.size();
-    int rc = upload(w.d_t23, a);
-    if (!rc) rc = upload(w.d_i23, ia);
-    if (!rc) rc = upload(w.d_t14, b);
-    if (!rc) rc = upload(w.d_i14, ib);
-    if (!rc) rc = upload(w.d_bt1, b1);
-    if (!rc) rc = upload(w.d_bi1, j1);
-    if (!rc) rc = upload(w.d_bt2, b2);
-    if (!rc) rc = upload(w.d_bi2, j2);
-    if (rc) {       // not in the cache yet: nothing else would free what this call allocated
-        (void)hipFree(w.d_t23); (void)hipFree(w.d_i23); (void)hipFree(w.d_t14); (void)hipFree(w.d_i14);
-        (void)hipFree(w.d_bt1); (void)hipFree(w.d_bi1); (void)hipFree(w.d_bt2); (void)hipFree(w.d_bi2);
-        return rc;
+    auto it = Tr->shapes.find({d.Bn, d.S});
+    if (it != Tr->shapes.end()) { *out = it->second; return XSQ_OK; }
+    xsq_train::ShapeTables st;
+    int rc = XSQ_OK;
+    for (int act = 0; act < 2 && !rc; ++act) {
+        std::vector<BnTile> bt; std::vector<BnInfo> bi; std::vector<WgTile> wt; std::vector<WgGroupInfo> wi;
+        for (int gi = 0; gi < Tr->ngroups; ++gi) {
+            const GroupChunks c = group_chunks(Tr->groups[gi], d, act);
+            bi.push_back(BnInfo{(int)bt.size(), c.nbn});
+            for (int k = 0; k < c.nbn; ++k) bt.push_back(BnTile{gi, k * BN_ROWS, std::min(c.M, (k + 1) * BN_ROWS)});
+            wi.push_back(WgGroupInfo{(int)wt.size(), c.nch});
+            for (int nt = 0; nt < c.ncol; ++nt)
+                for (int ch = 0; ch < c.nch; ++ch) wt.push_back(WgTile{gi, nt, ch * WG_KC, std::min(c.M, (ch + 1) * WG_KC)});
+        }
+        xsq_train::RowTables& r = st.act[act];
+        r.nbt = (int)bt.size(); r.nwg = (int)wt.size();
+        rc = upload(r.d_bt, bt);
+        if (!rc) rc = upload(r.d_bi, bi);
+        if (!rc) rc = upload(r.d_wt, wt);
+        if (!rc) rc = upload(r.d_wi, wi);
     }
-    Tr->wg[{Bn, S}] = w;
-    *out = w;
+    if (rc) { st.free_device(); return rc; }       // not in the cache yet: nothing else would free what this call allocated
+    Tr->shapes[{d.Bn, d.S}] = st;
+    *out = st;
     return XSQ_OK;
 }
-
-static int kf_of_t(int F) { return F < 10 ? 1 : (F < 20 ? 3 : 5); }
 
 extern "C" {
 
@@ -721,13 +739,11 @@ int xsq_train_set_precision(xsq_train* T, int mode) {
 int xsq_train_destroy(xsq_train* T) {
     if (!T) return XSQ_OK;
     if (T->model) xsq_model_destroy(T->model);
-    (void)hipFree(T->d_groups); (void)hipFree(T->d_geo); (void)hipFree(T->d_rows); (void)hipFree(T->d_params);
-    (void)hipFree(T->d_grads); (void)hipFree(T->d_m); (void)hipFree(T->d_v); (void)hipFree(T->d_trainable);
-    (void)hipFree(T->d_map_pool); (void)hipFree(T->d_map_mean); (void)hipFree(T->d_map_scale);
-    (void)hipFree(T->d_map_bwd); (void)hipFree(T->d_pool_bwd);
-    for (auto& kv : T->wg) { (void)hipFree(kv.second.d_t23); (void)hipFree(kv.second.d_t14); (void)hipFree(kv.second.d_i23); (void)hipFree(kv.second.d_i14);
-        (void)hipFree(kv.second.d_bt1); (void)hipFree(kv.second.d_bt2); (void)hipFree(kv.second.d_bi1); (void)hipFree(kv.second.d_bi2); }
-    (void)hipFree(T->d_frow1); (void)hipFree(T->d_frow2);
+    for (void* p : {(void*)T->d_groups, (void*)T->d_rows, (void*)T->d_params, (void*)T->d_grads, (void*)T->d_m, (void*)T->d_v,
+                    (void*)T->d_trainable, (void*)T->d_map_pool, (void*)T->d_map_mean, (void*)T->d_map_scale, (void*)T->d_map_bwd,
+                    (void*)T->d_pool_bwd, (void*)T->d_frow[0], (void*)T->d_frow[1]})
+        (void)hipFree(p);
+    for (auto& kv : T->shapes) kv.second.free_device();
     if (T->side) (void)hipStreamDestroy(T->side);
     for (hipEvent_t e : T->ev_fork) if (e) (void)hipEventDestroy(e);
     if (T->ev_join) (void)hipEventDestroy(T->ev_join);
@@ -735,6 +751,30 @@ int xsq_train_destroy(xsq_train* T) {
     if (T->h_loss) (void)hipHostFree(T->h_loss);
     delete T;
     return XSQ_OK;
+}
+
+// GEMM-layout weight slots of one (block, target) <- canonical offsets of the tensors that feed slot w1 .. w4: the same
+// placement as xsq_model_create, without the BatchNorm fold
+static void fill_gemm_slots(std::vector<int>& map, const CdaeBlockDev& cb, int t, int64_t s1, int64_t s2, int64_t s3, int64_t s4) {
+    const int kf = cb.kf, W = cb.T, hop = cb.hop;
+    const int K1 = 2 * kf * W, K2 = kf * 4 * CS;
+    for (int co = 0; co < H1; ++co)
+        for (int k = 0; k < K1; ++k) map[cb.w1[t] + (int64_t)co * cb.ld1 + k] = (int)(s1 + (int64_t)co * K1 + k);
+    for (int co = 0; co < H2; ++co)
+        for (int ci = 0; ci < H1; ++ci)
+            for (int df = 0; df < kf; ++df)
+                for (int dt = 0; dt < 4; ++dt) {
+                    const int64_t src = (((int64_t)co * H1 + ci) * kf + df) * 4 + dt;       // element (co, ci, df, dt) of an H2 x H1 x kf x 4 tensor
+                    map[cb.w2[t] + (int64_t)co * K2 + (df * 4 + dt) * CS + ci] = (int)(s2 + src);
+                    map[cb.w3[t] + (int64_t)ci * K2 + (df * 4 + (3 - dt)) * CS + co] = (int)(s3 + src);     // transposed, time taps reversed
+                }
+    for (int ci = 0; ci < H1; ++ci)
+        for (int c = 0; c < 2; ++c)
+            for (int df = 0; df < kf; ++df)
+                for (int tap = 0; tap < 2; ++tap)
+                    for (int dt = 0; dt < hop; ++dt)
+                        map[cb.w4[t] + (int64_t)(c * hop + dt) * cb.ld4 + (df * 2 + (1 - tap)) * CS + ci] =
+                            (int)(s4 + (((int64_t)ci * 2 + c) * kf + df) * W + dt + tap * hop);
 }
 
 static int train_build(xsq_train* Tr, int nblocks, const int32_t* F, const int32_t* T, int causal, const float* params,
@@ -746,14 +786,12 @@ static int train_build(xsq_train* Tr, int nblocks, const int32_t* F, const int32
     Tr->Fv.assign(F, F + nblocks); Tr->Tv.assign(T, T + nblocks);
     // walk the canonical order once more: offsets of every tensor, trainable mask, gather maps
     std::vector<unsigned char> trainable((size_t)nparams, 1);
-    std::vector<BlockGeo> geo;
     std::vector<int2> rows;
     std::vector<int> map_mean, map_scale;
     int64_t p = 0;
     for (int b = 0; b < nblocks; ++b) {
         const CdaeBlockDev& cb = Mo->blocks[b];
         const int kf = cb.kf, W = cb.T;
-        geo.push_back(BlockGeo{cb.F, cb.T, cb.cum});
         const int64_t p_mean = p, p_scale = p + cb.F;
         for (int f = 0; f < cb.F; ++f) { map_mean.push_back((int)(p_mean + f)); map_scale.push_back((int)(p_scale + f)); }
         for (int f = 0; f < cb.F; ++f) rows.push_back(make_int2((int)Tr->groups.size(), f));
@@ -778,76 +816,24 @@ static int train_build(xsq_train* Tr, int nblocks, const int32_t* F, const int32
     XSQ_REQUIRE(p == nparams, "xsq_train_create: parameter walk mismatch");
     Tr->ngroups = (int)Tr->groups.size();
     Tr->sumF = Mo->sumF;
-    // GEMM-pool gather map: the same placement as xsq_model_create, without the BatchNorm fold
+    // gather maps of the two GEMM pools: the forward's, and the data-gradient operators' in the same slots
     const int64_t extent = Mo->pool_floats;
     Tr->pool_floats = extent;
-    std::vector<int> map((size_t)extent, -1);
-    for (int b = 0; b < nblocks; ++b) {
-        const CdaeBlockDev& cb = Mo->blocks[b];
-        const int kf = cb.kf, W = cb.T, hop = cb.hop;
-        const int K1 = 2 * kf * W, K2 = kf * 4 * CS;
-        for (int t = 0; t < NT; ++t) {
-            const TrainGroup& g = Tr->groups[b * 4 + t];
-            for (int co = 0; co < H1; ++co)
-                for (int k = 0; k < K1; ++k) map[cb.w1[t] + (int64_t)co * cb.ld1 + k] = (int)(g.p_w1 + (int64_t)co * K1 + k);
-            for (int co = 0; co < H2; ++co)
-                for (int ci = 0; ci < H1; ++ci)
-                    for (int df = 0; df < kf; ++df)
-                        for (int dt = 0; dt < 4; ++dt)
-                            map[cb.w2[t] + (int64_t)co * K2 + (df * 4 + dt) * CS + ci] =
-                                (int)(g.p_w2 + (((int64_t)co * H1 + ci) * kf + df) * 4 + dt);
-            for (int co = 0; co < H1; ++co)
-                for (int ci = 0; ci < H2; ++ci)
-                    for (int df = 0; df < kf; ++df)
-                        for (int dt = 0; dt < 4; ++dt)
-                            map[cb.w3[t] + (int64_t)co * K2 + (df * 4 + (3 - dt)) * CS + ci] =
-                                (int)(g.p_w3 + (((int64_t)ci * H1 + co) * kf + df) * 4 + dt);
-            for (int ci = 0; ci < H1; ++ci)
-                for (int c = 0; c < 2; ++c)
-                    for (int df = 0; df < kf; ++df)
-                        for (int tap = 0; tap < 2; ++tap)
-                            for (int dt = 0; dt < hop; ++dt)
-                                map[cb.w4[t] + (int64_t)(c * hop + dt) * cb.ld4 + (df * 2 + (1 - tap)) * CS + ci] =
-                                    (int)(g.p_w4 + (((int64_t)ci * 2 + c) * kf + df) * W + dt + tap * hop);
-            map[cb.b4[t]] = (int)g.p_b4;
-            map[cb.b4[t] + 1] = (int)(g.p_b4 + 1);
-        }
-    }
     // data-gradient operators reuse the forward GEMM operators on the gradient arenas (cdae_api.h):
     //   slot w1 <- w4 (layer-1 operator = d/d a3 of layer 4)      slot w2 <- w3 (layer-2 operator = d/d a2 of layer 3)
     //   slot w3 <- w2 (layer-3 operator = d/d a1 of layer 2)      slot w4 <- w1 (layer-4 operator = d/d xin of layer 1)
-    std::vector<int> mapb((size_t)extent, -1);
-    for (int b = 0; b < nblocks; ++b) {
-        const CdaeBlockDev& cb = Mo->blocks[b];
-        const int kf = cb.kf, W = cb.T, hop = cb.hop;
-        const int K1 = 2 * kf * W, K2 = kf * 4 * CS;
+    // (w1 and w4, w2 and w3 have each other's shapes: H1 x 2 x kf x W and H2 x H1 x kf x 4); no bias there
+    std::vector<int> map((size_t)extent, -1), mapb((size_t)extent, -1);
+    for (int b = 0; b < nblocks; ++b)
         for (int t = 0; t < NT; ++t) {
+            const CdaeBlockDev& cb = Mo->blocks[b];
             const TrainGroup& g = Tr->groups[b * 4 + t];
-            for (int co = 0; co < H1; ++co)
-                for (int k = 0; k < K1; ++k) mapb[cb.w1[t] + (int64_t)co * cb.ld1 + k] = (int)(g.p_w4 + (int64_t)co * K1 + k);
-            for (int c2 = 0; c2 < H2; ++c2)
-                for (int c3 = 0; c3 < H1; ++c3)
-                    for (int df = 0; df < kf; ++df)
-                        for (int dt = 0; dt < 4; ++dt)
-                            mapb[cb.w2[t] + (int64_t)c2 * K2 + (df * 4 + dt) * CS + c3] =
-                                (int)(g.p_w3 + (((int64_t)c2 * H1 + c3) * kf + df) * 4 + dt);
-            for (int c1 = 0; c1 < H1; ++c1)
-                for (int c2 = 0; c2 < H2; ++c2)
-                    for (int df = 0; df < kf; ++df)
-                        for (int dt = 0; dt < 4; ++dt)
-                            mapb[cb.w3[t] + (int64_t)c1 * K2 + (df * 4 + (3 - dt)) * CS + c2] =
-                                (int)(g.p_w2 + (((int64_t)c2 * H1 + c1) * kf + df) * 4 + dt);
-            for (int co = 0; co < H1; ++co)
-                for (int c = 0; c < 2; ++c)
-                    for (int df = 0; df < kf; ++df)
-                        for (int tap = 0; tap < 2; ++tap)
-                            for (int dt = 0; dt < hop; ++dt)
-                                mapb[cb.w4[t] + (int64_t)(c * hop + dt) * cb.ld4 + (df * 2 + (1 - tap)) * CS + co] =
-                                    (int)(g.p_w1 + (((int64_t)co * 2 + c) * kf + df) * W + dt + tap * hop);
+            fill_gemm_slots(map, cb, t, g.p_w1, g.p_w2, g.p_w3, g.p_w4);
+            fill_gemm_slots(mapb, cb, t, g.p_w4, g.p_w3, g.p_w2, g.p_w1);
+            map[cb.b4[t]] = (int)g.p_b4;
+            map[cb.b4[t] + 1] = (int)(g.p_b4 + 1);
         }
-    }
     if (int rc = upload(Tr->d_groups, Tr->groups)) return rc;
-    if (int rc = upload(Tr->d_geo, geo)) return rc;
     if (int rc = upload(Tr->d_rows, rows)) return rc;
     if (int rc = upload(Tr->d_trainable, trainable)) return rc;
     if (int rc = upload(Tr->d_map_pool, map)) return rc;
@@ -860,16 +846,14 @@ static int train_build(xsq_train* Tr, int nblocks, const int32_t* F, const int32
         for (int f = 0; f < g.F1; ++f) frow1[4 * g.cumF1 + g.tgt * g.F1 + f] = gi;
         for (int f = 0; f < g.F2; ++f) frow2[4 * g.cumF2 + g.tgt * g.F2 + f] = gi;
     }
-    if (int rc = upload(Tr->d_frow1, frow1)) return rc;
-    if (int rc = upload(Tr->d_frow2, frow2)) return rc;
+    if (int rc = upload(Tr->d_frow[0], frow1)) return rc;
+    if (int rc = upload(Tr->d_frow[1], frow2)) return rc;
     XSQ_HIP(hipMalloc(&Tr->d_pool_bwd, (size_t)extent * 4));
     if (int rc = upload(Tr->d_params, params, (size_t)nparams)) return rc;
-    XSQ_HIP(hipMalloc(&Tr->d_grads, (size_t)nparams * 4));
-    XSQ_HIP(hipMalloc(&Tr->d_m, (size_t)nparams * 4));
-    XSQ_HIP(hipMalloc(&Tr->d_v, (size_t)nparams * 4));
-    XSQ_HIP(hipMemset(Tr->d_grads, 0, (size_t)nparams * 4));
-    XSQ_HIP(hipMemset(Tr->d_m, 0, (size_t)nparams * 4));
-    XSQ_HIP(hipMemset(Tr->d_v, 0, (size_t)nparams * 4));
+    for (float** pool : {&Tr->d_grads, &Tr->d_m, &Tr->d_v}) {
+        XSQ_HIP(hipMalloc(pool, (size_t)nparams * 4));
+        XSQ_HIP(hipMemset(*pool, 0, (size_t)nparams * 4));
+    }
     return XSQ_OK;
 }
 
@@ -923,252 +907,242 @@ int64_t xsq_train_step_count(xsq_train* Tr, int64_t set) {
     return Tr->step;
 }
 
-// workspace (floats): xin | z1 a1 g1 | z2 a2 g2 | z3 a3 g3 | masks gM | Y gY [Y0] | bn stats | mean scale | loss
+// ---- the two workspace layouts ---------------------------------------------------------------------------------------
+// xin | z1 a1 g1 | z2 a2 g2 | z3 a3 g3 | masks gM | Y gY | [Wiener-EM statistics: forward, backward] | bn stats |
+// reduction scratch | weight-gradient chunk sums | mean scale | loss terms | loss.hip's scratch
+struct TrainWs {
+    float *xin, *z[3], *a[3], *g[3], *masks, *gM, *Y, *gY;      // z, a, g by BatchNorm layer 0 .. 2 (behind layer 1 .. 3)
+    void *wst = nullptr, *wbst = nullptr; size_t wst_bytes;
+    float* stats; double* part; float* wpart; float *mean, *scale; double* d_loss; void* loss_ws;
+    ShapeCounts counts;
+    size_t used;        // bytes up to the end of the last region, slack included: what xsq_train_workspace returns
+};
+static TrainWs train_layout(const xsq_train* Tr, const TrainDims& d, int wiener, void* base) {
+    const xsq_model* Mo = Tr->model;
+    const size_t n2 = (size_t)d.Bn * 2 * d.S * Mo->sumFT, n8 = 4 * n2;
+    const size_t na[2] = {(size_t)CS * d.Bn * d.T1 * 4 * Mo->sumF1, (size_t)CS * d.Bn * d.T2 * 4 * Mo->sumF2};
+    Carver c{(char*)base, 0};
+    auto f = [&](size_t floats) { return c.take<float>(floats * 4); };
+    TrainWs w;
+    w.xin = f(n2);
+    for (int l = 0; l < 3; ++l) { w.z[l] = f(na[l == 1]); w.a[l] = f(na[l == 1]); w.g[l] = f(na[l == 1]); }
+    w.masks = f(n8); w.gM = f(n8); w.Y = f(2 * n8); w.gY = f(2 * n8);
+    w.wst_bytes = wiener ? xsq_wiener_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), d.Bn, d.S, 5000) : 0;
+    if (wiener) { w.wst = c.take(w.wst_bytes); w.wbst = c.take(w.wst_bytes); }
+    w.stats = f((size_t)Tr->ngroups * 3 * 256);
+    w.counts = shape_counts(Tr, d);
+    w.part = c.take<double>(w.counts.part_doubles * 8);
+    w.wpart = f(w.counts.wpart_floats);
+    w.mean = f(Tr->sumF); w.scale = f(Tr->sumF);
+    w.d_loss = c.take<double>((size_t)Tr->nblocks * 16);
+    w.loss_ws = c.take(0);
+    w.used = c.used + xsq_loss_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), d.Bn, d.S) + 4096 + (wiener ? 4096 : 0);
+    return w;
+}
+
 size_t xsq_train_workspace(const xsq_train* Tr, int Bn, int S, int wiener) {
     if (!Tr || Bn <= 0 || S < 3) return 0;
-    const xsq_model* Mo = Tr->model;
-    const int64_t T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    const size_t n2 = (size_t)Bn * 2 * S * Mo->sumFT, n8 = 4 * n2;
-    const size_t a1 = (size_t)CS * Bn * T1 * 4 * Mo->sumF1, a2 = (size_t)CS * Bn * T2 * 4 * Mo->sumF2;
-    size_t b = al256(n2 * 4) + 6 * al256(a1 * 4) + 3 * al256(a2 * 4) + 2 * al256(n8 * 4) + 2 * al256(n8 * 8);
-    const auto sz = train_sizes(Tr, Bn, S);
-    b += al256((size_t)Tr->ngroups * 3 * 256 * 4) + 2 * al256((size_t)Tr->sumF * 4) + al256(sz.first * 8) + al256(sz.second * 4);
-    b += xsq_loss_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S) + al256((size_t)Tr->nblocks * 16) + 4096;
-    if (wiener) b += 2 * al256(xsq_wiener_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S, 5000)) + 4096;
-    return b;
+    return train_layout(Tr, train_dims(Tr, Bn, S), wiener, nullptr).used;
 }
 
 // The SDR term of a step (xsq_train_step_sdr): the plan whose inverse turns the estimate arena into waveforms, the target
-// waveforms (4, B, 2, n), the weight of the term and the workspace behind the step's own.
-struct SdrStep { xsq_plan* plan; const float* yt; int64_t n; float mcoef; void* ws; size_t ws_bytes; };
-// region sizes of that workspace: waveforms (estimates, gradient) | criterion value | sdr.hip | inverse / adjoint transform
-static size_t sdr_transform_ws(xsq_plan* P, int Bn, int S) {
-    const size_t a = xsq_slicqt_inverse_workspace(P, 8 * Bn, S), b = xsq_slicqt_inverse_adjoint_workspace(P, 8 * Bn, S, 1);
-    return (a && b) ? std::max(a, b) : 0;
-}
-
-static int train_step_impl(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
-                           int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_, const SdrStep* sdr);
-
-// One step.  X: mix arena (2B ch), Yt: target arena (8B ch).  apply_update = 0 leaves the parameters untouched
-// (gradients stay readable through xsq_train_read).  loss_out: HOST double[2] (complex MSE, mask sum).
-int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
-                   int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_) {
-    XSQ_REQUIRE(Tr && X && Yt && ws, "xsq_train_step: null argument");
-    XSQ_REQUIRE(Bn > 0 && S >= 3, "xsq_train_step: B=%d S=%d", Bn, S);
-    XSQ_REQUIRE(ws_bytes >= xsq_train_workspace(Tr, Bn, S, wiener), "xsq_train_step: workspace too small");
-    return train_step_impl(Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, ws_bytes, stream_, nullptr);
+// waveforms (4, B, 2, n) and the weight of the term.  Its workspace lies behind the step's own, from al256(TrainWs::used):
+// waveforms (estimates, gradient) | criterion value | sdr.hip | inverse / adjoint transform
+struct SdrStep { xsq_plan* plan; const float* yt; int64_t n; float mcoef; };
+struct SdrWs {
+    float *yest, *gy; double* d_sdr; void *sdr_ws, *transform_ws;
+    size_t transform_at;    // where the transform's region starts: it may use every byte the caller gave from there on
+    size_t used;            // 0: a size that the plan or sdr.hip refuse
+};
+static SdrWs sdr_layout(xsq_plan* P, int Bn, int S, int64_t n, void* base) {
+    const size_t wave = (size_t)8 * Bn * n * 4, crit = xsq_sdr_loss_workspace(Bn, n);
+    const size_t inv = xsq_slicqt_inverse_workspace(P, 8 * Bn, S), adj = xsq_slicqt_inverse_adjoint_workspace(P, 8 * Bn, S, 1);
+    Carver c{(char*)base, 0};
+    SdrWs w;
+    w.yest = c.take<float>(wave); w.gy = c.take<float>(wave);
+    w.d_sdr = c.take<double>((size_t)(1 + 84 * Bn) * 8);
+    w.sdr_ws = c.take(crit);
+    w.transform_at = c.used;
+    w.transform_ws = c.take(0);
+    w.used = (crit && inv && adj) ? c.used + std::max(inv, adj) : 0;
+    return w;
 }
 
 size_t xsq_train_workspace_sdr(const xsq_train* Tr, xsq_plan* P, int Bn, int S, int wiener, int64_t n) {
     const size_t base = xsq_train_workspace(Tr, Bn, S, wiener);
     if (!base || !P || n <= 0) return 0;
-    const size_t sdr = xsq_sdr_loss_workspace(Bn, n), tr = sdr_transform_ws(P, Bn, S);
-    if (!sdr || !tr) return 0;
-    return al256(base) + 2 * al256((size_t)8 * Bn * n * 4) + al256((size_t)(1 + 84 * Bn) * 8) + al256(sdr) + tr;
+    const size_t sdr = sdr_layout(P, Bn, S, n, nullptr).used;
+    return sdr ? al256(base) + sdr : 0;
 }
 
-// The step with the SDR term: loss = complex MSE + mask sum + mcoef * SDR(inverse sliCQT of the estimates, y_targets).
-// loss_out: HOST double[3] (complex MSE, mask sum, SDR criterion unweighted).
-int xsq_train_step_sdr(xsq_train* Tr, xsq_plan* P, const float* X, const float* Yt, const float* y_targets, int64_t n, float mcoef,
-                       int Bn, int S, int wiener, float lr, float wd, int apply_update, double* loss_out, void* ws, size_t ws_bytes,
-                       void* stream_) {
-    XSQ_REQUIRE(Tr && P && X && Yt && y_targets && ws, "xsq_train_step_sdr: null argument");
-    XSQ_REQUIRE(Bn > 0 && S >= 3 && n > 0 && xsq_plan_num_slices(P, n) == S, "xsq_train_step_sdr: B=%d S=%d n=%lld (S must be the plan's slice count of n)",
-                Bn, S, (long long)n);
-    XSQ_REQUIRE(mcoef > 0.f && std::isfinite(mcoef), "xsq_train_step_sdr: mcoef = %g (the term is on for mcoef > 0; use xsq_train_step without it)", (double)mcoef);
-    XSQ_REQUIRE(xsq_plan_num_blocks(P) == Tr->nblocks && xsq_plan_coefs_per_slice(P) == Tr->model->sumFT,
-                "xsq_train_step_sdr: the plan's block table is not the trainer's");
-    const size_t base = al256(xsq_train_workspace(Tr, Bn, S, wiener)), need = xsq_train_workspace_sdr(Tr, P, Bn, S, wiener, n);
-    XSQ_REQUIRE(need && ws_bytes >= need, "xsq_train_step_sdr: workspace too small");
-    const SdrStep sdr{P, y_targets, n, mcoef, (char*)ws + base, ws_bytes - base};
-    return train_step_impl(Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, base, stream_, &sdr);
-}
-
-static int train_step_impl(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
-                           int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_, const SdrStep* sdr) {
-    hipStream_t stream = (hipStream_t)stream_;
+// The pipeline of DESIGN.md section 7, one line per stage.  Nothing is launched before the workspace and the tables are settled.
+static int train_step_impl(const char* who, xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr,
+                           float wd, int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_,
+                           const SdrStep* sdr) {
+    hipStream_t stream = (hipStream_t)stream_, side = Tr->side;
     xsq_model* Mo = Tr->model;
-    const int T1 = Tr->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
-    const TrainDims d{Bn, S, T1, T2, Tr->causal};
-    const size_t n2 = (size_t)Bn * 2 * S * Mo->sumFT, n8 = 4 * n2;
-    const size_t na1 = (size_t)CS * Bn * T1 * 4 * Mo->sumF1, na2 = (size_t)CS * Bn * T2 * 4 * Mo->sumF2;
-    char* w = (char*)ws;
-    auto take = [&](size_t bytes) { void* p = w; w += al256(bytes); return p; };
-    float* xin = (float*)take(n2 * 4);
-    float *z1 = (float*)take(na1 * 4), *a1 = (float*)take(na1 * 4), *g1 = (float*)take(na1 * 4);
-    float *z2 = (float*)take(na2 * 4), *a2 = (float*)take(na2 * 4), *g2 = (float*)take(na2 * 4);
-    float *z3 = (float*)take(na1 * 4), *a3 = (float*)take(na1 * 4), *g3 = (float*)take(na1 * 4);
-    float *masks = (float*)take(n8 * 4), *gM = (float*)take(n8 * 4);
-    float *Y = (float*)take(n8 * 8), *gY = (float*)take(n8 * 8);
-    const size_t wst_bytes = wiener ? xsq_wiener_workspace(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Bn, S, 5000) : 0;
-    void* wst = wiener ? take(wst_bytes) : nullptr;
-    void* wbst = wiener ? take(wst_bytes) : nullptr;
-    float* stats = (float*)take((size_t)Tr->ngroups * 3 * 256 * 4);
-    double* part = (double*)take(train_sizes(Tr, Bn, S).first * 8);
-    xsq_train::WgTables wt;
-    if (int rcw = wg_tables(Tr, Bn, S, &wt)) return rcw;
-    float* wpart = (float*)take(std::max((size_t)wt.n23 * 64 * WgL23Op::NTL, (size_t)wt.n14 * 64 * WgL14Op::NTL) * 4);
-    float *mean = (float*)take((size_t)Tr->sumF * 4), *scale = (float*)take((size_t)Tr->sumF * 4);
-    double* d_loss = (double*)take((size_t)Tr->nblocks * 16);
-    void* loss_ws = w;
+    const int nb = Tr->nblocks;
+    const int32_t *Fb = Tr->Fv.data(), *Tb = Tr->Tv.data();
+    const TrainGroup* gr = Tr->d_groups;
+    float *par = Tr->d_params, *gp = Tr->d_grads;
+    const TrainDims d = train_dims(Tr, Bn, S);
+    const TrainWs L = train_layout(Tr, d, wiener, ws);
+    const size_t sdr_at = al256(L.used);
+    const SdrWs Ls = sdr ? sdr_layout(sdr->plan, Bn, S, sdr->n, (char*)ws + sdr_at) : SdrWs{};
+    XSQ_REQUIRE((sdr ? Ls.used && sdr_at + Ls.used <= ws_bytes : L.used <= ws_bytes), "%s: workspace too small", who);
+    xsq_train::ShapeTables st;
+    if (int rc = shape_tables(Tr, d, &st)) return rc;
+    for (int k = 0; k < 2; ++k)     // the scratch regions were sized from the counts, the launches run over the lists
+        XSQ_REQUIRE((size_t)st.act[k].nbt == L.counts.nbt[k] && (size_t)st.act[k].nwg == L.counts.nwg[k], "%s: tile counts", who);
 
-    auto grid1 = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    // ---- parameters -> GEMM layouts -------------------------------------------------------------
-    auto gather_pools = [&]() {
-        { XSQ_PROF("train_gather", stream); hipLaunchKernelGGL(k_gather, grid1(Tr->pool_floats), dim3(256), 0, stream, Tr->d_params, Tr->d_map_pool, Mo->d_pool, Tr->pool_floats); }
-        { XSQ_PROF("train_gather", stream); hipLaunchKernelGGL(k_gather, grid1(Tr->pool_floats), dim3(256), 0, stream, Tr->d_params, Tr->d_map_bwd, Tr->d_pool_bwd, Tr->pool_floats); }
+    const unsigned G = (unsigned)Tr->ngroups;
+    auto grid1 = [](int64_t n) { return (unsigned)((n + 255) / 256); };
+    int64_t maxP = 0, maxW14 = 0, maxR23 = 0;       // largest group: arena plane, layer-1 / 4 weights, layer-2 / 3 weights
+    for (const TrainGroup& g : Tr->groups) {
+        maxP = std::max<int64_t>(maxP, (int64_t)Bn * 2 * g.F * S * g.T);
+        maxW14 = std::max<int64_t>(maxW14, (int64_t)H1 * 2 * g.kf * g.T);
+        maxR23 = std::max<int64_t>(maxR23, (int64_t)H2 * g.kf * 4 * CS);
+    }
+    // The two activation shapes (xsq_train): BatchNorm layer 0 / 2 works on the act1-like arrays, layer 1 on the act2-like ones;
+    // the weight gradients of layers 1 / 4 contract over the rows of the first, those of layers 2 / 3 over those of the second.
+    struct ActShape { xsq_train::RowTables t; const int* frow; int rows_per_f; unsigned frows; WgradReduce reduce; dim3 rgrid; };
+    const ActShape shape[2] = {
+        {st.act[0], Tr->d_frow[0], Bn * d.T1, (unsigned)(4 * Mo->sumF1), k_wgrad_reduce14, dim3(grid1(maxW14), G)},
+        {st.act[1], Tr->d_frow[1], Bn * d.T2, (unsigned)(4 * Mo->sumF2), k_wgrad_reduce23, dim3(grid1(maxR23), G)}};
+    const TrainSwitches sw;
+    const bool bf16 = Mo->precision == 3;       // the bf16 arm: the weight gradients on bf16 operands as well
+    const auto wg14 = wgrad_kernel_of<WgL14Op>(bf16, sw.wgrad_packed);
+    const auto wg23 = wgrad_kernel_of<WgL23Op>(bf16, sw.wgrad_packed);
+
+    auto gather = [&](const int* map, float* dst, int64_t n) {
+        XSQ_PROF("train_gather", stream);
+        launch(stream, k_gather, grid1(n), 256, par, map, dst, n);
+    };
+    auto gather_pools = [&]() {     // parameters -> the two GEMM layouts
+        gather(Tr->d_map_pool, Mo->d_pool, Tr->pool_floats);
+        gather(Tr->d_map_bwd, Tr->d_pool_bwd, Tr->pool_floats);
         Tr->pools_valid = true;
     };
+    // a = relu(BatchNorm(z)) on batch statistics; the apply kernels run one workgroup per frequency row
+    auto bn_forward = [&](int layer, const float* z, float* a) {
+        const ActShape& s = shape[layer == 1];
+        { XSQ_PROF("train_bn_stats", stream);
+          launch(stream, k_bn_stats_partial, s.t.nbt, 256, z, gr, s.t.d_bt, d, layer, L.part);
+          launch(stream, k_bn_stats_final, G, 64 * BN_FL, L.part, gr, s.t.d_bi, d, layer, L.stats, par, apply_update); }
+        XSQ_PROF("train_bn_relu_apply", stream);
+        launch(stream, k_bn_relu_apply, s.frows, 256, (const float4*)z, (float4*)a, gr, s.frow, s.rows_per_f, layer, L.stats,
+               par);
+    };
+    // g, the gradient of a = relu(BatchNorm(z)), becomes the gradient of z in place; d gamma and d beta on the way
+    auto bn_backward = [&](int layer, const float* z, float* g) {
+        const ActShape& s = shape[layer == 1];
+        { XSQ_PROF("train_bn_bwd_reduce", stream);
+          launch(stream, k_bn_bwd_partial, s.t.nbt, 256, z, g, gr, s.t.d_bt, d, layer, L.stats, par, L.part);
+          launch(stream, k_bn_bwd_final, G, 64 * BN_FL, L.part, gr, s.t.d_bi, d, layer, L.stats, gp); }
+        XSQ_PROF("train_bn_bwd_apply", stream);
+        launch(stream, k_bn_bwd_apply, s.frows, 256, (const float4*)z, (float4*)g, gr, s.frow, s.rows_per_f, layer, L.stats, par);
+    };
+    // The weight gradient of layer 1 .. 4 on the side stream, behind the kernel that has just finished its g (the data gradient
+    // that continues the chain starts from the same g): chunk sums, then their reduction into the canonical layout.
+    auto wgrad = [&](const char* label, int layer, auto kernel, auto op) -> int {
+        const ActShape& s = shape[layer == 2 || layer == 3];
+        XSQ_HIP(hipEventRecord(Tr->ev_fork[4 - layer], stream));
+        XSQ_HIP(hipStreamWaitEvent(side, Tr->ev_fork[4 - layer], 0));
+        XSQ_PROF(label, side);
+        launch(side, kernel, s.t.nwg, 256, op, s.t.d_wt, L.wpart);
+        launch(side, s.reduce, s.rgrid, 256, L.wpart, s.t.d_wi, gr, layer, gp);
+        return XSQ_OK;
+    };
+
+    // ---- parameters -> GEMM layouts -------------------------------------------------------------
     // the weights in GEMM layout: gathered here only on the first step or after the parameters were written from outside --
     // otherwise the gather of step k + 1 was issued BEHIND the update of step k (below), where it runs while the host looks at
     // the loss and prepares the next batch (the device idles there: profiles/r07h_timeline_train.txt) instead of in front
     // of the first GEMM
     if (!Tr->pools_valid) gather_pools();
-    { XSQ_PROF("train_gather", stream); hipLaunchKernelGGL(k_gather, grid1(Tr->sumF), dim3(256), 0, stream, Tr->d_params, Tr->d_map_mean, mean, Tr->sumF); }
-    { XSQ_PROF("train_gather", stream); hipLaunchKernelGGL(k_gather, grid1(Tr->sumF), dim3(256), 0, stream, Tr->d_params, Tr->d_map_scale, scale, Tr->sumF); }
+    gather(Tr->d_map_mean, L.mean, Tr->sumF);
+    gather(Tr->d_map_scale, L.scale, Tr->sumF);
     // ---- forward ----------------------------------------------------------------------------------
     int rc;
-    cdae_launch_magnitude(Mo, X, xin, mean, scale, Bn, S, stream);
-    int64_t maxM1 = 0, maxM2 = 0, maxP = 0, maxW14 = 0, maxR23 = 0;
-    for (const TrainGroup& g : Tr->groups) {
-        maxM1 = std::max<int64_t>(maxM1, (int64_t)Bn * g.F1 * T1 * CS);
-        maxM2 = std::max<int64_t>(maxM2, (int64_t)Bn * g.F2 * T2 * CS);
-        maxP = std::max<int64_t>(maxP, (int64_t)Bn * 2 * g.F * S * g.T);
-        maxW14 = std::max<int64_t>(maxW14, (int64_t)H1 * 2 * g.kf * g.T);
-        maxR23 = std::max<int64_t>(maxR23, (int64_t)H2 * g.kf * 4 * CS);
-    }
-    const unsigned G = (unsigned)Tr->ngroups;
-    const int64_t nq1 = (int64_t)na1 / 4, nq2 = (int64_t)na2 / 4;      // float4s of the act1-like / act2-like arrays
-    CdaeArgs a{Mo->d_blocks, Mo->d_pool, xin, z1, z2, z3, X, Y, masks, Bn, S, T1, T2, Tr->causal, 1, nullptr, nullptr};
+    cdae_launch_magnitude(Mo, X, L.xin, L.mean, L.scale, Bn, S, stream);
+    CdaeArgs a{Mo->d_blocks, Mo->d_pool, L.xin, L.z[0], L.z[1], L.z[2], X, L.Y, L.masks, Bn, S, d.T1, d.T2, Tr->causal, 1,
+               nullptr, nullptr};
     if ((rc = cdae_launch_layer(Mo, 1, a, stream))) return rc;                       // z1
-    { XSQ_PROF("train_bn_stats", stream); hipLaunchKernelGGL(k_bn_stats_partial, dim3(wt.nbt1), dim3(256), 0, stream, z1, Tr->d_groups, wt.d_bt1, d, 0, part);
-      hipLaunchKernelGGL(k_bn_stats_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi1, d, 0, stats, Tr->d_params, apply_update); }
-    { XSQ_PROF("train_bn_relu_apply", stream); hipLaunchKernelGGL(k_bn_relu_apply, dim3((unsigned)(nq1 / ((int64_t)(Bn * T1) * 13))), dim3(256), 0, stream, (const float4*)z1, (float4*)a1, Tr->d_groups, Tr->d_frow1, Bn * T1, nq1, 0, stats, Tr->d_params); }
-    a.act1 = a1; a.act2 = z2;
+    bn_forward(0, L.z[0], L.a[0]); a.act1 = L.a[0];
     if ((rc = cdae_launch_layer(Mo, 2, a, stream))) return rc;                       // z2 from a1
-    { XSQ_PROF("train_bn_stats", stream); hipLaunchKernelGGL(k_bn_stats_partial, dim3(wt.nbt2), dim3(256), 0, stream, z2, Tr->d_groups, wt.d_bt2, d, 1, part);
-      hipLaunchKernelGGL(k_bn_stats_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi2, d, 1, stats, Tr->d_params, apply_update); }
-    { XSQ_PROF("train_bn_relu_apply", stream); hipLaunchKernelGGL(k_bn_relu_apply, dim3((unsigned)(nq2 / ((int64_t)(Bn * T2) * 13))), dim3(256), 0, stream, (const float4*)z2, (float4*)a2, Tr->d_groups, Tr->d_frow2, Bn * T2, nq2, 1, stats, Tr->d_params); }
-    a.act2 = a2; a.act3 = z3;
+    bn_forward(1, L.z[1], L.a[1]); a.act2 = L.a[1];
     if ((rc = cdae_launch_layer(Mo, 3, a, stream))) return rc;                       // z3 from a2
-    { XSQ_PROF("train_bn_stats", stream); hipLaunchKernelGGL(k_bn_stats_partial, dim3(wt.nbt1), dim3(256), 0, stream, z3, Tr->d_groups, wt.d_bt1, d, 2, part);
-      hipLaunchKernelGGL(k_bn_stats_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi1, d, 2, stats, Tr->d_params, apply_update); }
-    { XSQ_PROF("train_bn_relu_apply", stream); hipLaunchKernelGGL(k_bn_relu_apply, dim3((unsigned)(nq1 / ((int64_t)(Bn * T1) * 13))), dim3(256), 0, stream, (const float4*)z3, (float4*)a3, Tr->d_groups, Tr->d_frow1, Bn * T1, nq1, 2, stats, Tr->d_params); }
-    a.act3 = a3;
+    bn_forward(2, L.z[2], L.a[2]); a.act3 = L.a[2];
     // model.py:264-268: the offline model filters the mix-phase estimate (phase.py:18-69).  Layer 4 then stores the
     // masks only; the EM passes -- forward and backward -- form mask * X while they load (no estimate arena, no copy of it).
     if (wiener) a.Y = nullptr;
     if ((rc = cdae_launch_layer(Mo, 4, a, stream))) return rc;                       // masks [, Y = mask * X]
-    if (wiener && (rc = xsq_wiener_em_masked(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), X, masks, Y, Bn, S, 5000, Bn, wst, wst_bytes, stream)))
+    if (wiener && (rc = xsq_wiener_em_masked(nb, Fb, Tb, X, L.masks, L.Y, Bn, S, 5000, Bn, L.wst, L.wst_bytes, stream)))
         return rc;
     // ---- loss + its gradients (one pass) ------------------------------------------------------------
-    if ((rc = loss_forward_backward(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), Y, Yt, masks, Bn, S, d_loss, gY, gM, loss_ws, stream))) return rc;
+    if ((rc = loss_forward_backward(nb, Fb, Tb, L.Y, Yt, L.masks, Bn, S, L.d_loss, L.gY, L.gM, L.loss_ws, stream))) return rc;
     // ---- SDR term: waveforms of the estimates, criterion + gradient on them, its adjoint added into gY --------------
-    double* d_sdr = nullptr;
     if (sdr) {
-        char* sw = (char*)sdr->ws;
-        auto stake = [&](size_t bytes) { void* p = sw; sw += al256(bytes); return p; };
-        const size_t wave = (size_t)8 * Bn * sdr->n * 4;
-        float *yest = (float*)stake(wave), *gy = (float*)stake(wave);
-        d_sdr = (double*)stake((size_t)(1 + 84 * Bn) * 8);
-        void* sdr_ws = stake(xsq_sdr_loss_workspace(Bn, sdr->n));
-        const size_t tws = sdr->ws_bytes - (size_t)(sw - (char*)sdr->ws);
-        if ((rc = xsq_slicqt_inverse(sdr->plan, Y, 8 * Bn, S, sdr->n, yest, sw, tws, stream))) return rc;
-        if ((rc = sdr_loss(yest, sdr->yt, 2 * Bn, sdr->n, sdr->mcoef, d_sdr, gy, sdr_ws, stream))) return rc;
-        if ((rc = xsq_slicqt_inverse_adjoint(sdr->plan, gy, 8 * Bn, S, sdr->n, gY, 1, sw, tws, stream))) return rc;
+        const size_t tws = ws_bytes - sdr_at - Ls.transform_at;
+        if ((rc = xsq_slicqt_inverse(sdr->plan, L.Y, 8 * Bn, S, sdr->n, Ls.yest, Ls.transform_ws, tws, stream))) return rc;
+        if ((rc = sdr_loss(Ls.yest, sdr->yt, 2 * Bn, sdr->n, sdr->mcoef, Ls.d_sdr, Ls.gy, Ls.sdr_ws, stream))) return rc;
+        rc = xsq_slicqt_inverse_adjoint(sdr->plan, Ls.gy, 8 * Bn, S, sdr->n, L.gY, 1, Ls.transform_ws, tws, stream);
+        if (rc) return rc;
     }
     // (Wiener-EM: the last pass of its backward forms the mask gradient itself -- no gradient arena written and re-read)
-    if (wiener && (rc = wiener_em_backward(Tr->nblocks, Tr->Fv.data(), Tr->Tv.data(), X, nullptr, masks, gY, Bn, S, 5000, Bn, wst, wbst, stream, gM)))
+    if (wiener && (rc = wiener_em_backward(nb, Fb, Tb, X, nullptr, L.masks, L.gY, Bn, S, 5000, Bn, L.wst, L.wbst, stream, L.gM)))
         return rc;
-    if (!wiener) { XSQ_PROF("train_mask_bwd", stream); hipLaunchKernelGGL(k_mask_bwd, dim3(grid1(maxP).x, G), dim3(256), 0, stream, (const float2*)X, (const float2*)gY, masks, gM, Tr->d_groups, d); }
-    // ---- backward -----------------------------------------------------------------------------------
-    float* gp = Tr->d_grads;
-    { XSQ_PROF("train_l4_bias_grad", stream); hipLaunchKernelGGL(k_l4_bias_partial, dim3(2 * Bn, G), dim3(256), 0, stream, gM, Tr->d_groups, d, part);
-      hipLaunchKernelGGL(k_l4_bias_final, grid1(2 * Tr->ngroups), dim3(256), 0, stream, part, Tr->d_groups, Tr->ngroups, d, gp); }
-    // weight gradients: on the side stream, each behind the kernel that finishes its g (XSQ_TRAIN_SIDE=0: in line)
-    static const bool use_side = !(getenv("XSQ_TRAIN_SIDE") && atoi(getenv("XSQ_TRAIN_SIDE")) == 0);
-    hipStream_t ws_ = use_side ? Tr->side : stream;
-    auto fork = [&](int i) {
-        if (!use_side) return hipSuccess;
-        hipError_t e = hipEventRecord(Tr->ev_fork[i], stream);
-        return e != hipSuccess ? e : hipStreamWaitEvent(Tr->side, Tr->ev_fork[i], 0);
-    };
-    // bf16 arm: the weight gradients on bf16 operands as well (XSQ_TRAIN_WGRAD_FP32=1: keep them on the fp32 pipe, an A/B arm)
-    static const bool wgrad_fp32 = getenv("XSQ_TRAIN_WGRAD_FP32") && atoi(getenv("XSQ_TRAIN_WGRAD_FP32")) != 0;
-    const bool bf16w = Mo->precision == 3 && !wgrad_fp32;
-    // XSQ_TRAIN_WGRAD_PACKED=1: the bf16 weight gradients on wgrad_bf16p_kernel (operands rounded once at staging time, k-pair-packed
-    // in LDS, one 16-byte fragment read per MFMA operand) -- an A/B arm, bitwise the default's gradients and measured SLOWER
-    // (0.30-0.34 ms per launch against 0.24, step 3.19 against 3.02 on one box: its 8-byte staging writes land 16 lanes on four
-    // banks and it holds four rows of loads per thread; profiles/r11_ab_runs.txt r11wg).  Default: round 5's kernel.
-    const char* wp_ = getenv("XSQ_TRAIN_WGRAD_PACKED");          // (read per step: tests/test_training.py flips it inside one process)
-    const bool wgrad_packed = wp_ && atoi(wp_) != 0;
-    XSQ_HIP(fork(0));
-    { XSQ_PROF("train_l4_wgrad", ws_);
-      if (bf16w && wgrad_packed) hipLaunchKernelGGL((wgrad_bf16p_kernel<WgL14Op>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{a3, gM, Tr->d_groups, d, 1, 0}, wt.d_t14, wpart);
-      else if (bf16w) hipLaunchKernelGGL((wgrad_kernel<WgL14Op, true>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{a3, gM, Tr->d_groups, d, 1, 0}, wt.d_t14, wpart);
-      else hipLaunchKernelGGL((wgrad_kernel<WgL14Op>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{a3, gM, Tr->d_groups, d, 1, 0}, wt.d_t14, wpart);
-      hipLaunchKernelGGL(k_wgrad_reduce14, dim3(grid1(maxW14).x, G), dim3(256), 0, ws_, wpart, wt.d_i14, Tr->d_groups, 4, gp); }
-    CdaeArgs bw{Mo->d_blocks, Tr->d_pool_bwd, xin, g1, g2, g3, X, Y, nullptr, Bn, S, T1, T2, Tr->causal, 1, nullptr, nullptr};
-    bw.xin8 = gM; bw.act1 = g3;                                                    // g_a3 <- g_p4   (layer-1 operator)
+    if (!wiener) {
+        XSQ_PROF("train_mask_bwd", stream);
+        launch(stream, k_mask_bwd, dim3(grid1(maxP), G), 256, (const float2*)X, (const float2*)L.gY, L.masks, L.gM, gr, d);
+    }
+    // ---- backward: per layer its weight gradient (side stream), then the data gradient through the mirrored operator ----
+    { XSQ_PROF("train_l4_bias_grad", stream);
+      launch(stream, k_l4_bias_partial, dim3(2 * Bn, G), 256, L.gM, gr, d, L.part);
+      launch(stream, k_l4_bias_final, grid1(2 * Tr->ngroups), 256, L.part, gr, Tr->ngroups, d, gp); }
+    CdaeArgs bw{Mo->d_blocks, Tr->d_pool_bwd, L.xin, L.g[0], L.g[1], L.g[2], X, L.Y, nullptr, Bn, S, d.T1, d.T2, Tr->causal, 1,
+                nullptr, nullptr};
+    if ((rc = wgrad("train_l4_wgrad", 4, wg14, WgL14Op{L.a[2], L.gM, gr, d, 1, 0}))) return rc;
+    bw.xin8 = L.gM; bw.act1 = L.g[2];                                              // g_a3 <- g_p4   (layer-1 operator)
     if ((rc = cdae_launch_layer(Mo, 1, bw, stream, "train_l4_dgrad_gemm"))) return rc;
     bw.xin8 = nullptr;
-    { XSQ_PROF("train_bn_bwd_reduce", stream); hipLaunchKernelGGL(k_bn_bwd_partial, dim3(wt.nbt1), dim3(256), 0, stream, z3, g3, Tr->d_groups, wt.d_bt1, d, 2, stats, Tr->d_params, part);
-      hipLaunchKernelGGL(k_bn_bwd_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi1, d, 2, stats, gp); }
-    { XSQ_PROF("train_bn_bwd_apply", stream); hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)(nq1 / ((int64_t)(Bn * T1) * 13))), dim3(256), 0, stream, (const float4*)z3, (float4*)g3, Tr->d_groups, Tr->d_frow1, Bn * T1, nq1, 2, stats, Tr->d_params); }
-    XSQ_HIP(fork(1));
-    { XSQ_PROF("train_l3_wgrad", ws_);
-      if (bf16w && wgrad_packed) hipLaunchKernelGGL((wgrad_bf16p_kernel<WgL23Op>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{a2, g3, Tr->d_groups, d}, wt.d_t23, wpart);
-      else if (bf16w) hipLaunchKernelGGL((wgrad_kernel<WgL23Op, true>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{a2, g3, Tr->d_groups, d}, wt.d_t23, wpart);
-      else hipLaunchKernelGGL((wgrad_kernel<WgL23Op>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{a2, g3, Tr->d_groups, d}, wt.d_t23, wpart);
-      hipLaunchKernelGGL(k_wgrad_reduce23, dim3(grid1(maxR23).x, G), dim3(256), 0, ws_, wpart, wt.d_i23, Tr->d_groups, 3, gp); }
-    bw.act1 = g3; bw.act2 = g2;                                                    // g_a2 <- g_z3   (layer-2 operator)
+    bn_backward(2, L.z[2], L.g[2]);
+    if ((rc = wgrad("train_l3_wgrad", 3, wg23, WgL23Op{L.a[1], L.g[2], gr, d}))) return rc;
+    bw.act1 = L.g[2]; bw.act2 = L.g[1];                                            // g_a2 <- g_z3   (layer-2 operator)
     if ((rc = cdae_launch_layer(Mo, 2, bw, stream, "train_l3_dgrad_gemm"))) return rc;
-    { XSQ_PROF("train_bn_bwd_reduce", stream); hipLaunchKernelGGL(k_bn_bwd_partial, dim3(wt.nbt2), dim3(256), 0, stream, z2, g2, Tr->d_groups, wt.d_bt2, d, 1, stats, Tr->d_params, part);
-      hipLaunchKernelGGL(k_bn_bwd_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi2, d, 1, stats, gp); }
-    { XSQ_PROF("train_bn_bwd_apply", stream); hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)(nq2 / ((int64_t)(Bn * T2) * 13))), dim3(256), 0, stream, (const float4*)z2, (float4*)g2, Tr->d_groups, Tr->d_frow2, Bn * T2, nq2, 1, stats, Tr->d_params); }
-    XSQ_HIP(fork(2));
-    { XSQ_PROF("train_l2_wgrad", ws_);
-      if (bf16w && wgrad_packed) hipLaunchKernelGGL((wgrad_bf16p_kernel<WgL23Op>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{g2, a1, Tr->d_groups, d}, wt.d_t23, wpart);
-      else if (bf16w) hipLaunchKernelGGL((wgrad_kernel<WgL23Op, true>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{g2, a1, Tr->d_groups, d}, wt.d_t23, wpart);
-      else hipLaunchKernelGGL((wgrad_kernel<WgL23Op>), dim3(wt.n23), dim3(256), 0, ws_, WgL23Op{g2, a1, Tr->d_groups, d}, wt.d_t23, wpart);
-      hipLaunchKernelGGL(k_wgrad_reduce23, dim3(grid1(maxR23).x, G), dim3(256), 0, ws_, wpart, wt.d_i23, Tr->d_groups, 2, gp); }
-    bw.act2 = g2; bw.act3 = g1;                                                    // g_a1 <- g_z2   (layer-3 operator)
+    bn_backward(1, L.z[1], L.g[1]);
+    if ((rc = wgrad("train_l2_wgrad", 2, wg23, WgL23Op{L.g[1], L.a[0], gr, d}))) return rc;
+    bw.act2 = L.g[1]; bw.act3 = L.g[0];                                            // g_a1 <- g_z2   (layer-3 operator)
     if ((rc = cdae_launch_layer(Mo, 3, bw, stream, "train_l2_dgrad_gemm"))) return rc;
-    { XSQ_PROF("train_bn_bwd_reduce", stream); hipLaunchKernelGGL(k_bn_bwd_partial, dim3(wt.nbt1), dim3(256), 0, stream, z1, g1, Tr->d_groups, wt.d_bt1, d, 0, stats, Tr->d_params, part);
-      hipLaunchKernelGGL(k_bn_bwd_final, dim3(G), dim3(64 * BN_FL), 0, stream, part, Tr->d_groups, wt.d_bi1, d, 0, stats, gp); }
-    { XSQ_PROF("train_bn_bwd_apply", stream); hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)(nq1 / ((int64_t)(Bn * T1) * 13))), dim3(256), 0, stream, (const float4*)z1, (float4*)g1, Tr->d_groups, Tr->d_frow1, Bn * T1, nq1, 0, stats, Tr->d_params); }
-    XSQ_HIP(fork(3));
-    { XSQ_PROF("train_l1_wgrad", ws_);
-      if (bf16w && wgrad_packed) hipLaunchKernelGGL((wgrad_bf16p_kernel<WgL14Op>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{g1, xin, Tr->d_groups, d, 0, 1}, wt.d_t14, wpart);
-      else if (bf16w) hipLaunchKernelGGL((wgrad_kernel<WgL14Op, true>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{g1, xin, Tr->d_groups, d, 0, 1}, wt.d_t14, wpart);
-      else hipLaunchKernelGGL((wgrad_kernel<WgL14Op>), dim3(wt.n14), dim3(256), 0, ws_, WgL14Op{g1, xin, Tr->d_groups, d, 0, 1}, wt.d_t14, wpart);
-      hipLaunchKernelGGL(k_wgrad_reduce14, dim3(grid1(maxW14).x, G), dim3(256), 0, ws_, wpart, wt.d_i14, Tr->d_groups, 1, gp); }
-    bw.act3 = g1; bw.gx8 = gY;                                                     // g_xin (per target) <- g_z1   (layer-4 operator);
+    bn_backward(0, L.z[0], L.g[0]);
+    if ((rc = wgrad("train_l1_wgrad", 1, wg14, WgL14Op{L.g[0], L.xin, gr, d, 0, 1}))) return rc;
+    bw.act3 = L.g[0]; bw.gx8 = L.gY;                                               // g_xin (per target) <- g_z1 (layer-4 op.)
     if ((rc = cdae_launch_layer(Mo, 4, bw, stream, "train_l1_dgrad_gemm"))) return rc;   // gY is free by now
-    { XSQ_PROF("train_input_grad_reduce", stream); hipLaunchKernelGGL(k_input_grad_partial, dim3((unsigned)Tr->sumF, 4 * Bn), dim3(256), 0, stream, xin, gY, Tr->d_groups, Tr->d_rows, d, part);
-      hipLaunchKernelGGL(k_input_grad_final, grid1(Tr->sumF), dim3(256), 0, stream, part, Tr->d_params, Tr->d_groups, Tr->d_rows, (int)Tr->sumF, 4 * Bn, gp); }
-    if (use_side) {      // the caller's stream joins: every gradient is complete before the update / before returning
-        XSQ_HIP(hipEventRecord(Tr->ev_join, Tr->side));
-        XSQ_HIP(hipStreamWaitEvent(stream, Tr->ev_join, 0));
-    }
+    { XSQ_PROF("train_input_grad_reduce", stream);
+      launch(stream, k_input_grad_partial, dim3((unsigned)Tr->sumF, 4 * Bn), 256, L.xin, L.gY, gr, Tr->d_rows, d, L.part);
+      launch(stream, k_input_grad_final, grid1(Tr->sumF), 256, L.part, par, gr, Tr->d_rows, (int)Tr->sumF, 4 * Bn, gp); }
+    // the caller's stream joins: every gradient is complete before the update / before returning
+    XSQ_HIP(hipEventRecord(Tr->ev_join, side));
+    XSQ_HIP(hipStreamWaitEvent(stream, Tr->ev_join, 0));
     // ---- update ---------------------------------------------------------------------------------------
     if (apply_update) {
         Tr->step += 1;
         // 1 - beta and the bias corrections are formed in double and rounded once, as torch.optim.AdamW hands them to its fp32
         // kernels: 1.f - 0.999f is 1.3e-5 (relative) below 0.001, which went straight into the checkpointed exp_avg_sq
         const double b1 = 0.9, b2 = 0.999;
-        { XSQ_PROF("train_adamw", stream); hipLaunchKernelGGL(k_adamw, grid1(Tr->nparams), dim3(256), 0, stream, Tr->d_params, gp, Tr->d_m, Tr->d_v, Tr->d_trainable,
-                           Tr->nparams, lr, wd, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f,
-                           (float)(1.0 - pow(b1, (double)Tr->step)), (float)(1.0 - pow(b2, (double)Tr->step))); }
+        XSQ_PROF("train_adamw", stream);
+        launch(stream, k_adamw, grid1(Tr->nparams), 256, par, gp, Tr->d_m, Tr->d_v, Tr->d_trainable, Tr->nparams, lr, wd,
+               (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f, (float)(1.0 - pow(b1, (double)Tr->step)),
+               (float)(1.0 - pow(b2, (double)Tr->step)));
     }
     XSQ_HIP(hipGetLastError());
     // loss scalars: per-block terms to pinned host memory behind an event (ring slot = ticket % LOSS_RING)
     const int64_t ticket = Tr->seq++;
     const int slot = (int)(ticket % xsq_train::LOSS_RING);
-    XSQ_HIP(hipMemcpyAsync(Tr->h_loss + (size_t)slot * Tr->nblocks * 2, d_loss, (size_t)Tr->nblocks * 16, hipMemcpyDeviceToHost, stream));
-    Tr->has_sdr[slot] = d_sdr != nullptr;
-    if (d_sdr) XSQ_HIP(hipMemcpyAsync(Tr->h_loss + (size_t)xsq_train::LOSS_RING * Tr->nblocks * 2 + slot, d_sdr, 8, hipMemcpyDeviceToHost, stream));
+    XSQ_HIP(hipMemcpyAsync(Tr->h_loss + (size_t)slot * nb * 2, L.d_loss, (size_t)nb * 16, hipMemcpyDeviceToHost, stream));
+    Tr->has_sdr[slot] = sdr != nullptr;
+    double* h_sdr = Tr->h_loss + (size_t)xsq_train::LOSS_RING * nb * 2 + slot;
+    if (sdr) XSQ_HIP(hipMemcpyAsync(h_sdr, Ls.d_sdr, 8, hipMemcpyDeviceToHost, stream));
     XSQ_HIP(hipEventRecord(Tr->ev_loss[slot], stream));
     // the next step's weights in GEMM layout (see above): BEHIND the loss event, so that a caller who waits for the loss --
     // the step and its update are complete by then -- does not wait for them
@@ -1176,6 +1150,33 @@ static int train_step_impl(xsq_train* Tr, const float* X, const float* Yt, int B
     // loss_out given: wait here, as loss.item() does every step in the reference (training.py:110)
     if (!loss_out) return XSQ_OK;
     return sdr ? xsq_train_loss_sdr(Tr, ticket, loss_out) : xsq_train_loss(Tr, ticket, loss_out);
+}
+
+// One step.  X: mix arena (2B ch), Yt: target arena (8B ch).  apply_update = 0 leaves the parameters untouched
+// (gradients stay readable through xsq_train_read).  loss_out: HOST double[2] (complex MSE, mask sum).
+int xsq_train_step(xsq_train* Tr, const float* X, const float* Yt, int Bn, int S, int wiener, float lr, float wd,
+                   int apply_update, double* loss_out, void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(Tr && X && Yt && ws, "xsq_train_step: null argument");
+    XSQ_REQUIRE(Bn > 0 && S >= 3, "xsq_train_step: B=%d S=%d", Bn, S);
+    return train_step_impl("xsq_train_step", Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, ws_bytes, stream_,
+                           nullptr);
+}
+
+// The step with the SDR term: loss = complex MSE + mask sum + mcoef * SDR(inverse sliCQT of the estimates, y_targets).
+// loss_out: HOST double[3] (complex MSE, mask sum, SDR criterion unweighted).
+int xsq_train_step_sdr(xsq_train* Tr, xsq_plan* P, const float* X, const float* Yt, const float* y_targets, int64_t n,
+                       float mcoef, int Bn, int S, int wiener, float lr, float wd, int apply_update, double* loss_out, void* ws,
+                       size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(Tr && P && X && Yt && y_targets && ws, "xsq_train_step_sdr: null argument");
+    XSQ_REQUIRE(Bn > 0 && S >= 3 && n > 0 && xsq_plan_num_slices(P, n) == S,
+                "xsq_train_step_sdr: B=%d S=%d n=%lld (S must be the plan's slice count of n)", Bn, S, (long long)n);
+    XSQ_REQUIRE(mcoef > 0.f && std::isfinite(mcoef),
+                "xsq_train_step_sdr: mcoef = %g (the term is on for mcoef > 0; use xsq_train_step without it)", (double)mcoef);
+    XSQ_REQUIRE(xsq_plan_num_blocks(P) == Tr->nblocks && xsq_plan_coefs_per_slice(P) == Tr->model->sumFT,
+                "xsq_train_step_sdr: the plan's block table is not the trainer's");
+    const SdrStep sdr{P, y_targets, n, mcoef};
+    return train_step_impl("xsq_train_step_sdr", Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, ws_bytes, stream_,
+                           &sdr);
 }
 
 int64_t xsq_train_ticket(xsq_train* Tr) { return Tr ? Tr->seq - 1 : XSQ_ERR_ARG; }

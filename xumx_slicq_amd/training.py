@@ -109,7 +109,10 @@ class Trainer:
         # "bf16": the reference's autocast arithmetic for the convolutions (training.py:473-476): operands rounded to bf16, fp32 accumulate
         _lib.check(_lib.lib.xsq_train_set_precision(self._h, {"fp32": 0, "bf16": 1, "bf16x6": 2}[precision]), "xsq_train_set_precision")
         self._ws = None
+        self._need = {}          # workspace bytes per step shape
+        self._side = None        # stream of the targets' transform, made by the first step()
         self.steps = 0
+        self._synced = 0         # steps already counted into num_batches_tracked by sync_to
 
     def __del__(self):
         try:
@@ -127,7 +130,7 @@ class Trainer:
         sdr = nterms == 3
         name = "xsq_train_step_sdr" if sdr else "xsq_train_step"
         with torch.cuda.device(self.device):
-            need = self.__dict__.setdefault("_need", {}).get(key)
+            need = self._need.get(key)
             if need is None:
                 need = workspace()
                 if need == 0:
@@ -170,8 +173,9 @@ class Trainer:
         y_targets = y_targets.to(self.device, torch.float32)
         # the two transforms are independent: the targets' (4x the rows) goes to a side stream beside the mix's
         main = torch.cuda.current_stream(self.device)
-        side = self.__dict__.setdefault("_side", None) or torch.cuda.Stream(device=self.device)
-        self._side = side
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        side = self._side
         # (straight to the arenas: the module API's list of 70 block views per transform -- built, checked back into an arena
         #  and record_stream'ed one by one -- cost ~0.3 ms of host time per step during which the device sat idle,
         #  profiles/r07h_timeline_train.txt)
@@ -302,7 +306,7 @@ class Trainer:
         sd = unmix.state_dict()
         for k, v in self.state_dict().items():
             sd[k] = v
-        fresh = self.steps - getattr(self, "_synced", 0)
+        fresh = self.steps - self._synced
         for k in sd:
             if k.endswith("num_batches_tracked"):
                 sd[k] = sd[k] + fresh
