@@ -220,6 +220,9 @@ int xsq_model_set_precision(xsq_model* model, int mode);
  *      output quad instead of ten).  An A/B arm, off by default: parity-green and measured 8-10 % slower than F(2, 4) on
  *      MI355X.  Its weights are built only into models created with XSQ_WINO4=1 in the environment; the bit is an error on
  *      any other model.
+ *  16  (with bit 1) layers 2 and 3 of the blocks with ONE frequency tap in one launch where both layers run F(2, 4) (rows of
+ *      layer 2 of >= 127 positions too): layer 2's output stays in LDS (csrc/cdae_wino23.h).  Bit for bit the result of the two
+ *      launches.  On by default: the default mask is 23.
  * The split-bf16 modes, the causal first layer and (bits 1, 8) shorter rows always take the direct kernels.              */
 int xsq_model_set_winograd(xsq_model* model, int on);
 size_t xsq_cdae_workspace(const xsq_model* model, int B, int S);          /* 0 on error */

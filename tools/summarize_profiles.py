@@ -37,6 +37,8 @@ def short(n):
     m = re.match(r"void xsq::cdae_wino_kernel<(true|false)>", n)
     if m:
         return "wino" + ("<CdaeL3>" if m.group(1) == "true" else "<CdaeL2>")
+    if "cdae_wino23_kernel" in n:              # layers 2 + 3 of the one-tap blocks in one launch (cdae_wino23.h)
+        return "wino23<CdaeL2L3>"
     if "cdae_l1f_kernel" in n:                 # layers 1 / 4 as F(2, 2) along the hop (cdae_l1f.h, cdae_l4f.h: round 6)
         return "l1f<CdaeL1>"
     if "cdae_l4f_kernel" in n:

@@ -584,6 +584,7 @@ struct CdaeL4Op {
 }  // namespace xsq
 #include "cdae_slab.h"
 #include "cdae_wino.h"
+#include "cdae_wino23.h"
 #include "cdae_wino4.h"
 #include "cdae_l1f.h"
 #include "cdae_l4f.h"
@@ -677,14 +678,20 @@ static int get_slab_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* ou
     });
 }
 
+// a block that the fused launch of layers 2 and 3 takes (cdae_wino23.h): one frequency tap, so that a row of act3 needs its own
+// row of act2 and act1 only
+static bool block_fuses23(const CdaeBlockDev& d) { return d.kf == 1 && d.F1 == d.F2; }
+
 // tiles of the Winograd kernels, `outs` outputs per entry of a tile: F(2, 4) (cdae_wino.h; outs = 2) -- 64 consecutive output
-// PAIRS of one batch item in the flattened (f, pair) space -- or F(4, 4) (cdae_wino4.h; outs = 4) -- 64 consecutive QUADS
-static int get_wino_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int outs = 2) {
-    return cached_tiles<WinoTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeWino, Bn, S, layer, outs}, out, [&](std::vector<WinoTileDev>& t) {
+// PAIRS of one batch item in the flattened (f, pair) space -- or F(4, 4) (cdae_wino4.h; outs = 4) -- 64 consecutive QUADS.
+// skip_fused: without the blocks of the fused launch (get_wino23_tiles), the others in their order
+static int get_wino_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* out, int outs = 2, bool skip_fused = false) {
+    return cached_tiles<WinoTileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeWino, Bn, S, layer, outs | (skip_fused ? 16 : 0)}, out, [&](std::vector<WinoTileDev>& t) {
         const int T1 = Mo->causal ? 2 * S : 2 * S - 1, T2 = T1 - 3;
         const int To = layer == 2 ? T2 : T1, P = (To + outs - 1) / outs, len = outs == 4 ? W4_QUADS : WN_PAIRS;
         for (int b : blocks_by_taps(Mo)) {
             const CdaeBlockDev& d = Mo->blocks[b];
+            if (skip_fused && block_fuses23(d)) continue;
             for (int tgt = 0; tgt < NT; ++tgt) {
                 const int64_t off1 = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
                 const int64_t off2 = (int64_t)CS * Bn * T2 * (4 * (int64_t)d.cumF2 + (int64_t)tgt * d.F2);   // act2
@@ -699,6 +706,29 @@ static int get_wino_tiles(xsq_model* Mo, int layer, int Bn, int S, TileTable* ou
                         e.Q0 = Q; e.b = bi;
                         t.push_back(e);
                     }
+            }
+        }
+    });
+}
+
+// tiles of the fused layer-2 + layer-3 kernel (cdae_wino23.h): 62 consecutive act3 pairs of one (b, f) row of a one-tap block
+static int get_wino23_tiles(xsq_model* Mo, int Bn, int S, TileTable* out) {
+    return cached_tiles<Wino23TileDev>(Mo->mu, Mo->tiles, TileKey{TileKind::CdaeWino23, Bn, S, 23, 0}, out, [&](std::vector<Wino23TileDev>& t) {
+        const int T1 = Mo->causal ? 2 * S : 2 * S - 1, P = (T1 + 1) / 2;
+        for (int b : blocks_by_taps(Mo)) {
+            const CdaeBlockDev& d = Mo->blocks[b];
+            if (!block_fuses23(d)) continue;
+            for (int tgt = 0; tgt < NT; ++tgt) {
+                Wino23TileDev e;
+                e.F = d.F1;
+                e.in_off = e.out_off = (int64_t)CS * Bn * T1 * (4 * (int64_t)d.cumF1 + (int64_t)tgt * d.F1);   // act1 / act3 of the (block, target)
+                e.shift2_off = d.s2[tgt]; e.shift3_off = d.s3[tgt]; e.u2_off = d.u2[tgt]; e.u3_off = d.u3[tgt];
+                for (int bi = 0; bi < Bn; ++bi)
+                    for (int f = 0; f < d.F1; ++f)
+                        for (int A = 0; A < P; A += WN23_OUT) {
+                            e.A = A; e.f = f; e.b = bi;
+                            t.push_back(e);
+                        }
             }
         }
     });
@@ -1013,7 +1043,8 @@ int xsq_model_set_wiener_options(xsq_model* Mo, int softmask, int residual) {
 }
 
 int xsq_model_set_winograd(xsq_model* Mo, int on) {
-    XSQ_REQUIRE(Mo && on >= 0 && on <= 15, "xsq_model_set_winograd: null model or mask %d (1 = layers 2 / 3 Winograd F(2, 4), 2 / 4 = layer 1 / 4 F(2, 2), 8 = F(4, 4) for long rows)", on);
+    XSQ_REQUIRE(Mo && on >= 0 && on <= 31, "xsq_model_set_winograd: null model or mask %d (1 = layers 2 / 3 Winograd F(2, 4), 2 / 4 = layer 1 / 4 F(2, 2), 8 = F(4, 4) for long rows, "
+                "16 = one-tap blocks' layers 2 and 3 in one launch)", on);
     XSQ_REQUIRE(!(on & 8) || Mo->wino4, "xsq_model_set_winograd: bit 8 (F(4, 4)) needs a model created with XSQ_WINO4=1 in the environment");
     Mo->winograd = on;
     return XSQ_OK;
@@ -1063,6 +1094,36 @@ static auto slab_kernel(bool bf3, bool bf6) {
     return bf3 ? cdae_slab_kernel<TRANSPOSED, 1> : bf6 ? cdae_slab_kernel<TRANSPOSED, 2> : cdae_slab_kernel<TRANSPOSED, 3, true>;
 }
 
+// which Winograd kernel layers 2 / 3 take on rows of To outputs: 0 none (the direct kernels), 2 = F(2, 4) (cdae_wino.h), 4 = F(4, 4)
+// (cdae_wino4.h).  xsq_model_set_winograd without bit 1: the direct slab kernels.
+static int wino_arm(const xsq_model* Mo, int To) {
+    if (!(Mo->winograd & 1) || To < 86 || (To + 1) / 2 < WN_PAIRS) return 0;      // F(2, 4): rows of >= 64 pairs, i.e. To >= 127
+    return ((Mo->winograd & 8) && Mo->wino4 && (To + 3) / 4 >= W4_QUADS) ? 4 : 2;   // bit 8: F(4, 4) on rows of >= 64 quads, i.e. To >= 253
+}
+
+// fp32 inference with bit 16 of xsq_model_set_winograd, at shapes where BOTH layers take the F(2, 4) kernel: the one-tap blocks'
+// layers 2 and 3 run in one launch (cdae_wino23.h) and the two layers' own tables skip them.  (Only xsq_cdae_forward_xin sets
+// CdaeArgs::upool, and it runs cdae_launch_fused23 behind layer 1.)
+static bool fuses23(const xsq_model* Mo, const CdaeArgs& a) {
+    const bool fp32 = !a.raw && !a.xin8 && !a.gx8 && !a.split && Mo->precision != 2 && Mo->precision != 3;
+    if (!fp32 || !a.upool || !(Mo->winograd & 16) || wino_arm(Mo, a.T1) != 2 || wino_arm(Mo, a.T2) != 2) return false;
+    for (const CdaeBlockDev& d : Mo->blocks) if (block_fuses23(d)) return true;
+    return false;
+}
+
+int cdae_launch_fused23(xsq_model* Mo, const CdaeArgs& a, hipStream_t stream) {
+    if (!fuses23(Mo, a)) return XSQ_OK;
+    for (const CdaeBlockDev& d : Mo->blocks)
+        XSQ_REQUIRE((int64_t)4 * CS * a.Bn * a.T1 * d.F1 < ((int64_t)1 << 30), "xsq_cdae_forward: B=%d S=%d overflows the 32-bit "
+                    "offsets of a block's activations; split the batch", a.Bn, a.S);
+    TileTable tt;
+    if (int rc = get_wino23_tiles(Mo, a.Bn, a.S, &tt)) return rc;
+    // one event pair, half of its time under each layer's name (bench.py counts equal flops for the two layers on every block)
+    ProfScope prof("cdae_l2_slab", "cdae_l3_slab", stream);
+    launch_tiles<Wino23TileDev>(cdae_wino23_kernel, 256, a, tt, stream);
+    return XSQ_OK;
+}
+
 int cdae_launch_layer(xsq_model* Mo, int layer, const CdaeArgs& a, hipStream_t stream, const char* prof_name) {
     // layers 1 and 4 read their operand rows through buffer descriptors with 32-bit byte offsets and out-of-range switches
     // (common.h), layer 4 stores its masks that way: a block's whitened magnitudes / masks of one target and its layer-3
@@ -1093,16 +1154,15 @@ int cdae_launch_layer(xsq_model* Mo, int layer, const CdaeArgs& a, hipStream_t s
             XSQ_REQUIRE((int64_t)4 * CS * a.Bn * a.T1 * d.F1 < ((int64_t)1 << 30), "xsq_cdae_forward: B=%d S=%d overflows the 32-bit "
                         "offsets of a block's activations; split the batch", a.Bn, a.S);
         const char* name = prof_name ? prof_name : (layer == 2 ? "cdae_l2_slab" : "cdae_l3_slab");      // its own event name: one kernel, one name
-        // fp32: Winograd F(2, 4) along the four time taps (cdae_wino.h) -- 5 instead of 8 MFMA products per output pair;
-        // rows of >= 64 pairs, i.e. To >= 127.  xsq_model_set_winograd(0): the direct slab kernels.
-        const bool wino = fp32 && a.upool && (Mo->winograd & 1) && (To + 1) / 2 >= WN_PAIRS;
-        if (wino && (Mo->winograd & 8) && Mo->wino4 && (To + 3) / 4 >= W4_QUADS) {
-            // bit 8: F(4, 4) (cdae_wino4.h) -- 7 products per output quad instead of 10; rows of >= 64 quads, i.e. To >= 253
+        // fp32: Winograd F(2, 4) along the four time taps (cdae_wino.h) -- 5 instead of 8 MFMA products per output pair -- or
+        // F(4, 4) (cdae_wino4.h) -- 7 products per output quad instead of 10
+        const int arm = fp32 && a.upool ? wino_arm(Mo, To) : 0;
+        if (arm == 4) {
             if ((rc = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, 4))) return rc;
             XSQ_PROF(name, stream);
             launch_tiles<WinoTileDev>(layer == 2 ? cdae_wino4_kernel<false> : cdae_wino4_kernel<true>, 512, a, tt, stream);
-        } else if (wino) {
-            if ((rc = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, 2))) return rc;
+        } else if (arm == 2) {
+            if ((rc = get_wino_tiles(Mo, layer, a.Bn, a.S, &tt, 2, fuses23(Mo, a)))) return rc;     // (the fused launch took the one-tap blocks)
             XSQ_PROF(name, stream);
             launch_tiles<WinoTileDev>(layer == 2 ? cdae_wino_kernel<false> : cdae_wino_kernel<true>, 256, a, tt, stream);
         } else {
@@ -1218,7 +1278,8 @@ int xsq_cdae_forward_xin(xsq_model* Mo, const float* X, int Bn, int S, float* Y,
     a.poolB = split ? Mo->d_pool_split : nullptr;
     a.upool = Mo->d_upool;
     for (int layer = 1; layer <= 4; ++layer) {
-        const int rc = cdae_launch_layer(Mo, layer, a, stream);
+        int rc = cdae_launch_layer(Mo, layer, a, stream);
+        if (!rc && layer == 1) rc = cdae_launch_fused23(Mo, a, stream);      // act1 -> act3 of the one-tap blocks, where it applies
         if (rc) return rc;
     }
     XSQ_HIP(hipGetLastError());

@@ -33,9 +33,10 @@ struct CdaeBlockDev {
 struct xsq_model {
     int causal = 0;
     int precision = 0;             // 0 fp32 MFMA, 1 split-bf16 MFMA (xsq_model_set_precision)
-    int winograd = 7;              // fast-convolution forms of the fp32 inference layers (xsq_model_set_winograd), a bit mask: 1 = layers 2 / 3 as Winograd
+    int winograd = 23;             // fast-convolution forms of the fp32 inference layers (xsq_model_set_winograd), a bit mask: 1 = layers 2 / 3 as Winograd
                                    // F(2, 4) along the time taps (cdae_wino.h), 2 / 4 = layer 1 / layer 4 as F(2, 2) along the hop (cdae_l1f.h, cdae_l4f.h),
-                                   // 8 = layers 2 / 3 as F(4, 4) where the rows are long enough (cdae_wino4.h; needs bit 1); 0 = the direct kernels
+                                   // 8 = layers 2 / 3 as F(4, 4) where the rows are long enough (cdae_wino4.h; needs bit 1), 16 = layers 2 and 3 of the one-tap blocks in one
+                                   // launch where both run F(2, 4) (cdae_wino23.h; needs bit 1); 0 = the direct kernels
     int wiener_flags = 0;          // XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL: the post-filter options of the whole call (xsq_model_set_wiener_options)
     bool wino4 = false;            // the F(4, 4) weights of layers 2 / 3 exist (XSQ_WINO4=1 at xsq_model_create; cdae_wino4.h)
     int nblocks = 0;

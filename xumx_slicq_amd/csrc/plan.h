@@ -25,7 +25,7 @@ struct TileTable {
 
 // Key of a cached tile table: the builder, the call shape and the builder's own parameters, each in a field of its own --
 // two builders, or two parameter sets of one builder, cannot meet in one key.
-enum class TileKind { BandGemm, Dft4Full, CdaeGemm, CdaeSlab, CdaeWino, CdaeL1f, CdaeL4f };
+enum class TileKind { BandGemm, Dft4Full, CdaeGemm, CdaeSlab, CdaeWino, CdaeWino23, CdaeL1f, CdaeL4f };
 struct TileKey {
     TileKind kind;
     int rows, S;        // call shape: rows of the transform (S = `share`) / batch items and slices of the CDAE

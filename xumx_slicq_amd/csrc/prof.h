@@ -6,7 +6,7 @@
 namespace xsq {
 bool prof_enabled();
 bool prof_wanted(const char* name);
-void prof_begin(const char* name, hipStream_t stream);
+void prof_begin(const char* name, hipStream_t stream, const char* name2 = nullptr);
 void prof_end(hipStream_t stream);
 
 struct ProfScope {
@@ -14,6 +14,10 @@ struct ProfScope {
     bool on;
     ProfScope(const char* name, hipStream_t stream) : s(stream), on(prof_wanted(name)) {
         if (on) prof_begin(name, s);
+    }
+    // one launch that does the work of two event names: one event pair, half of its time and one launch under each
+    ProfScope(const char* name, const char* name2, hipStream_t stream) : s(stream), on(prof_wanted(name) || prof_wanted(name2)) {
+        if (on) prof_begin(name, s, name2);
     }
     ~ProfScope() {
         if (on) prof_end(s);

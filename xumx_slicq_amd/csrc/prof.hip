@@ -11,6 +11,7 @@ namespace xsq {
 
 struct Pending {
     const char* name;
+    const char* name2;              // non-null: the launch is shared, half of its time goes to each name
     hipEvent_t a, b;
 };
 static std::mutex g_mu;
@@ -34,9 +35,9 @@ static hipEvent_t get_event() {
 bool prof_enabled() { return g_on; }
 bool prof_wanted(const char* name) { return g_on && (g_only.empty() || g_only == name); }
 
-void prof_begin(const char* name, hipStream_t stream) {
+void prof_begin(const char* name, hipStream_t stream, const char* name2) {
     std::lock_guard<std::mutex> lk(g_mu);
-    Pending p{name, get_event(), get_event()};
+    Pending p{name, name2, get_event(), get_event()};
     (void)hipEventRecord(p.a, stream);
     g_pending.push_back(p);
 }
@@ -51,9 +52,12 @@ static void collect_locked() {
         (void)hipEventSynchronize(p.b);
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            auto& e = g_acc[p.name];
-            e.first += ms;
-            e.second += 1;
+            for (const char* name : {p.name, p.name2}) {
+                if (!name || (p.name2 && !g_only.empty() && g_only != name)) continue;
+                auto& e = g_acc[name];
+                e.first += p.name2 ? 0.5 * ms : ms;
+                e.second += 1;
+            }
         }
         g_pool.push_back(p.a);
         g_pool.push_back(p.b);

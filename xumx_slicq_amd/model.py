@@ -336,7 +336,7 @@ class Unmix(nn.Module):
                 1 if causal.pop() else 0, params.ctypes.data, params.size), "xsq_model_create")
             # inside the device guard: bf16 modes allocate and launch on the CURRENT device
             _lib.check(_lib.lib.xsq_model_set_precision(out, _PRECISIONS[self.precision]), "xsq_model_set_precision")
-            _lib.check(_lib.lib.xsq_model_set_winograd(out, int(getattr(self, "winograd", 7))), "xsq_model_set_winograd")
+            _lib.check(_lib.lib.xsq_model_set_winograd(out, int(getattr(self, "winograd", 23))), "xsq_model_set_winograd")
             _lib.check(_lib.lib.xsq_model_set_wiener_options(out, *self.wiener_options()), "xsq_model_set_wiener_options")
         self._handles[idx] = (ver, out)
         return out
@@ -366,8 +366,10 @@ class Unmix(nn.Module):
         """Fast-convolution forms of the fp32 inference layers.  True (default) = all of them, False = the direct kernels, an int =
         a bit mask: 1 = layers 2 / 3 of long rows as Winograd F(2, 4) along the four time taps (csrc/cdae_wino.h), 2 / 4 = layer 1 /
         layer 4 as F(2, 2) along the hop (csrc/cdae_l1f.h, csrc/cdae_l4f.h), 8 = layers 2 / 3 of rows >= 253 as F(4, 4) (csrc/cdae_wino4.h: an A/B
-        arm, measured slower; needs a model created with XSQ_WINO4=1).  Same result to fp32 rounding (~2e-7 of a layer's output)."""
-        self.winograd = (7 if on else 0) if isinstance(on, bool) else int(on)
+        arm, measured slower; needs a model created with XSQ_WINO4=1), 16 = layers 2 and 3 of the one-tap blocks in one launch where both run
+        F(2, 4) (csrc/cdae_wino23.h: bit for bit the two launches' result).  True = 23.  Same result to fp32 rounding (~2e-7 of a layer's
+        output)."""
+        self.winograd = (23 if on else 0) if isinstance(on, bool) else int(on)
         for _ver, h in self._handles.values():
             _lib.check(_lib.lib.xsq_model_set_winograd(h, self.winograd), "xsq_model_set_winograd")
 

@@ -46,7 +46,7 @@ SWITCHES = {
     "max_item_slices": ("separator", None, 0, True),
     "wiener_masked": ("model", "XSQ_WIENER_MASKED", True, True),
     "niter_method": ("model", None, "auto", True),
-    "winograd": ("model", None, 7, True),
+    "winograd": ("model", None, 23, True),
     "precision": ("model", None, "fp32", False),
 }
 _ABSENT = object()
