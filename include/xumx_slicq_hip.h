@@ -728,6 +728,36 @@ int xsq_slicqt_inverse_masked_carry(xsq_plan* plan, const float* masks, const fl
                                     int shift, int64_t length, float* y, int64_t y_stride, const float* carry_in, float* carry_out,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- scoring a separation (csrc/score.hip) -------------------------------------------------------------------------
+ * Replaces the host half of evaluation.py:16-44 (museval's headline SDR) and slicqfinder.py:20-40 (_fast_sdr) for waveforms
+ * that are already on the device.  A track of N samples has F = max(1, N / W) frames of W samples (hop = window); N < W is one
+ * frame of N samples; a tail shorter than W belongs to no frame.  Per target i, row b and frame, over the frame's samples and
+ * both channels, formed in fp64 from the fp32 samples:  num = sum s^2,  den = sum (s_hat - s)^2,  est = sum s_hat^2.
+ * table (device, fp64; the CALLER zeroes it before a track's first piece): moments (4, B, F + 1, 2) = (num, den), cell F the
+ *   tail, followed by the estimates' energies (4, B, F + 1), which the joint silence rule needs.
+ * xsq_score_workspace: *table_bytes and *ws_bytes for a track, enough for any piece of it; refuses more than
+ *   xsq_score_max_frames() frames (the median is a sort in LDS), saying so.
+ * xsq_score_accumulate: adds samples [offset, offset + n) of the track to the table.  est / tgt point at the piece's first
+ *   sample of row 0; row (stem j, b, channel c) lies ((j * B + b) * 2 + c) * row_stride floats further, so a view into a longer
+ *   tensor is read where it lies.  Target i is row block i of tgt and row block perm[i] of est (perm: HOST array of four
+ *   different values in 0..4; est holds every stem it names, a fifth, residual stem is simply never named).  16-byte loads
+ *   when both strides are multiples of 4 and est and tgt share their alignment modulo 16 bytes, 4-byte loads otherwise.  Two
+ *   launches; no atomics: within a launch every cell has one reduction tree and one writer, launches on one stream add in
+ *   order, so one way of cutting a track into pieces gives the same bits on every run.  Pieces must not overlap.
+ * xsq_score_finalise: table -> out_frames fp64 (4, B, F): 10 log10(num / den), +inf for den == 0, NaN for a silent frame
+ *   (XSQ_SCORE_SILENT_ANY: some target's num or est is 0 in the frame; XSQ_SCORE_SILENT_OWN: the target's own num is 0); and
+ *   out_scores fp64 (4, B, 2): the nanmedian of the frames (exact selection; the mean of the two middle values for an even
+ *   count; NaN when every frame is NaN) and 10 log10((sum num + 1e-10) / (sum den + 1e-10)) over all cells, the tail included. */
+#define XSQ_SCORE_SILENT_ANY 0
+#define XSQ_SCORE_SILENT_OWN 1
+int xsq_score_max_frames(void);
+int xsq_score_workspace(int B, int64_t N, int64_t W, size_t* table_bytes, size_t* ws_bytes);
+int xsq_score_accumulate(const float* est, const float* tgt, const int* perm, int B, int64_t n, int64_t est_row_stride,
+                         int64_t tgt_row_stride, int64_t offset, int64_t N, int64_t W, double* table, void* ws, size_t ws_bytes,
+                         void* stream);
+int xsq_score_finalise(const double* table, int B, int64_t frames, int silent_mode, double* out_frames, double* out_scores,
+                       void* stream);
+
 /* ---- per-kernel timing (bench.py roofline) ------------------------------------------
  * When enabled, every kernel launch of the library is bracketed by hipEvents recorded on
  * its own launch stream.  xsq_profile_read synchronises the outstanding events and

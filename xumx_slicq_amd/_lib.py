@@ -163,6 +163,11 @@ _SIGS = {
     "xsq_crossfade_place_sources": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                               C.c_int, _vp]),
     "xsq_batch_assemble": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
+    "xsq_score_max_frames": (C.c_int, []),
+    "xsq_score_workspace": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "xsq_score_accumulate": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp,
+                                       C.c_size_t, _vp]),
+    "xsq_score_finalise": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -83,6 +83,14 @@ __device__ __forceinline__ void buf_st4(float4 v, __amdgpu_buffer_rsrc_t r, unsi
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(buf_u32x4, v), r, (int)vo, so, 0);
 }
 
+// Sum of one double per lane over the 64 lanes of a wave, in lane 0: the fixed shuffle tree of every fp64 reduction here
+// (sdr.hip, score.hip) -- the same tree on every run, so the sums are bitwise reproducible.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
+    return v;
+}
+
 struct TileDev;
 // tiles of one group: 128-row x 64-column tiles, plus a 32-column tile when the N tail is <= 32
 template <class Vec>

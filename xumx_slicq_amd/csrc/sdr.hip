@@ -60,9 +60,7 @@ __global__ __launch_bounds__(256) void k_sdr_moments(const float* __restrict__ p
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int m = 0; m < SDR_NM; ++m) {
-        double v = acc[m];
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
+        const double v = wave_sum(acc[m]);
         if (lane == 0) red[wave][m] = v;
     }
     __syncthreads();
@@ -135,8 +133,7 @@ __global__ __launch_bounds__(64) void k_sdr_finalise(const double* __restrict__ 
 __global__ __launch_bounds__(64) void k_sdr_total(const double* __restrict__ rowloss, int R, double* __restrict__ out) {
     double a = 0.0;
     for (int i = threadIdx.x; i < 14 * R; i += 64) a += rowloss[i];
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) a += __shfl_down(a, s, 64);
+    a = wave_sum(a);
     if (threadIdx.x == 0) out[0] = a / (14.0 * (double)R);
 }
 
