@@ -668,6 +668,35 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* model, const float
                                    int64_t chunk_size, int64_t chunk_len, int64_t ov, int max_stack, int wiener, float* out,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the ideal-mask oracle (ideal_slicqt of xumx_slicq_v2/slicqfinder.py:43-117) -------------------------------------------
+ * What a filterbank can reach at best: the true stems are transformed, their magnitudes keep the phase of the mix
+ * (strategy XSQ_IDEAL_PHASEMIX) or go through one Wiener-EM iteration (XSQ_IDEAL_WIENER), and the result is inverted.
+ * The forward transform of the four stems stacked as rows IS the estimates' arena (source-major, 8*B complex channels), so
+ * the filters below read that arena and need neither a mix arena nor magnitudes.  Per point and channel:
+ *   m   = eps + sum_j (s_j + eps) on the real and on the imaginary part, eps = 1e-10 (slicqfinder.py:57,71: 5e-10 in all);
+ *   v_j = |s_j|;  start y_j = v_j m/|m| with angle(0) = 0, as xsq_phasemix.
+ * xsq_phasemix_sources: Y = the starts.  xsq_wiener_em_sources: one iteration of norbert.wiener(v, m, 1, False) on them, the
+ *   arithmetic of xsq_wiener_em (window statistics, the window maximum over the rows of a batch_group, the 2x2 solve per
+ *   point).  Sc is read once by the statistics pass and once by the apply pass, Y is written once; Y == Sc (in place) is
+ *   allowed and gives the same bits.  Both arenas 16-byte aligned.  win_len == 0: one window over all frames of a row.  One
+ *   iteration only -- the entry point has no count to pass: a further one needs the mix in memory (write the estimates and call
+ *   xsq_wiener_em_iter with a mix arena) -- and no softmask / residual.  No atomics: the same bits on every run.
+ *   workspace: xsq_wiener_sources_workspace bytes (0 on error).
+ * xsq_ideal_separate: sources (4, B, 2, n) -> estimates (4, B, 2, n), DEVICE fp32 contiguous, in one call:
+ *   xsq_slicqt_forward on the 8*B rows -> the filter of `strategy` in place (batch_group = 1: every item is a track of its
+ *   own) -> xsq_slicqt_inverse to n samples.  XSQ_ERR_ARG for null or misshapen arguments and for a shape whose arena does
+ *   not fit one launch (xsq_ideal_workspace returns 0 for it), XSQ_ERR_WORKSPACE for a workspace below xsq_ideal_workspace. */
+#define XSQ_IDEAL_WIENER 0
+#define XSQ_IDEAL_PHASEMIX 1
+size_t xsq_wiener_sources_workspace(int nblocks, const int32_t* F, const int32_t* T, int B, int S, int win_len);
+int xsq_wiener_em_sources(int nblocks, const int32_t* F, const int32_t* T, const float* Sc, float* Y, int B, int S,
+                          int win_len, int batch_group, void* workspace, size_t workspace_bytes, void* stream);
+int xsq_phasemix_sources(int nblocks, const int32_t* F, const int32_t* T, const float* Sc, float* Y, int B, int S,
+                         void* stream);
+size_t xsq_ideal_workspace(xsq_demixer* d, int B, int64_t n, int strategy, int win_len);
+int xsq_ideal_separate(xsq_demixer* d, const float* sources, int B, int64_t n, int strategy, int win_len, float* estimates,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the streaming session: Separator.stream, block-by-block demixing equal to one forward ---------------------------
  * With h = L / 4, slice s covers the samples [(2s - 2)h, (2s + 2)h) and block k = samples [2kh, (2k + 2)h) is the second half
  * of inverted slice k plus the first half of slice k + 1.  In mix-phase mode the mask of slice s depends on the coefficients

@@ -168,6 +168,11 @@ _SIGS = {
     "xsq_score_accumulate": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp,
                                        C.c_size_t, _vp]),
     "xsq_score_finalise": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "xsq_wiener_sources_workspace": (C.c_size_t, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    "xsq_wiener_em_sources": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "xsq_phasemix_sources": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "xsq_ideal_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "xsq_ideal_separate": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

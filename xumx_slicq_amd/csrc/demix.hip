@@ -851,6 +851,73 @@ int xsq_separator_forward_segments(xsq_demixer* d, xsq_model* Mo, const float* a
     return XSQ_OK;
 }
 
+// ---- the ideal-mask oracle (slicqfinder.py:43-117): forward of the stems -> filter in place -> inverse ------------------
+namespace {
+
+struct IdealLayout { size_t Y, tf, wien, total, Y_bytes, tf_bytes, wien_bytes; int S; };
+
+// workspace of a call: the arena of the 8B channels | transform ws (forward, then inverse: one after the other) | statistics.
+// XSQ_ERR_ARG, with the reason, for a shape the stages would refuse: nothing is launched for it.
+static int ideal_layout(const char* who, xsq_demixer* d, int B, int64_t n, int strategy, int win_len, IdealLayout* L) {
+    XSQ_REQUIRE(d, "%s: null demixer", who);
+    XSQ_REQUIRE(B > 0 && n > 0, "%s: B=%d n=%lld", who, B, (long long)n);
+    XSQ_REQUIRE(strategy == XSQ_IDEAL_WIENER || strategy == XSQ_IDEAL_PHASEMIX, "%s: strategy=%d (XSQ_IDEAL_WIENER, XSQ_IDEAL_PHASEMIX)", who,
+                strategy);
+    XSQ_REQUIRE(win_len >= 0, "%s: win_len=%d (0: one window over all frames)", who, win_len);
+    xsq_plan* P = d->plan;
+    const int S = xsq_plan_num_slices(P, n);
+    XSQ_REQUIRE(S >= 2, "%s: %lld samples give %d slices", who, (long long)n, S);
+    XSQ_REQUIRE((int64_t)B * S <= default_max_item_slices(P), "%s: B=%d items of %d slices exceed one launch (%d item-slices): fewer items or "
+                "shorter pieces", who, B, S, default_max_item_slices(P));
+    int64_t rows = 0;
+    for (int32_t f : d->F) rows += (int64_t)B * f;
+    XSQ_REQUIRE(rows <= 65535, "%s: %lld (item, bin) rows exceed one launch", who, (long long)rows);
+    L->S = S;
+    L->Y_bytes = (size_t)8 * B * S * P->sumFT * 8;
+    L->tf_bytes = std::max(xsq_slicqt_forward_workspace(P, 8 * B, n), xsq_slicqt_inverse_workspace(P, 8 * B, S));
+    L->wien_bytes = strategy == XSQ_IDEAL_WIENER ? xsq_wiener_sources_workspace(P->nblocks, d->F.data(), d->T.data(), B, S, win_len) : 0;
+    if (!L->tf_bytes || (strategy == XSQ_IDEAL_WIENER && !L->wien_bytes)) {
+        const std::string why = xsq_last_error();
+        set_error("%s: B=%d, %lld samples: a stage's workspace query failed (%s)", who, B, (long long)n, why.c_str());
+        return XSQ_ERR_ARG;
+    }
+    size_t o = 0;
+    L->Y = o;    o += al256(L->Y_bytes);
+    L->tf = o;   o += al256(L->tf_bytes);
+    L->wien = o; o += al256(L->wien_bytes);
+    L->total = o + 256;
+    return XSQ_OK;
+}
+
+}  // namespace
+
+size_t xsq_ideal_workspace(xsq_demixer* d, int B, int64_t n, int strategy, int win_len) {
+    IdealLayout L;
+    return ideal_layout("xsq_ideal_workspace", d, B, n, strategy, win_len, &L) ? 0 : L.total;
+}
+
+int xsq_ideal_separate(xsq_demixer* d, const float* sources, int B, int64_t n, int strategy, int win_len, float* estimates, void* ws,
+                       size_t ws_bytes, void* stream) {
+    XSQ_REQUIRE(d && sources && estimates && ws, "xsq_ideal_separate: null argument");
+    IdealLayout L;
+    if (int rc = ideal_layout("xsq_ideal_separate", d, B, n, strategy, win_len, &L)) return rc;
+    if (L.total > ws_bytes) {
+        set_error("xsq_ideal_separate: workspace too small (%zu needed, %zu given)", L.total, ws_bytes);
+        return XSQ_ERR_WORKSPACE;
+    }
+    xsq_plan* P = d->plan;
+    char* w = (char*)ws;
+    float* Y = (float*)(w + L.Y);
+    if (int rc = xsq_slicqt_forward(P, sources, 8 * B, n, Y, w + L.tf, L.tf_bytes, stream)) return rc;
+    if (strategy == XSQ_IDEAL_WIENER) {
+        if (int rc = xsq_wiener_em_sources(P->nblocks, d->F.data(), d->T.data(), Y, Y, B, L.S, win_len, 1, w + L.wien, L.wien_bytes, stream))
+            return rc;
+    } else if (int rc = xsq_phasemix_sources(P->nblocks, d->F.data(), d->T.data(), Y, Y, B, L.S, stream)) {
+        return rc;
+    }
+    return xsq_slicqt_inverse(P, Y, 8 * B, L.S, n, estimates, w + L.tf, L.tf_bytes, stream);
+}
+
 int xsq_separator_remix(xsq_demixer* d, xsq_model* Mo, const float* audio, int nb, int64_t N, int64_t cs, int max_stack, int wiener,
                         int overlap_tail, float* out, void* ws, size_t ws_bytes, void* tail_ws, size_t tail_ws_bytes, void* stream_,
                         void* tail_stream_, const float* gains, int R) {

@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void k_wiener_start(const float2* __restrict__
 //              left alone; st[0..15] become R, st[20..23] the denominators: the arithmetic of k_wiener_finalize.
 // J sources (Slot<J>: the slot above is J = 4) and, from masks, the kind of start (start_channel: the residual and the softmask
 // are formed on the way in; J = 4 from the mixture phase is the line above).
-enum class YFrom { Estimates, Masks, Current };
+//   Sources    the oracle (slicqfinder.py): Y holds the coefficients of the four true sources; the mix, its maximum and the
+//              starts |s_j| m/|m| are formed on the way in (sources_channel).  64 B per point, X is not read.
+enum class YFrom { Estimates, Masks, Current, Sources };
 
 template <YFrom SRC, int J, Start ST>
 __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__ X, const float2* __restrict__ Y,
@@ -132,18 +134,28 @@ __global__ __launch_bounds__(256) void k_wiener_stats(const float2* __restrict__
     float acc[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) acc[i] = 0.f;
-    const float2* x0 = X + aidx(r, 2 * Bn, S, r.b * 2, 0);
-    const float2* x1 = X + aidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
+    const float2* x0 = SRC == YFrom::Sources ? nullptr : X + aidx(r, 2 * Bn, S, r.b * 2, 0);
+    const float2* x1 = SRC == YFrom::Sources ? nullptr : X + aidx(r, 2 * Bn, S, r.b * 2 + 1, 0);
     // target 0, channel 0 of this row: in the masks' arena (8B channels) or the estimates' (2JB); the same index at J = 4
     const int64_t base = aidx(r, SRC == YFrom::Masks ? 8 * Bn : 2 * J * Bn, S, r.b * 2, 0);
     const int64_t cstride = (int64_t)r.F * W.N, jstride = (int64_t)Bn * 2 * cstride;
     for (int64_t n = W.n0 + threadIdx.x; n < W.n1; n += 256) {
         float2 a, b;
-        if constexpr (MAX) {
+        if constexpr (MAX && SRC != YFrom::Sources) {
             a = x0[n], b = x1[n];
             acc[NV - 1] = fmaxf(acc[NV - 1], fmaxf(abs2(a), abs2(b)));
         }
-        if constexpr (SRC == YFrom::Masks && (J != 4 || ST != Start::MixPhase)) {
+        if constexpr (SRC == YFrom::Sources) {
+            static_assert(J == 4, "the oracle has the four targets");
+            float2 s0[4], s1[4], y0[4], y1[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { s0[j] = Y[base + j * jstride + n]; s1[j] = Y[base + j * jstride + cstride + n]; }
+            sources_channel(s0, a, y0);
+            sources_channel(s1, b, y1);
+            acc[NV - 1] = fmaxf(acc[NV - 1], fmaxf(abs2(a), abs2(b)));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) accumulate(acc, j, y0[j], y1[j]);
+        } else if constexpr (SRC == YFrom::Masks && (J != 4 || ST != Start::MixPhase)) {
             float m0[4], m1[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { m0[j] = Mk[base + j * jstride + n]; m1[j] = Mk[base + j * jstride + cstride + n]; }
@@ -295,6 +307,74 @@ __global__ __launch_bounds__(256) void k_wiener_apply_masked(const float2* __res
     for (int j = 0; j < J; ++j) {
         *reinterpret_cast<float4*>(y0p + j * jstride) = make_float4(o0[j][0].x, o0[j][0].y, o1[j][0].x, o1[j][0].y);
         *reinterpret_cast<float4*>(y0p + j * jstride + cstride) = make_float4(o0[j][1].x, o0[j][1].y, o1[j][1].x, o1[j][1].y);
+    }
+}
+
+// The same pass fed by the sources' coefficients (the oracle): Sc and Y are arenas of 8B complex channels, 64 B read and 64 B
+// written per point, and Y == Sc is allowed -- a thread reads its frames of all eight channels before it stores any, and no other
+// thread touches them (no __restrict__ on the two).  EM = false stops at the starts |s_j| m/|m| (xsq_phasemix_sources: no
+// statistics, no window).  A thread owns the frames n, n + 1: one 16-byte access per channel where the row allows it (S*T even;
+// with EM an even window too, so that both frames share a slot), else 8-byte accesses frame by frame -- the arithmetic of a
+// frame is the same either way.
+template <bool EM>
+__device__ inline void sources_point(const float* __restrict__ st, const float2 (&s)[4][2], float2 (&o)[4][2]) {
+    float2 s0[4], s1[4], y0[4], y1[4], m0, m1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s0[j] = s[j][0]; s1[j] = s[j][1]; }
+    sources_channel(s0, m0, y0);
+    sources_channel(s1, m1, y1);
+    float2 y[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { y[j][0] = y0[j]; y[j][1] = y1[j]; }
+    if constexpr (EM) {
+        wiener_point<4>(st, m0, m1, y, o);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { o[j][0] = y[j][0]; o[j][1] = y[j][1]; }
+    }
+}
+
+template <bool EM>
+__global__ __launch_bounds__(256) void k_wiener_apply_sources(const float2* Sc, float2* Y, const WRow* __restrict__ rows,
+                                                               const float* __restrict__ stats, int Bn, int S, int win_len) {
+    const WRow r = rows[blockIdx.y];
+    const int64_t N = (int64_t)S * r.T;
+    const int64_t n = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+    if (n >= N) return;
+    const int64_t cstride = (int64_t)r.F * N, jstride = (int64_t)Bn * 2 * cstride;
+    const int64_t i0 = aidx(r, 8 * Bn, S, r.b * 2, n);
+    const bool wide = N % 2 == 0 && (!EM || win_len % 2 == 0);          // the same for every thread of the row
+    float2 s[4][2], o[4][2];
+    if (wide) {
+        const float* st = EM ? stats + r.stat + (n / win_len) * Slot<4>::N : nullptr;
+        float4 in[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            in[j][0] = *reinterpret_cast<const float4*>(Sc + i0 + j * jstride);
+            in[j][1] = *reinterpret_cast<const float4*>(Sc + i0 + j * jstride + cstride);
+        }
+        float2 o1[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[j][0] = make_float2(in[j][0].x, in[j][0].y); s[j][1] = make_float2(in[j][1].x, in[j][1].y); }
+        sources_point<EM>(st, s, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[j][0] = make_float2(in[j][0].z, in[j][0].w); s[j][1] = make_float2(in[j][1].z, in[j][1].w); }
+        sources_point<EM>(st, s, o1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            *reinterpret_cast<float4*>(Y + i0 + j * jstride) = make_float4(o[j][0].x, o[j][0].y, o1[j][0].x, o1[j][0].y);
+            *reinterpret_cast<float4*>(Y + i0 + j * jstride + cstride) = make_float4(o[j][1].x, o[j][1].y, o1[j][1].x, o1[j][1].y);
+        }
+        return;
+    }
+    for (int64_t k = n; k < n + 2 && k < N; ++k) {
+        const float* st = EM ? stats + r.stat + (k / win_len) * Slot<4>::N : nullptr;
+        const int64_t i = i0 + (k - n);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[j][0] = Sc[i + j * jstride]; s[j][1] = Sc[i + j * jstride + cstride]; }
+        sources_point<EM>(st, s, o);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { Y[i + j * jstride] = o[j][0]; Y[i + j * jstride + cstride] = o[j][1]; }
     }
 }
 
@@ -580,6 +660,8 @@ struct EmCall {                     // the arguments of a forward entry point
     size_t ws_bytes;
     hipStream_t stream;
     int flags = 0;                  // XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL: J = 5 sources with the latter
+    const float* sources = nullptr; // the oracle: the coefficients of the four true sources (arena of 8B channels) in place of X and
+                                    // the starts; may be Y itself.  One iteration, no options.
 };
 
 static inline int sources_of(int flags) { return (flags & XSQ_WIENER_RESIDUAL) ? 5 : 4; }
@@ -629,7 +711,9 @@ static size_t iter_bytes(int nblocks, const int32_t* F, const int32_t* T, int Bn
 // niter / method and the larger workspace.  Defaults batch_group; *resident: the form the call takes (niter >= 2).
 static int check_em(const char* who, EmCall& c, bool masked, bool iter, int niter, int method, bool* resident) {
     if (int rc = check_table(who, c.nblocks, c.F, c.T, c.Bn, c.S)) return rc;
-    XSQ_REQUIRE(c.X && c.Y && c.ws && (c.masks || !masked), "%s: null argument", who);
+    XSQ_REQUIRE((c.X || c.sources) && c.Y && c.ws && (c.masks || !masked), "%s: null argument", who);
+    // from sources: xsq_wiener_em_sources is the only caller and has no iteration count, flags or shared maximum to pass
+    if (c.sources) XSQ_REQUIRE(((uintptr_t)c.sources | (uintptr_t)c.Y) % 16 == 0, "%s: the arenas must be 16-byte aligned", who);
     XSQ_REQUIRE((c.flags & ~(XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)) == 0, "%s: flags=%d (XSQ_WIENER_SOFTMASK | XSQ_WIENER_RESIDUAL)", who, c.flags);
     const int J = sources_of(c.flags);
     if (masked) XSQ_REQUIRE(c.win_len > 0 && c.win_len % 2 == 0, "%s: win_len=%d must be even (two frames per thread)", who, c.win_len);
@@ -661,7 +745,10 @@ static void launch_window_max(const WTable& t, const float* X, float* ext_max, i
 // in place on Y; with masks (iteration 1 of the masked form) Y is only written
 static void launch_apply(const WTable& t, const EmCall& c, const float* masks) {
     XSQ_PROF("wiener_apply", c.stream);
-    if (masks)
+    if (c.sources)
+        hipLaunchKernelGGL(k_wiener_apply_sources<true>, dim3((unsigned)(((t.max_frames + 1) / 2 + 255) / 256), t.nrows), dim3(256), 0, c.stream,
+                           (const float2*)c.sources, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
+    else if (masks)
         with_options<true>(c.flags, [&](auto j, auto st) {
             hipLaunchKernelGGL((k_wiener_apply_masked<decltype(j)::value, decltype(st)::value>), dim3((unsigned)((t.max_frames / 2 + 255) / 256), t.nrows),
                                dim3(256), 0, c.stream, (const float2*)c.X, masks, (float2*)c.Y, t.d_rows, (const float*)c.ws, c.Bn, c.S, c.win_len);
@@ -676,10 +763,15 @@ static void launch_apply(const WTable& t, const EmCall& c, const float* masks) {
 template <YFrom SRC>
 static void launch_stats(const WTable& t, const EmCall& c) {
     XSQ_PROF(SRC == YFrom::Current ? "wiener_stats_iter" : "wiener_stats", c.stream);
-    with_options<SRC == YFrom::Masks>(c.flags, [&](auto j, auto st) {
-        hipLaunchKernelGGL((k_wiener_stats<SRC, decltype(j)::value, decltype(st)::value>), dim3(t.nwork), dim3(256), 0, c.stream,
-                           (const float2*)c.X, (const float2*)c.Y, c.masks, t.d_rows, t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
-    });
+    if constexpr (SRC == YFrom::Sources) {
+        hipLaunchKernelGGL((k_wiener_stats<SRC, 4, Start::MixPhase>), dim3(t.nwork), dim3(256), 0, c.stream, nullptr, (const float2*)c.sources,
+                           nullptr, t.d_rows, t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
+    } else {
+        with_options<SRC == YFrom::Masks>(c.flags, [&](auto j, auto st) {
+            hipLaunchKernelGGL((k_wiener_stats<SRC, decltype(j)::value, decltype(st)::value>), dim3(t.nwork), dim3(256), 0, c.stream,
+                               (const float2*)c.X, (const float2*)c.Y, c.masks, t.d_rows, t.d_work, (float*)c.ws, c.Bn, c.S, c.win_len);
+        });
+    }
 }
 
 // the J starts of an option set into Y (2JB channels), from the masks or from magnitudes (a: real arena of 8B channels)
@@ -708,7 +800,8 @@ static int run_em(const EmCall& c, int niter) {
     WTable t;
     const int J = sources_of(c.flags);
     if (int rc = get_wtable(c.nblocks, c.F, c.T, c.Bn, c.S, c.win_len, c.batch_group, &t, slot_of(J))) return rc;
-    if (c.masks) launch_stats<YFrom::Masks>(t, c);
+    if (c.sources) launch_stats<YFrom::Sources>(t, c);
+    else if (c.masks) launch_stats<YFrom::Masks>(t, c);
     else launch_stats<YFrom::Estimates>(t, c);
     { XSQ_PROF("wiener_finalize", c.stream);
     hipLaunchKernelGGL((J == 5 ? k_wiener_finalize<5> : k_wiener_finalize<4>), dim3(t.nblockwin), dim3(256), 0, c.stream, t.d_rows, t.d_blockwin,
@@ -860,6 +953,40 @@ int xsq_wiener_em_masked_ext(int nblocks, const int32_t* F, const int32_t* T, co
                              void* stream_) {
     return em("xsq_wiener_em_masked", {nblocks, F, T, X, masks, Y, Bn, S, win_len, batch_group, ext_max, ws, ws_bytes, (hipStream_t)stream_},
               true, false, 1, 1);
+}
+
+// ---- the oracle's filter: fed by the coefficients of the four true sources (slicqfinder.py:43-117) -----------------------
+// win_len == 0: one window over all the frames of a row, as the reference's blockwise_wiener takes it
+static int whole_row_window(int nblocks, const int32_t* T, int S, int win_len) {
+    if (win_len != 0 || nblocks <= 0 || !T || S <= 0) return win_len;
+    return (int)std::min<int64_t>(std::max<int64_t>(longest_window(nblocks, T, S, INT32_MAX), 1), INT32_MAX);
+}
+
+size_t xsq_wiener_sources_workspace(int nblocks, const int32_t* F, const int32_t* T, int Bn, int S, int win_len) {
+    return stats_bytes(nblocks, F, T, Bn, S, whole_row_window(nblocks, T, S, win_len), 4);
+}
+
+int xsq_wiener_em_sources(int nblocks, const int32_t* F, const int32_t* T, const float* Sc, float* Y, int Bn, int S, int win_len,
+                          int batch_group, void* ws, size_t ws_bytes, void* stream_) {
+    XSQ_REQUIRE(Sc, "xsq_wiener_em_sources: null argument");
+    EmCall c{nblocks, F, T, nullptr, nullptr, Y, Bn, S, whole_row_window(nblocks, T, S, win_len), batch_group, nullptr, ws, ws_bytes,
+             (hipStream_t)stream_};
+    c.sources = Sc;
+    return em("xsq_wiener_em_sources", c, false, false, 1, 1);
+}
+
+int xsq_phasemix_sources(int nblocks, const int32_t* F, const int32_t* T, const float* Sc, float* Y, int Bn, int S, void* stream_) {
+    int rc = check_table("xsq_phasemix_sources", nblocks, F, T, Bn, S);
+    if (rc) return rc;
+    XSQ_REQUIRE(Sc && Y, "xsq_phasemix_sources: null argument");
+    XSQ_REQUIRE(((uintptr_t)Sc | (uintptr_t)Y) % 16 == 0, "xsq_phasemix_sources: the arenas must be 16-byte aligned");
+    WTable t;
+    if ((rc = get_wtable(nblocks, F, T, Bn, S, 5000, Bn, &t))) return rc;
+    XSQ_PROF("phasemix_sources", (hipStream_t)stream_);
+    hipLaunchKernelGGL(k_wiener_apply_sources<false>, dim3((unsigned)(((t.max_frames + 1) / 2 + 255) / 256), t.nrows), dim3(256), 0,
+                       (hipStream_t)stream_, (const float2*)Sc, (float2*)Y, t.d_rows, nullptr, Bn, S, 0);
+    XSQ_HIP(hipGetLastError());
+    return XSQ_OK;
 }
 
 // ---- niter iterations (norbert/__init__.py:133-148, 247-260) -----------------------------------------------------------

@@ -266,4 +266,22 @@ __device__ inline void start_channel(float2 x, const float (&a)[4], float2 (&y)[
     }
 }
 
+// ---- the ideal-mask oracle: one channel of one point from the coefficients of the four true sources ------------------------
+// (xumx_slicq_v2/slicqfinder.py:43-117.)  The mix is their sum, formed as the reference forms it on the real and on the
+// imaginary part: model = eps, then model += s_j + eps per source (slicqfinder.py:57,71; eps = 1e-10, five of them in all).
+// The magnitudes are v_j = |s_j| and the starts v_j m/|m| are those of start_channel from magnitudes (angle(0) = 0).
+static constexpr float ORACLE_EPS = 1.0e-10f;
+
+__device__ inline void sources_channel(const float2 (&s)[4], float2& m, float2 (&y)[4]) {
+    m = make_float2(ORACLE_EPS, ORACLE_EPS);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m.x += s[j].x + ORACLE_EPS;
+        m.y += s[j].y + ORACLE_EPS;
+        v[j] = sqrtf(abs2(s[j]));
+    }
+    start_channel<4, Start::MixPhase, false>(m, v, y);
+}
+
 }  // namespace xsq

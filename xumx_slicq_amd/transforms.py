@@ -134,12 +134,21 @@ class SliCQEngine:
             self._ws[key] = ws
         return ws
 
+    def close(self):
+        """Frees the device side now -- demixers, plan handles, workspaces -- after the work queued on their devices has ended.
+        The engine stays usable: the next call builds new handles.  (A parameter search drops a plan per draw.)"""
+        for idx in set(self._handles) | {k[0] for k in self._ws}:
+            torch.cuda.synchronize(idx)
+        for d in self.__dict__.pop("_demixers", {}).values():
+            _lib.lib.xsq_demixer_destroy(d)
+        for h in self._handles.values():
+            _lib.lib.xsq_plan_destroy(h)
+        self._handles.clear()
+        self._ws.clear()
+
     def __del__(self):
         try:
-            for d in self.__dict__.get("_demixers", {}).values():
-                _lib.lib.xsq_demixer_destroy(d)
-            for h in self._handles.values():
-                _lib.lib.xsq_plan_destroy(h)
+            self.close()
         except Exception:
             pass
 
