@@ -787,6 +787,40 @@ int xsq_score_accumulate(const float* est, const float* tgt, const int* perm, in
 int xsq_score_finalise(const double* table, int B, int64_t frames, int silent_mode, double* out_frames, double* out_scores,
                        void* stream);
 
+/* ---- the sliCQT spectrogram (csrc/spectrogram.hip) ----------------------------------------------------------------------
+ * The device side of visualization.py:13-35 (overlap_add_slicq) and :55-81 (blockwise_spectrogram), plus the raster that is
+ * the only thing to leave the device.  Geometry as for the Wiener entry points: HOST arrays F[nblocks], T[nblocks] (T a multiple
+ * of 4; at most xsq_spectrogram_max_blocks() blocks, the geometry goes to the kernels by value), S slices, hop h_b = T_b / 2;
+ * no plan handle.  All pointers but F / T / N are DEVICE pointers; every launch goes to `stream`; no floating-point atomics:
+ * the same input gives the same bits on every run.
+ * xsq_spectrogram_overlap_add: complex arena for BC packed channels -> complex rows, block b (BC, F_b, Lout_b, 2) contiguous,
+ *   blocks back to back (xsq_spectrogram_overlap_add_size floats in all, 0 on bad arguments).  flatten = 0:
+ *   Lout_b = (S + 1) h_b and out[p] = 0 + x[j - 1, h_b + r] + x[j, r] for p = j h_b + r, the terms whose slice exists -- one
+ *   correctly rounded fp32 add per component, the bits of the reference's loop.  flatten = 1: Lout_b = S T_b, the slices side
+ *   by side.  arena and out 16-byte aligned.
+ * xsq_spectrogram_db: arena for B items of two channels -> db, block b (B, F_b, N_b) fp32 contiguous, blocks back to back, in
+ *   one pass: column p is overlap-add position p + h_b (h_b columns dropped at each end; flatten: position p + h_b of the
+ *   slices side by side), value = mean over the two channels of 20 log10 |.| (log first, mix-down second; |.| by hypotf;
+ *   |.| == 0 gives -inf and the mean of anything with -inf is -inf).  N: HOST array, 1 <= N_b <= (S - 1) h_b (flatten:
+ *   S T_b - T_b), the caller's truncation min(int(T_b / L * n), ...).  S >= 2.
+ * xsq_spectrogram_order_stats: for every batch item the k_lo-th and k_hi-th smallest (0-based, k_lo <= k_hi <= k_lo + 1) of
+ *   ITS values in all blocks of db (sum F_b N_b < 2^32 of them; -inf counts as a value) -> out (B, 2) fp32.  Exact: a radix
+ *   select over the order-preserving integer image of the floats, integer atomics only.  The quantile's lerp is the caller's.
+ *   (T is not needed; one block of one row selects from a plain array.)  workspace: xsq_spectrogram_order_workspace(B) bytes.
+ * xsq_spectrogram_raster: db -> image (B, sum F_b, W) fp32, row = band; row f of block b, column w = max of that row's
+ *   columns [lo, hi), lo = w N_b / W, hi = max(lo + 1, (w + 1) N_b / W) in 64-bit integers. */
+int xsq_spectrogram_max_blocks(void);
+int64_t xsq_spectrogram_overlap_add_size(int nblocks, const int32_t* F, const int32_t* T, int BC, int S, int flatten);
+int xsq_spectrogram_overlap_add(int nblocks, const int32_t* F, const int32_t* T, const float* arena, int BC, int S, int flatten,
+                                float* out, void* stream);
+int xsq_spectrogram_db(int nblocks, const int32_t* F, const int32_t* T, const int32_t* N, const float* arena, int B, int S,
+                       int flatten, float* db, void* stream);
+size_t xsq_spectrogram_order_workspace(int B);
+int xsq_spectrogram_order_stats(int nblocks, const int32_t* F, const int32_t* N, const float* db, int B, int64_t k_lo, int64_t k_hi,
+                                float* out, void* workspace, size_t workspace_bytes, void* stream);
+int xsq_spectrogram_raster(int nblocks, const int32_t* F, const int32_t* N, const float* db, int B, int W, float* image,
+                           void* stream);
+
 /* ---- per-kernel timing (bench.py roofline) ------------------------------------------
  * When enabled, every kernel launch of the library is bracketed by hipEvents recorded on
  * its own launch stream.  xsq_profile_read synchronises the outstanding events and

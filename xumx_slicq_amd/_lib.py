@@ -173,6 +173,13 @@ _SIGS = {
     "xsq_phasemix_sources": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "xsq_ideal_workspace": (C.c_size_t, [_vp, C.c_int, C.c_int64, C.c_int, C.c_int]),
     "xsq_ideal_separate": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_spectrogram_max_blocks": (C.c_int, []),
+    "xsq_spectrogram_overlap_add_size": (C.c_int64, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    "xsq_spectrogram_overlap_add": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "xsq_spectrogram_db": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "xsq_spectrogram_order_workspace": (C.c_size_t, [C.c_int]),
+    "xsq_spectrogram_order_stats": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "xsq_spectrogram_raster": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 for _name, (_res, _args) in _SIGS.items():
