@@ -65,14 +65,25 @@ const char* xsq_build_info(void);
 int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg,
                     const int32_t* c, const float* g, const double* gd, const float* tw);
 
-/* What the inverse transforms of this library leave out of the reference's (nsgt/nsigtf.py:57-99): the second synthesis of a
- * band that reaches across DC (0 < c_j < Lg_j/2) through its negative-frequency mirror.  share[nbands] = the weight of that
+/* What the inverse transforms of this library leave out of the reference's on a plan of xsq_plan_create
+ * (nsgt/nsigtf.py:57-99): the second synthesis of a band that reaches across DC (0 < c_j < Lg_j/2) through its negative-frequency mirror.  share[nbands] = the weight of that
  * term relative to the band's kept synthesis (0 for a band that does not cross DC), *worst (may be null) the band of the
  * largest.  Host arithmetic, no device.  xsq_plan_create returns XSQ_ERR_ARG, naming the band, for a plan with a share of
  * XSQ_TWIN_SHARE_MAX or more: Bark-262 has no such band, Mel-32 one of 0.0084; `bark, 96, 32.9` (0.109) is refused.   */
 #define XSQ_TWIN_SHARE_MAX 0.03
 int xsq_slicqt_dropped_twin_share(int L, int nbands, const int32_t* Lg, const int32_t* c, const double* gd, double* share,
                                   int* worst);
+/* xsq_plan_create with that term computed instead (opt-in; build_plan(dc_twins=True)): never refuses for a band across DC.
+ * The table of the term -- band j with 0 < c_j < Lg_j/2 lands on bin q - c_j, c_j <= q < Lg_j/2, with the weight
+ * (-1)^(c_j/2) (-1)^q Lg_j gd_j[Lg_j - q] -- is derived here from Lg, c and gd and uploaded.  Every inverse without a carry
+ * (xsq_slicqt_inverse{,_rows,_masked,_remix}, and through them xsq_separator_forward and xsq_ideal_separate) then adds it to the
+ * slice spectra (k_twin_synthesis), and xsq_slicqt_inverse_adjoint its transpose (k_twin_analysis).  Such a plan always takes
+ * the rocFFT path, and xsq_slicqt_inverse_masked_carry (streaming) refuses it.  A plan without such a band behaves exactly
+ * like xsq_plan_create's.  xsq_plan_num_twins: the number of landing entries (8 for `bark, 28, 32.9`), 0 for any plan of
+ * xsq_plan_create.                                                                                                  */
+int xsq_plan_create_twins(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg,
+                          const int32_t* c, const float* g, const double* gd, const float* tw);
+int xsq_plan_num_twins(const xsq_plan* plan);
 int xsq_plan_destroy(xsq_plan* plan);
 int xsq_plan_num_blocks(const xsq_plan* plan);
 /* slice-FFT backend: 0 (default) = the hand-written LDS-resident transform when L == 18060

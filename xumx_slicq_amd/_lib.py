@@ -44,6 +44,8 @@ _SIGS = {
     "xsq_last_error": (C.c_char_p, []),
     "xsq_build_info": (C.c_char_p, []),
     "xsq_plan_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "xsq_plan_create_twins": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "xsq_plan_num_twins": (C.c_int, [_vp]),
     "xsq_plan_destroy": (C.c_int, [_vp]),
     "xsq_plan_num_blocks": (C.c_int, [_vp]),
     "xsq_plan_set_fft_backend": (C.c_int, [_vp, C.c_int]),

@@ -136,6 +136,12 @@ struct xsq_plan {
     int nfold_dst = 0;
     void *d_fold_inl_dst = nullptr, *d_fold_inl_src = nullptr;    // the hand-written slice FFT's: inside k_slice_irfft (FoldSched)
     int nfold_inl = 0;
+    // The mirrored synthesis of the bands that reach across DC (dc_twins.h): made by xsq_plan_create_twins alone, so a plan of
+    // xsq_plan_create has ntwins == 0 and launches nothing for it.  Such a plan always takes the rocFFT path (lds_fft).
+    void *d_twin_bins = nullptr, *d_twin_src = nullptr;     // synthesis: TwinDst per landing bin / TwinSrc per entry
+    void *d_twin_bands = nullptr, *d_twin_asrc = nullptr;   // its transpose: TwinDst per band / TwinSrc per entry
+    float2* d_twin_tw = nullptr;                            // e^{2 pi i r / Lg}, r = 0 .. Lg - 1, per distinct Lg of those bands
+    int ntwin_bins = 0, ntwin_bands = 0, ntwins = 0;        // ntwins: landing entries (xsq_plan_num_twins)
     // caches keyed by the call shape
     std::mutex mu;
     std::map<std::pair<int, int>, xsq::FftPlan> fft;              // (direction, batch)

@@ -9,6 +9,7 @@
 // Inverse  (closed form I2; reference nsgt/nsigtf.py, nsgt/unslicing.py)
 //   Z[bc,j,s,:]   = coef[bc,j,s,:] x Wi_j,  Wi_j = DFT_Lg * diag(gd_j * Lg_j * (-1)^(c_j/2) / L)
 //   fr[bc,s,k]    = sum over bands covering bin k of Z[bc,j,s,k-bin0_j]   k_spectrum_gather (HBM stream)
+//   fr[bc,s,q-c_j] += the mirrored synthesis of a band across DC           k_twin_synthesis (dc_twins.h; plans of xsq_plan_create_twins only)
 //   seg[bc,s,:]   = L * irfft_L(fr[bc,s,:])  (unnormalised c2r; the 1/L sits in Wi)   rocFFT
 //   y[bc,i]       = seg[bc,s0,i-(2s0-2)h] + seg[bc,s0+1,i-2h*s0],  s0 = i/(2h)        k_overlap_add
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include "slice_fft.h"
 #include "band_dft4.h"
 #include "band_dft4s.h"
+#include "dc_twins.h"
 
 namespace xsq {
 
@@ -596,7 +598,8 @@ static int run_fft(const FftPlan& f, void* in, void* out, void* work, hipStream_
     return XSQ_OK;
 }
 
-static inline bool lds_fft(const xsq_plan* P) { return P->fft_backend == 0 && P->L == FFT_L && P->d_tgt != nullptr; }
+// (a plan with the mirrored synthesis adds it to the slice spectra in memory, dc_twins.h: rocFFT whatever L is)
+static inline bool lds_fft(const xsq_plan* P) { return P->fft_backend == 0 && P->L == FFT_L && P->d_tgt != nullptr && P->ntwins == 0; }
 static inline FftTables fft_tables(const xsq_plan* P) {
     return FftTables{P->d_T, P->d_T + FFT_R1 * FFT_M1, P->d_T + FFT_R1 * FFT_M1 + FFT_R2 * FFT_R3};
 }
@@ -917,8 +920,49 @@ static bool build_short_schedule(xsq_plan* P, const PlanArgs& A, const std::vect
     return true;
 }
 
+// Tables of the mirrored synthesis (dc_twins.h) from Lg, c and gd alone: band j = 1 .. nbands - 2 with 0 < c_j < Lg_j / 2 lands
+// on bin q - c_j for c_j <= q < Lg_j / 2 with the weight (-1)^(c_j/2) (-1)^q Lg_j gd_j[Lg_j - q] / L (the inverse slice FFT is
+// unnormalised: the 1/L sits in the weights, as in Wi).  Synthesis entries by bin, then band; the transpose's by band, then q,
+// with the irfft weight of the bin folded in.
+static int build_twin_tables(xsq_plan* P, const PlanArgs& A) {
+    std::map<int, std::vector<TwinSrc>> by_bin;
+    std::vector<TwinDst> bands;
+    std::vector<TwinSrc> asrc;
+    std::map<int, int> tw_off;
+    std::vector<float2> tw;
+    for (int j = 1; j < A.nbands - 1; ++j) {
+        const int n = A.Lg[j], cj = A.c[j];
+        if (!(cj > 0 && cj < n / 2)) continue;
+        if (!tw_off.count(n)) {
+            tw_off[n] = (int)tw.size();
+            for (int r = 0; r < n; ++r) tw.push_back(make_float2((float)std::cos(PI2 * r / n), (float)std::sin(PI2 * r / n)));
+        }
+        bands.push_back(TwinDst{j, (int)asrc.size(), n / 2 - cj, tw_off[n]});
+        for (int q = cj; q < n / 2; ++q) {
+            const int k = q - cj;
+            const double w = A.sign(j) * (q % 2 ? -1.0 : 1.0) * n * A.gd[A.g_off[j] + n - q] / A.L;
+            by_bin[k].push_back(TwinSrc{j, q + 1, tw_off[n], (float)w});
+            asrc.push_back(TwinSrc{k, q + 1, tw_off[n], (float)((k == 0 || k == A.L / 2) ? w : 2.0 * w)});
+        }
+    }
+    std::vector<TwinDst> bins;
+    std::vector<TwinSrc> src;
+    for (auto& kv : by_bin) {
+        bins.push_back(TwinDst{kv.first, (int)src.size(), (int)kv.second.size(), 0});
+        src.insert(src.end(), kv.second.begin(), kv.second.end());
+    }
+    int rc;
+    if ((rc = upload(P->d_twin_bins, bins))) return rc;
+    if ((rc = upload(P->d_twin_src, src))) return rc;
+    if ((rc = upload(P->d_twin_bands, bands))) return rc;
+    if ((rc = upload(P->d_twin_asrc, asrc))) return rc;
+    if ((rc = upload(P->d_twin_tw, tw))) return rc;
+    P->ntwin_bins = (int)bins.size(); P->ntwin_bands = (int)bands.size(); P->ntwins = (int)src.size();
+    return XSQ_OK;
+}
+
 static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
-                      const float* g, const double* gd, const float* tw) {
+                      const float* g, const double* gd, const float* tw, bool twins) {
     PlanArgs A{L, tr, nbands, Lg, c, g, gd, tw, std::vector<int64_t>(nbands, 0)};
     for (int j = 1; j < nbands; ++j) A.g_off[j] = A.g_off[j - 1] + Lg[j - 1];
     int rc;
@@ -984,6 +1028,31 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
         P->short_n1 = (int)H.item1.size(); P->short_n2 = (int)H.codes.size();
         P->short_nent = H.nent; P->short_sc0 = SHORT_SCRATCH0;
     }
+    if (twins && (rc = build_twin_tables(P, A))) return rc;
+    return XSQ_OK;
+}
+
+// xsq_plan_create (twins false: a plan whose dropped mirrored synthesis is not negligible is refused) and xsq_plan_create_twins
+static int plan_create(const char* who, bool twins, xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
+                       const float* g, const double* gd, const float* tw) {
+    XSQ_REQUIRE(out && Lg && c && g && gd && tw, "%s: null argument", who);
+    XSQ_REQUIRE(L > 0 && L % 4 == 0 && tr % 2 == 0 && nbands >= 2, "%s: bad L/tr/nbands", who);
+    if (!twins) {   // no silently different audio
+        std::vector<double> share(nbands);
+        int worst = 0;
+        if (int rc = xsq_slicqt_dropped_twin_share(L, nbands, Lg, c, gd, share.data(), &worst)) return rc;
+        XSQ_REQUIRE(share[worst] < XSQ_TWIN_SHARE_MAX,
+                    "xsq_plan_create: band %d (centre bin %d, Lg %d) reaches across DC and the reference's mirrored synthesis of it, "
+                    "which this library does not compute, is %.3g of the band's own (limit %.3g): plan refused",
+                    worst, (int)c[worst], (int)Lg[worst], share[worst], (double)XSQ_TWIN_SHARE_MAX);
+    }
+    xsq_plan* P = new xsq_plan();
+    const int rc = plan_build(P, L, tr, nbands, Lg, c, g, gd, tw, twins);
+    if (rc != XSQ_OK) {          // frees whatever was allocated before the failure
+        xsq_plan_destroy(P);
+        return rc;
+    }
+    *out = P;
     return XSQ_OK;
 }
 
@@ -1006,26 +1075,15 @@ const char* xsq_last_error(void) { return g_err; }
 
 int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
                     const float* g, const double* gd, const float* tw) {
-    XSQ_REQUIRE(out && Lg && c && g && gd && tw, "xsq_plan_create: null argument");
-    XSQ_REQUIRE(L > 0 && L % 4 == 0 && tr % 2 == 0 && nbands >= 2, "xsq_plan_create: bad L/tr/nbands");
-    {   // no silently different audio: a plan whose dropped mirrored synthesis is not negligible is refused
-        std::vector<double> share(nbands);
-        int worst = 0;
-        if (int rc = xsq_slicqt_dropped_twin_share(L, nbands, Lg, c, gd, share.data(), &worst)) return rc;
-        XSQ_REQUIRE(share[worst] < XSQ_TWIN_SHARE_MAX,
-                    "xsq_plan_create: band %d (centre bin %d, Lg %d) reaches across DC and the reference's mirrored synthesis of it, "
-                    "which this library does not compute, is %.3g of the band's own (limit %.3g): plan refused",
-                    worst, (int)c[worst], (int)Lg[worst], share[worst], (double)XSQ_TWIN_SHARE_MAX);
-    }
-    xsq_plan* P = new xsq_plan();
-    const int rc = plan_build(P, L, tr, nbands, Lg, c, g, gd, tw);
-    if (rc != XSQ_OK) {          // frees whatever was allocated before the failure
-        xsq_plan_destroy(P);
-        return rc;
-    }
-    *out = P;
-    return XSQ_OK;
+    return plan_create("xsq_plan_create", false, out, L, tr, nbands, Lg, c, g, gd, tw);
 }
+
+int xsq_plan_create_twins(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
+                          const float* g, const double* gd, const float* tw) {
+    return plan_create("xsq_plan_create_twins", true, out, L, tr, nbands, Lg, c, g, gd, tw);
+}
+
+int xsq_plan_num_twins(const xsq_plan* P) { return P ? P->ntwins : XSQ_ERR_ARG; }
 
 int xsq_plan_destroy(xsq_plan* P) {
     if (!P) return XSQ_OK;
@@ -1040,6 +1098,7 @@ int xsq_plan_destroy(xsq_plan* P) {
     (void)hipFree(P->d_adj_tw); (void)hipFree(P->d_adj_Wf); (void)hipFree(P->d_adj_pool4f);
     (void)hipFree(P->d_fadj_Wi); (void)hipFree(P->d_fadj_pool4i); (void)hipFree(P->d_fold_dst); (void)hipFree(P->d_fold_src);
     (void)hipFree(P->d_fold_inl_dst); (void)hipFree(P->d_fold_inl_src);
+    (void)hipFree(P->d_twin_bins); (void)hipFree(P->d_twin_src); (void)hipFree(P->d_twin_bands); (void)hipFree(P->d_twin_asrc); (void)hipFree(P->d_twin_tw);
     (void)hipFree(P->d_s_item1); (void)hipFree(P->d_s_tw1); (void)hipFree(P->d_s_item2); (void)hipFree(P->d_s_tgt); (void)hipFree(P->d_s_wd);
     delete P;
     return XSQ_OK;
@@ -1261,7 +1320,8 @@ int xsq_slicqt_adjoint_window(int L, int nbands, const int32_t* Lg, const int32_
     return XSQ_OK;
 }
 
-// ---- the part of the reference's inverse that this library does not compute ----
+// ---- the part of the reference's inverse that this library does not compute on a plan of xsq_plan_create ----
+// (xsq_plan_create_twins computes it: build_twin_tables, dc_twins.h)
 // The reference synthesises every band 1 .. nbands-2 a second time through the dual window of its negative-frequency
 // mirror (centre L - c_j), from conj(cat(t[1:], flip(t[1:]))) of the band's spectrum t, and keeps bins 0..L/2 of the sum
 // (nsgt/nsigtf.py:57-99).  For a band that reaches across DC (0 < c_j < Lg_j/2) that second synthesis lands on the kept
@@ -1366,8 +1426,15 @@ int xsq_slicqt_inverse_adjoint(xsq_plan* P, const float* gy, int BC, int S, int6
     if (int rc = forward_impl(P, gy, nullptr, nullptr, BC, length, S, 0, 0, dst, nullptr, nullptr, nullptr, 0, w, ws_bytes - (size_t)(w - (char*)ws),
                               stream_, RingNew{nullptr, 0, 0}, &adj))
         return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P->ntwins) {   // the transpose of the mirrored synthesis (dc_twins.h), from the slice spectra forward_impl left in its workspace (seg | U)
+        const float2* V = (const float2*)(w + al256((size_t)BC * S * P->L * 4));
+        XSQ_PROF("twin_analysis", stream);
+        hipLaunchKernelGGL(k_twin_analysis, dim3(BC * S), dim3(64), 0, stream, V, P->d_bands, (const TwinDst*)P->d_twin_bands,
+                           (const TwinSrc*)P->d_twin_asrc, P->d_twin_tw, P->ntwin_bands, dst, BC, S, P->nbins);
+        XSQ_HIP(hipGetLastError());
+    }
     if (accumulate) {
-        hipStream_t stream = (hipStream_t)stream_;
         const int64_t quads = (int64_t)(arena_bytes / 16);
         XSQ_PROF("adjoint_accumulate", stream);
         hipLaunchKernelGGL(k_arena_add, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, gcoef, dst, quads);
@@ -1495,6 +1562,10 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
         { XSQ_PROF(adj ? "fwd_adjoint_spectrum_gather" : "spectrum_gather", stream);
         hipLaunchKernelGGL(k_spectrum_gather, dim3((P->nbins + 255) / 256, rows), dim3(256), 0, stream, Z,
                            P->d_bands, P->d_cov_ptr, P->d_cov_band, fr, BC, S, P->nbins); }
+        // the mirrored synthesis of the bands across DC (dc_twins.h); not in the adjoint of the analysis, which has no such term
+        if (P->ntwins && !adj) { XSQ_PROF("twin_synthesis", stream);
+        hipLaunchKernelGGL(k_twin_synthesis, dim3(rows), dim3(64), 0, stream, coef, mask, BCx, P->d_bands, (const TwinDst*)P->d_twin_bins,
+                           (const TwinSrc*)P->d_twin_src, P->d_twin_tw, P->ntwin_bins, fr, BC, S, P->nbins); }
         { XSQ_PROF(adj ? "fwd_adjoint_irfft_L" : "irfft_L", stream); rc = run_fft(f, fr, seg, fwork, stream); }
         if (rc) return rc;
     }
@@ -1643,6 +1714,8 @@ int xsq_slicqt_inverse_masked_carry(xsq_plan* P, const float* masks, const float
                                     int shift, int64_t length, float* y, int64_t y_stride, const float* carry_in, float* carry_out,
                                     void* ws, size_t ws_bytes, void* stream_) {
     XSQ_REQUIRE(P && masks && mix && y && carry_out && ws, "xsq_slicqt_inverse_masked_carry: null argument");
+    // the mirrored synthesis turns with the parity of the slice's index in the whole stream, which a step does not know
+    XSQ_REQUIRE(!P->ntwins, "xsq_slicqt_inverse_masked_carry: a plan with bands across DC (dc_twins, xsq_plan_create_twins) cannot stream");
     XSQ_REQUIRE(BCx > 0 && BC > 0 && BC % BCx == 0, "xsq_slicqt_inverse_masked_carry: %d mix channels do not divide %d mask channels", BCx, BC);
     XSQ_REQUIRE(S >= 1 && first >= 0 && first + S <= S_window, "xsq_slicqt_inverse_masked_carry: slices [%d, %d) of a window of %d", first,
                 first + S, S_window);

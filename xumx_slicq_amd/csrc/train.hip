@@ -1174,6 +1174,7 @@ int xsq_train_step_sdr(xsq_train* Tr, xsq_plan* P, const float* X, const float* 
                 "xsq_train_step_sdr: mcoef = %g (the term is on for mcoef > 0; use xsq_train_step without it)", (double)mcoef);
     XSQ_REQUIRE(xsq_plan_num_blocks(P) == Tr->nblocks && xsq_plan_coefs_per_slice(P) == Tr->model->sumFT,
                 "xsq_train_step_sdr: the plan's block table is not the trainer's");
+    XSQ_REQUIRE(xsq_plan_num_twins(P) == 0, "xsq_train_step_sdr: training on a plan with bands across DC (dc_twins, xsq_plan_create_twins) is not supported");
     const SdrStep sdr{P, y_targets, n, mcoef};
     return train_step_impl("xsq_train_step_sdr", Tr, X, Yt, Bn, S, wiener, lr, wd, apply_update, loss_out, ws, ws_bytes, stream_,
                            &sdr);

@@ -10,7 +10,7 @@ checked against reference-generated integers in tests/golden/plan.npz.
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Tuple
 
 import numpy as np
@@ -99,6 +99,8 @@ class SliCQPlan:
     gd: np.ndarray             # (sum Lg,) fp64 dual windows
     tw: np.ndarray             # (L,) fp32 slice window
     blocks: List[Tuple[int, int, int]]   # (first_band, F_b, T_b)
+    dc_twins: bool = False     # build_plan(dc_twins=True): the device plan computes the mirrored synthesis (xsq_plan_create_twins)
+    twins: list = field(default_factory=list)   # [(band, q, landing bins, fp64 dual window of the mirrored band at q)] as oracle.slicqt.Plan.twins
 
     @property
     def nbands(self) -> int:
@@ -151,7 +153,11 @@ class SliCQPlan:
 
 
 def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: float = 22050.0,
-               fs: float = 44100.0, min_win: int = 16) -> SliCQPlan:
+               fs: float = 44100.0, min_win: int = 16, dc_twins: bool = False) -> SliCQPlan:
+    """``dc_twins`` False: a plan in which a band reaches across DC (0 < c_j < Lg_j / 2) with a mirrored synthesis of
+    TWIN_SHARE_MAX or more of the band's own is refused, and a smaller one is dropped by contract.  True: never refused for
+    that; the plan carries ``twins`` and the device computes the term.  A plan without such a band
+    is the default plan field for field, with ``twins == []``."""
     if scale not in _SCALES:
         raise ValueError(f"scale '{scale}' is not on the accelerated path (have: {sorted(_SCALES)})")
     f, q = _SCALES[scale](fmin, fmax, fbins)
@@ -235,12 +241,22 @@ def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: 
     gd_used = torch.cat(gd[:used]).numpy().astype(np.float64)
     share = dropped_twin_share(L, Lg, c, gd_used)
     worst = int(np.argmax(share))
-    if share[worst] >= TWIN_SHARE_MAX:             # xsq_plan_create refuses the same plans
+    if not dc_twins and share[worst] >= TWIN_SHARE_MAX:             # xsq_plan_create refuses the same plans
         raise ValueError(f"plan ({scale}, {fbins}, {fmin}): band {worst} (centre bin {int(c[worst])}, Lg {int(Lg[worst])}) reaches across DC "
                          f"and the reference's mirrored synthesis of it, which the kernels do not compute, is {share[worst]:.3g} of the "
                          f"band's own (limit {TWIN_SHARE_MAX}): the stems would differ from the reference's")
+    # nsgt/nsigtf.py:61-80: band j is also synthesised through the window of its mirror, band len(g) - j, centred on bin L - c_j;
+    # for q >= c_j of the window's first half that lands on the kept bin q - c_j
+    twins = []
+    if dc_twins:
+        for j in range(1, used - 1):
+            n, cj = int(Lg[j]), int(c[j])
+            if 0 < cj < n // 2:
+                assert M[len(g) - j] == n and centre[len(g) - j] == L - cj
+                q = np.arange(cj, n // 2)
+                twins.append((j, q, q - cj, gd[len(g) - j].numpy()[q].copy()))
     return SliCQPlan(
         scale=scale, fbins=fbins, fmin=fmin, fmax=fmax, fs=fs, L=L, tr=tr, Lg=Lg, c=c,
         g=torch.cat(g[:used]).numpy().astype(np.float32),
         gd=gd_used,
-        tw=tw.numpy(), blocks=blocks)
+        tw=tw.numpy(), blocks=blocks, dc_twins=bool(dc_twins), twins=twins)

@@ -457,6 +457,9 @@ class ShardedDemixer:
                  nb_samples: int = 1, stack: int = 4, solo: bool = False, exchange: str = "sendrecv", fallback: bool = False):
         if exchange not in ("sendrecv", "allgather"):
             raise ValueError(f"exchange must be 'sendrecv' or 'allgather'; got {exchange!r}")
+        if getattr(separator, "dc_twins", False):
+            from ._lib import XsqError
+            raise XsqError("sharding: a plan with bands across DC (dc_twins = True) is served by Separator.forward only")
         self.sep, self.get_chunk, self.dev, self.group, self.gather = separator, get_chunk, torch.device(device), group, gather
         self.exchange, self.fallback, self.exchange_note = exchange, bool(fallback), None
         live = dist.is_initialized() and not solo

@@ -103,10 +103,12 @@ def filter_sources_arena(table, Sc: Tensor, Y: Tensor, B: int, S: int, strategy:
 
 class TrackEvaluator:
     """slicqfinder.py:120-201 over a ``data.DeviceDataset``.  ``oracle(scale, fmin, bins)`` -> the SDRs of bass, drums,
-    vocals, other: per target the mean over ``tracks`` (indices or names; default all) of the whole-track ``sdr_global``."""
+    vocals, other: per target the mean over ``tracks`` (indices or names; default all) of the whole-track ``sdr_global``.
+    ``dc_twins``: score the plans with bands across DC too, decoded with the reference's mirrored synthesis
+    (``plan.build_plan``); by default such a draw is refused."""
 
     def __init__(self, dataset, max_sllen: int = 44100, piece: Optional[int] = None, tracks: Optional[Sequence] = None,
-                 strategy: str = "wiener", wiener_win_len: int = 5000):
+                 strategy: str = "wiener", wiener_win_len: int = 5000, dc_twins: bool = False):
         from .evaluation import _track_indices
         if strategy not in STRATEGIES:
             raise ValueError(f"strategy {strategy!r} not in {sorted(STRATEGIES)}")
@@ -116,6 +118,7 @@ class TrackEvaluator:
             raise ValueError(f"piece {piece}: at least one sample")
         self.tracks = _track_indices(dataset, tracks)
         self.strategy, self.wiener_win_len = strategy, int(wiener_win_len)
+        self.dc_twins = bool(dc_twins)
         self.refusals: List[Dict] = []                 # every draw that was not scored, with the reason
 
     def _refuse(self, scale, fmin, bins, reason) -> Tuple[float, float, float, float]:
@@ -127,7 +130,7 @@ class TrackEvaluator:
         from .transforms import NSGTBase
         bins = int(bins)
         try:
-            base = NSGTBase(scale, bins, float(fmin), device=self.dataset.device)
+            base = NSGTBase(scale, bins, float(fmin), device=self.dataset.device, dc_twins=self.dc_twins)
         except ValueError as e:                        # an unknown scale, a band across DC: plan.build_plan says which
             return self._refuse(scale, fmin, bins, f"plan refused: {e}")
         if base.sllen > self.max_sllen:                # slicqfinder.py:137: "skip too big transforms"
@@ -173,14 +176,15 @@ def _reason(refusals: Optional[List], before: int) -> str:
 
 
 def optimize_many(f: Callable, params: Dict, n_iter: int, per_target: bool = False, seed: int = 42, out: Optional[str] = None,
-                  refusals: Optional[List] = None) -> Dict:
+                  refusals: Optional[List] = None, dc_twins: Optional[bool] = None) -> Dict:
     """slicqfinder.py:225-354: ``n_iter`` scored rounds; a draw whose oracle value is four ``-inf`` is rerolled (the next
     row of the table is taken in its place) and counted.  ``params``: {"scales", "bins": (lo, hi), "fmin": (lo, hi, step)}.
     The table holds ``8 * n_iter + 8`` draws; a search that exhausts it stops short and says so (``"exhausted"``).
     ``refusals``: the list ``f`` appends its reasons to (``TrackEvaluator.refusals`` for ``TrackEvaluator.oracle``); whatever it
     gained during a refused call becomes that draw's reason, and a draw refused without one says so (``NO_REASON``).
     Returns -- and, with ``out``, writes as JSON -- the best score and parameters (per target with ``per_target``), every
-    scored round, and under ``"refusals"`` every rerolled draw with its reason (``"rerolled"`` counts them)."""
+    scored round, and under ``"refusals"`` every rerolled draw with its reason (``"rerolled"`` counts them).  ``dc_twins`` (when
+    given): the evaluator's flag, recorded in the result under that name."""
     table = draw_params(seed, 8 * int(n_iter) + 8, params["scales"], params["bins"], params["fmin"])
     names = ORACLE_TARGETS if per_target else ("total",)
     best = {t: {"sdr": float("-inf"), "params": None} for t in names}
@@ -205,18 +209,23 @@ def optimize_many(f: Callable, params: Dict, n_iter: int, per_target: bool = Fal
     result = {"seed": int(seed), "n_iter": int(n_iter), "per_target": bool(per_target), "params": {k_: list(v) for k_, v in params.items()},
               "best": best, "rounds": rounds, "rerolled": len(rerolls), "refusals": rerolls,
               "exhausted": len(rounds) < n_iter}
+    if dc_twins is not None:
+        result["dc_twins"] = bool(dc_twins)
     _write(result, out)
     return result
 
 
-def evaluate_single(f: Callable, params: Dict, out: Optional[str] = None, refusals: Optional[List] = None) -> Dict:
-    """slicqfinder.py:204-222: one (scale, bins, fmin).  ``refusals``: as in ``optimize_many``; a refused parameter set is named
-    with its reason under ``"refusals"``."""
+def evaluate_single(f: Callable, params: Dict, out: Optional[str] = None, refusals: Optional[List] = None,
+                    dc_twins: Optional[bool] = None) -> Dict:
+    """slicqfinder.py:204-222: one (scale, bins, fmin).  ``refusals``, ``dc_twins``: as in ``optimize_many``; a refused parameter set
+    is named with its reason under ``"refusals"``."""
     before = len(refusals) if refusals is not None else 0
     scores = tuple(float(s) for s in f(scale=params["scale"], fmin=params["fmin"], bins=params["bins"]))
     print("  ".join(f"{t} {v:.2f} dB" for t, v in zip(ORACLE_TARGETS, scores)) + f"  mean {sum(scores) / 4:.2f} dB")
     result = {"params": dict(params), "sdr": dict(zip(ORACLE_TARGETS, scores)), "total": sum(scores) / 4,
               "refusals": [dict(params, reason=_reason(refusals, before))] if _is_reroll(scores) else []}
+    if dc_twins is not None:
+        result["dc_twins"] = bool(dc_twins)
     _write(result, out)
     return result
 
@@ -241,6 +250,7 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--max-sllen", type=int, default=44100, help="a plan with a longer slice is not scored and the round is drawn again")
     p.add_argument("--single", action="store_true", help="score the one parameter set --fscale / --fbins / --fmins name; no search")
     p.add_argument("--per-target", action="store_true", help="keep the best parameter set of each target, not of their mean")
+    p.add_argument("--dc-twins", action="store_true", help="score plans with bands across DC too (the reference's mirrored synthesis on the device); by default they are drawn again")
     p.add_argument("--root", type=str, required=True, help="<root>/<track>/{vocals,drums,bass,other}.wav, the MUSDB18-HQ layout")
     p.add_argument("--valid", type=str, default=None, metavar="NAME,...", help="the validation track directories (default: all, sorted)")
     p.add_argument("--storage", choices=("fp32", "pcm16"), default="fp32", help="how the stems are kept on the device (pcm16: 16-bit files only)")
@@ -285,11 +295,12 @@ def slicqfinder_main(argv=None) -> Dict:
     p = cli_parser()
     args = parse_args(p, argv)
     ds = DeviceDataset.from_directory(args.root, names=args.valid, storage=args.storage, device=args.device)
-    ev = TrackEvaluator(ds, args.max_sllen, piece=args.piece, strategy=args.oracle_strategy)
+    ev = TrackEvaluator(ds, args.max_sllen, piece=args.piece, strategy=args.oracle_strategy, dc_twins=args.dc_twins)
     if args.single:
-        return evaluate_single(ev.oracle, args.params, out=args.out, refusals=ev.refusals)
+        return evaluate_single(ev.oracle, args.params, out=args.out, refusals=ev.refusals, dc_twins=ev.dc_twins)
     print(f"searching scales {args.params['scales']}, bins {args.params['bins']}, fmin {args.params['fmin']}; sllen at most {args.max_sllen}")
-    return optimize_many(ev.oracle, args.params, args.n_iter, args.per_target, seed=args.random_seed, out=args.out, refusals=ev.refusals)
+    return optimize_many(ev.oracle, args.params, args.n_iter, args.per_target, seed=args.random_seed, out=args.out, refusals=ev.refusals,
+                         dc_twins=ev.dc_twins)
 
 
 if __name__ == "__main__":

@@ -93,6 +93,9 @@ class Trainer:
             raise _lib.XsqError(f"training differentiates ONE Wiener-EM iteration (the reference trains with iterations=1, and the "
                                 f"backward kernels are the gradient of one); this model has niter = {unmix.niter}: set it to 1 "
                                 "to train and back afterwards")
+        if getattr(getattr(getattr(self.nsgt, "nsgt", None), "plan", None), "dc_twins", False):
+            raise _lib.XsqError("training on a plan with bands across DC (dc_twins = True) is not supported: the training step has not "
+                                "been held to the reference on such a plan; build the plan without the flag (it is then refused by name)")
         self._spec = [(k, tuple(v.shape)) for k, v in unmix.state_dict().items() if not k.endswith("num_batches_tracked")]
         params = unmix.packed_parameters()
         self.nparams = int(params.size)

@@ -94,10 +94,12 @@ class SliCQEngine:
             p = self.plan
             out = C.c_void_p()
             with torch.cuda.device(idx):
-                _lib.check(_lib.lib.xsq_plan_create(
+                # a plan built with dc_twins=True: the library derives the table of the mirrored synthesis from Lg, c and gd
+                create = "xsq_plan_create_twins" if p.dc_twins else "xsq_plan_create"
+                _lib.check(getattr(_lib.lib, create)(
                     C.byref(out), p.L, p.tr, p.nbands,
                     p.Lg.ctypes.data, p.c.ctypes.data, p.g.ctypes.data, p.gd.ctypes.data, p.tw.ctypes.data),
-                    "xsq_plan_create")
+                    create)
             h = out
             _lib.check(_lib.lib.xsq_plan_set_fft_backend(h, self._fft_backend), "xsq_plan_set_fft_backend")
             _lib.check(_lib.lib.xsq_plan_set_band_radix4(h, int(getattr(self, "_band_radix4", True))),
@@ -277,14 +279,15 @@ class SliCQEngine:
 
 
 class NSGTBase(nn.Module):
-    """transforms.py:21-94.  Holds the plan; `.nsgt` is the device engine."""
+    """transforms.py:21-94.  Holds the plan; `.nsgt` is the device engine.  ``dc_twins=True`` accepts a plan with bands across
+    DC and computes the reference's mirrored synthesis of them (``plan.build_plan``); the default refuses such a plan."""
 
-    def __init__(self, scale, fbins, fmin, fmax=22050.0, fgamma=15.0, fs=44100.0, device="cuda"):
+    def __init__(self, scale, fbins, fmin, fmax=22050.0, fgamma=15.0, fs=44100.0, device="cuda", dc_twins=False):
         super().__init__()
         self.fbins = fbins
         self.fmin = fmin
         self.fmax = fmax
-        self.plan = build_plan(scale, fbins, fmin, fmax, fs)
+        self.plan = build_plan(scale, fbins, fmin, fmax, fs, dc_twins=dc_twins)
         self.sllen, self.trlen = self.plan.L, self.plan.tr
         print(f"scale={scale}, fbins={fbins}, fmin={fmin:.2f}, fmax={fmax:.2f}, "
               f"sllen={self.sllen}, trlen={self.trlen}")
