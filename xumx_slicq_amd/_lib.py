@@ -213,9 +213,63 @@ def check(rc: int, what: str):
         raise XsqError(f"{what} failed ({rc}): {last_error()}")
 
 
+def call(name: str, *args):
+    """The native entry point ``name`` on ``args``; ``XsqError`` naming it, with the library's message, unless it returns 0."""
+    check(getattr(lib, name)(*args), name)
+
+
+def workspace_bytes(name: str, *args, why=None) -> int:
+    """Bytes the size query ``name`` asks for.  A query refuses with 0: ``XsqError`` naming it.  ``why`` is the reason where the
+    query sets no error text of its own -- the library's buffer is per thread and never cleared, so it may hold the message of
+    an earlier call."""
+    nbytes = getattr(lib, name)(*args)
+    if nbytes == 0:
+        raise XsqError(f"{name}: {why or last_error()}")
+    return nbytes
+
+
 def stream_ptr() -> int:
     """The HIP stream torch is currently issuing work on."""
     return torch.cuda.current_stream().cuda_stream
+
+
+def device_index(device) -> int:
+    """The index of a ROCm ``torch.device``; one without an index is torch's current device."""
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+class Scratch(dict):
+    """Grow-only workspaces of one owner: {(device index, stream pointer, tag): uint8 tensor}.  Calls issued on different
+    streams may overlap, so every stream has its own buffer.  PyTorch owns the memory.
+
+    Captured graphs hold raw pointers into these buffers, so a buffer stays where it is while it is large enough and is
+    never replaced by a smaller one; whoever captures keeps ``tensors()`` alive with the graph.  A copy or pickle of a pool
+    is an empty pool: the copy allocates its own on first use."""
+
+    FLOOR = 256     # what a zero-byte request gets: the alignment unit of the library's workspace layouts
+
+    def get(self, device, nbytes: int, stream=None, tag=None):
+        """At least ``nbytes`` bytes on ``device`` for work on ``stream`` (a stream pointer; default: torch's current stream of
+        that device); ``tag`` tells apart the buffers one owner uses side by side on one stream."""
+        key = (device_index(device), torch.cuda.current_stream(device).cuda_stream if stream is None else stream, tag)
+        ws = dict.get(self, key)
+        if ws is None or ws.numel() < nbytes:
+            ws = self[key] = None               # drop the old buffer first: the allocator may hand its pages to the new one
+            ws = self[key] = self._allocate(int(nbytes) or self.FLOOR, device)
+        return ws
+
+    @staticmethod
+    def _allocate(nbytes: int, device):
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    def tensors(self) -> list:
+        return [ws for ws in self.values() if ws is not None]
+
+    def __deepcopy__(self, memo):
+        return type(self)()
+
+    def __reduce__(self):
+        return type(self), ()
 
 
 def profile_enable(on: bool = True):

@@ -241,10 +241,8 @@ class DeviceDataset:
                 or draws.numel() < (step + 1) * B * 16:
             raise ValueError("the draw table must be a contiguous int32 device tensor holding the step's rows")
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.xsq_batch_assemble(self.pool.data_ptr(), 1 if self.storage == "pcm16" else 0,
-                                                   self.tracks.data_ptr(), len(self), draws.data_ptr(), step, B, n,
-                                                   self._toc.data_ptr(), x.data_ptr(), y.data_ptr(), _lib.stream_ptr()),
-                       "xsq_batch_assemble")
+            _lib.call("xsq_batch_assemble", self.pool.data_ptr(), 1 if self.storage == "pcm16" else 0, self.tracks.data_ptr(), len(self),
+                      draws.data_ptr(), step, B, n, self._toc.data_ptr(), x.data_ptr(), y.data_ptr(), _lib.stream_ptr())
 
     def batch(self, table: DrawTable, step: int, out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
         """(x (B, 2, n) mix, y (4, B, 2, n) targets) of step ``step`` of ``table``, in buffers the dataset owns and

@@ -35,11 +35,10 @@ def _per_block_losses(pred: Sequence[Tensor], target: Sequence[Tensor], masks: O
     F, T = _tables(table)
     with torch.cuda.device(P.device):
         out = torch.empty(len(table), 2, dtype=torch.float64, device=P.device)
-        nbytes = _lib.lib.xsq_loss_workspace(len(table), F.ctypes.data, T.ctypes.data, B, S)
-        ws = _workspace(P.device, nbytes)
-        _lib.check(_lib.lib.xsq_loss_forward(len(table), F.ctypes.data, T.ctypes.data, P.data_ptr(), Tg.data_ptr(),
-                                             M.data_ptr() if M is not None else None, B, S, out.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_loss_forward")
+        ws = _workspace(P.device, _lib.workspace_bytes("xsq_loss_workspace", len(table), F.ctypes.data, T.ctypes.data, B, S,
+                                                       why=f"bad shape: {len(table)} blocks, B={B}, S={S}"))
+        _lib.call("xsq_loss_forward", len(table), F.ctypes.data, T.ctypes.data, P.data_ptr(), Tg.data_ptr(),
+                  M.data_ptr() if M is not None else None, B, S, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
     return out
 
 
@@ -66,17 +65,13 @@ def _sdr(pred: Tensor, target: Tensor, scale: Optional[float]):
     B, n = p.shape[1], p.shape[3]
     with torch.cuda.device(p.device):
         out = torch.empty(1 + 84 * B, dtype=torch.float64, device=p.device)
-        nbytes = _lib.lib.xsq_sdr_loss_workspace(B, n)
-        if nbytes == 0:
-            raise _lib.XsqError(f"xsq_sdr_loss_workspace: bad shape B={B} n={n}")
-        ws = _workspace(p.device, nbytes)
+        ws = _workspace(p.device, _lib.workspace_bytes("xsq_sdr_loss_workspace", B, n, why=f"bad shape B={B} n={n}"))
         if scale is None:
-            _lib.check(_lib.lib.xsq_sdr_loss_forward(p.data_ptr(), t.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     _lib.stream_ptr()), "xsq_sdr_loss_forward")
+            _lib.call("xsq_sdr_loss_forward", p.data_ptr(), t.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
             return out, None
         gy = torch.empty_like(p)
-        _lib.check(_lib.lib.xsq_sdr_loss_backward(p.data_ptr(), t.data_ptr(), B, n, float(scale), out.data_ptr(), gy.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_sdr_loss_backward")
+        _lib.call("xsq_sdr_loss_backward", p.data_ptr(), t.data_ptr(), B, n, float(scale), out.data_ptr(), gy.data_ptr(), ws.data_ptr(),
+                  ws.numel(), _lib.stream_ptr())
     return out, gy
 
 

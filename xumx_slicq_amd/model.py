@@ -42,6 +42,11 @@ def split_bf16_active() -> bool:
     return bool(_SPLIT_BF16_OWNERS)
 
 
+def _cdae_scratch(pool: "_lib.Scratch", device, h, B: int, S: int) -> Tensor:
+    """The workspace of a CDAE call on model handle ``h`` from its owner's pool (xsq_cdae_workspace sets no error text)."""
+    return pool.get(device, _lib.workspace_bytes("xsq_cdae_workspace", h, B, S, why=f"B={B}, S={S}: need at least 3 slices"))
+
+
 class _CausalConv2d(Conv2d):
     """model.py:274-290: left-pads time by kernel_width-1 (parameter holder here)."""
 
@@ -124,6 +129,7 @@ class _SlicedUnmixCDAE(nn.Module):
         scale = torch.from_numpy(1.0 / input_scale).float() if input_scale is not None else torch.ones(nb_f_bins)
         self.input_mean = Parameter(mean)
         self.input_scale = Parameter(scale)
+        self._block_ws = _lib.Scratch()   # the workspaces of the per-block call
 
     def freeze(self):
         for p in self.parameters():
@@ -133,7 +139,7 @@ class _SlicedUnmixCDAE(nn.Module):
     # -- the reference's per-block call, sliced_umx[i](Xblock, abs(Xblock)) (model.py:76-80, 213-271) ------
     def _block_model(self, device: torch.device):
         """A one-block xsq_model of this block's parameters, rebuilt when any of them changed."""
-        idx = device.index if device.index is not None else torch.cuda.current_device()
+        idx = _lib.device_index(device)
         sd = self.state_dict()
         key = tuple((v.data_ptr(), v._version) for v in sd.values())
         cached = self.__dict__.setdefault("_block_handles", {}).get(idx)
@@ -147,9 +153,8 @@ class _SlicedUnmixCDAE(nn.Module):
         T_ = np.asarray([self.nb_t_bins], dtype=np.int32)
         out = C.c_void_p()
         with torch.cuda.device(idx):
-            _lib.check(_lib.lib.xsq_model_create(C.byref(out), 1, F_.ctypes.data, T_.ctypes.data,
-                                                 1 if self.causal else 0, params.ctypes.data, params.size),
-                       "xsq_model_create")
+            _lib.call("xsq_model_create", C.byref(out), 1, F_.ctypes.data, T_.ctypes.data, 1 if self.causal else 0, params.ctypes.data,
+                      params.size)
         self._block_handles[idx] = (key, out)
         return out
 
@@ -163,7 +168,6 @@ class _SlicedUnmixCDAE(nn.Module):
     def __getstate__(self):
         st = dict(self.__dict__)
         st.pop("_block_handles", None)
-        st.pop("_block_ws", None)
         return st
 
     def forward(self, xcomplex: Tensor, x: Tensor):
@@ -193,16 +197,8 @@ class _SlicedUnmixCDAE(nn.Module):
         with torch.cuda.device(dev):
             Y = torch.empty(4, B, 2, F_, S, T_, 2, dtype=torch.float32, device=dev)
             masks = torch.empty(4, B, 2, F_, S, T_, dtype=torch.float32, device=dev)
-            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
-            if nbytes == 0:
-                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
-            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-            wss = self.__dict__.setdefault("_block_ws", {})
-            ws = wss.get(key)
-            if ws is None or ws.numel() < nbytes:
-                ws = wss[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(_lib.lib.xsq_cdae_forward(h, X.data_ptr(), B, S, Y.data_ptr(), masks.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_cdae_forward")
+            ws = _cdae_scratch(self._block_ws, dev, h, B, S)
+            _lib.call("xsq_cdae_forward", h, X.data_ptr(), B, S, Y.data_ptr(), masks.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
             if not self.realtime:
                 wiener_em_arena(table, X, Y.view(-1), B, S)
         return Y, masks
@@ -228,7 +224,7 @@ class Unmix(nn.Module):
         self._F = np.asarray([s[0] for s in shapes], dtype=np.int32)
         self._T = np.asarray([s[1] for s in shapes], dtype=np.int32)
         self._handles = {}      # device index -> (version, handle)
-        self._ws = {}
+        self._ws = _lib.Scratch()
         # EM iterations of the Wiener post-filter of an offline model (the `niter` of the Open-Unmix family; the reference pins
         # 1, phase.py:53-58): read per call, as ``.realtime`` of the blocks.  0 = the mix-phase estimate.
         self.niter = 1
@@ -287,18 +283,18 @@ class Unmix(nn.Module):
         return super().train(mode)
 
     def __deepcopy__(self, memo):
-        """Copies share nothing with the original on the device side: the ctypes handles and workspaces are
-        dropped (a copied raw handle would be freed twice) and rebuilt on the copy's first forward."""
+        """Copies share nothing with the original on the device side: the ctypes handles are dropped (a copied raw handle
+        would be freed twice) and the copy of a workspace pool is empty; both are rebuilt on the copy's first forward."""
         cls = self.__class__
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k in ("_handles", "_ws") else copy.deepcopy(v, memo)
+            new.__dict__[k] = {} if k == "_handles" else copy.deepcopy(v, memo)
         return new
 
     def __getstate__(self):
         st = dict(self.__dict__)
-        st["_handles"], st["_ws"] = {}, {}
+        st["_handles"] = {}
         return st
 
     def packed_parameters(self) -> np.ndarray:
@@ -316,12 +312,12 @@ class Unmix(nn.Module):
             raise _lib.XsqError(f"Unmix runs on a ROCm device only (got '{device}'); there is no CPU fallback")
         if self.training:
             raise _lib.XsqError("the HIP CDAE is the inference path (BatchNorm folded); call .eval()/.freeze()")
-        idx = device.index if device.index is not None else torch.cuda.current_device()
+        idx = _lib.device_index(device)
         ver = self._version()
         cached = self._handles.get(idx)
         if cached is not None and cached[0] == ver:
             # (the option set of the whole native call is state of the handle, read per call: two ints, set every time)
-            _lib.check(_lib.lib.xsq_model_set_wiener_options(cached[1], *self.wiener_options()), "xsq_model_set_wiener_options")
+            _lib.call("xsq_model_set_wiener_options", cached[1], *self.wiener_options())
             return cached[1]
         if cached is not None:
             _lib.lib.xsq_model_destroy(cached[1])
@@ -331,13 +327,12 @@ class Unmix(nn.Module):
             raise _lib.XsqError("all blocks must share the same first-layer type")
         out = C.c_void_p()
         with torch.cuda.device(idx):
-            _lib.check(_lib.lib.xsq_model_create(
-                C.byref(out), len(self.table), self._F.ctypes.data, self._T.ctypes.data,
-                1 if causal.pop() else 0, params.ctypes.data, params.size), "xsq_model_create")
+            _lib.call("xsq_model_create", C.byref(out), len(self.table), self._F.ctypes.data, self._T.ctypes.data, 1 if causal.pop() else 0,
+                      params.ctypes.data, params.size)
             # inside the device guard: bf16 modes allocate and launch on the CURRENT device
-            _lib.check(_lib.lib.xsq_model_set_precision(out, _PRECISIONS[self.precision]), "xsq_model_set_precision")
-            _lib.check(_lib.lib.xsq_model_set_winograd(out, int(getattr(self, "winograd", 23))), "xsq_model_set_winograd")
-            _lib.check(_lib.lib.xsq_model_set_wiener_options(out, *self.wiener_options()), "xsq_model_set_wiener_options")
+            _lib.call("xsq_model_set_precision", out, _PRECISIONS[self.precision])
+            _lib.call("xsq_model_set_winograd", out, int(getattr(self, "winograd", 23)))
+            _lib.call("xsq_model_set_wiener_options", out, *self.wiener_options())
         self._handles[idx] = (ver, out)
         return out
 
@@ -360,7 +355,7 @@ class Unmix(nn.Module):
         note_precision(self, precision)
         for idx, (_ver, h) in self._handles.items():
             with torch.cuda.device(idx):       # the split-weight pool is allocated / converted on the model's device
-                _lib.check(_lib.lib.xsq_model_set_precision(h, _PRECISIONS[precision]), "xsq_model_set_precision")
+                _lib.call("xsq_model_set_precision", h, _PRECISIONS[precision])
 
     def set_winograd(self, on):
         """Fast-convolution forms of the fp32 inference layers.  True (default) = all of them, False = the direct kernels, an int =
@@ -371,7 +366,7 @@ class Unmix(nn.Module):
         output)."""
         self.winograd = (23 if on else 0) if isinstance(on, bool) else int(on)
         for _ver, h in self._handles.values():
-            _lib.check(_lib.lib.xsq_model_set_winograd(h, self.winograd), "xsq_model_set_winograd")
+            _lib.call("xsq_model_set_winograd", h, self.winograd)
 
     def __del__(self):
         try:
@@ -381,15 +376,10 @@ class Unmix(nn.Module):
         except Exception:
             pass
 
+    scratch = property(lambda self: self._ws, doc="the pool of this model's workspaces (``_lib.Scratch``)")
+
     def _workspace(self, device, nbytes):
-        key = (device.index if device.index is not None else torch.cuda.current_device(),
-               torch.cuda.current_stream(device).cuda_stream)      # per stream: see SliCQEngine.workspace
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            self._ws[key] = None
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+        return self._ws.get(device, nbytes)
 
     # -- forward -----------------------------------------------------------------------
     def whitening_target(self, device: torch.device, B: int, S: int):
@@ -398,12 +388,9 @@ class Unmix(nn.Module):
         ``masks_arena`` / ``forward`` call on the same stream runs with ``xin_ready=True`` and skips its magnitude pass."""
         h = self._model(device)
         with torch.cuda.device(device):
-            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
-            if nbytes == 0:
-                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
-            ws = self._workspace(device, nbytes)
+            ws = _cdae_scratch(self._ws, device, h, B, S)
         mean, scale, split = C.c_void_p(), C.c_void_p(), C.c_int()
-        _lib.check(_lib.lib.xsq_model_whitening(h, C.byref(mean), C.byref(scale), C.byref(split)), "xsq_model_whitening")
+        _lib.call("xsq_model_whitening", h, C.byref(mean), C.byref(scale), C.byref(split))
         return ws, mean.value, scale.value, split.value
 
     def masks_arena(self, Xcomplex: List[Tensor], xin_ready: bool = False):
@@ -420,13 +407,9 @@ class Unmix(nn.Module):
         h = self._model(dev)
         with torch.cuda.device(dev):
             masks = torch.empty(self.table.numel(8 * B, S, complex_=False), dtype=torch.float32, device=dev)
-            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
-            if nbytes == 0:
-                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
-            ws = self._workspace(dev, nbytes)
-            _lib.check(_lib.lib.xsq_cdae_forward_xin(h, X.data_ptr(), B, S, None, masks.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(), int(bool(xin_ready))),
-                       "xsq_cdae_forward")
+            ws = _cdae_scratch(self._ws, dev, h, B, S)
+            _lib.call("xsq_cdae_forward_xin", h, X.data_ptr(), B, S, None, masks.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(),
+                      int(bool(xin_ready)))
         return masks, X, B, S
 
     def forward(self, Xcomplex: List[Tensor], return_masks=False, wiener_batch_group: int = 0, xin_ready: bool = False):
@@ -465,13 +448,9 @@ class Unmix(nn.Module):
             Y = torch.empty(self.table.numel(8 * B, S), dtype=torch.float32, device=dev)
             masks = torch.empty(self.table.numel(8 * B, S, complex_=False), dtype=torch.float32,
                                 device=dev) if (return_masks or masked) else None
-            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
-            if nbytes == 0:
-                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
-            ws = self._workspace(dev, nbytes)
-            _lib.check(_lib.lib.xsq_cdae_forward_xin(
-                h, X.data_ptr(), B, S, None if masked else Y.data_ptr(), masks.data_ptr() if masks is not None else None,
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr(), int(bool(xin_ready))), "xsq_cdae_forward")
+            ws = _cdae_scratch(self._ws, dev, h, B, S)
+            _lib.call("xsq_cdae_forward_xin", h, X.data_ptr(), B, S, None if masked else Y.data_ptr(),
+                      masks.data_ptr() if masks is not None else None, ws.data_ptr(), ws.numel(), _lib.stream_ptr(), int(bool(xin_ready)))
             if masked:
                 wiener_em_masked_arena(self.table, X, masks, Y, B, S, batch_group=wiener_batch_group, niter=niter, method=method)
             elif not phasemix:
@@ -491,12 +470,9 @@ class Unmix(nn.Module):
         with torch.cuda.device(dev):
             Y = torch.empty(self.table.numel(2 * J * B, S), dtype=torch.float32, device=dev)
             masks = torch.empty(self.table.numel(8 * B, S, complex_=False), dtype=torch.float32, device=dev)
-            nbytes = _lib.lib.xsq_cdae_workspace(h, B, S)
-            if nbytes == 0:
-                raise _lib.XsqError(f"xsq_cdae_workspace(B={B}, S={S}) failed: need at least 3 slices")
-            ws = self._workspace(dev, nbytes)
-            _lib.check(_lib.lib.xsq_cdae_forward_xin(h, X.data_ptr(), B, S, None, masks.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     _lib.stream_ptr(), int(bool(xin_ready))), "xsq_cdae_forward")
+            ws = _cdae_scratch(self._ws, dev, h, B, S)
+            _lib.call("xsq_cdae_forward_xin", h, X.data_ptr(), B, S, None, masks.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(),
+                      int(bool(xin_ready)))
             wiener_em_masked_arena(self.table, X, masks, Y, B, S, batch_group=group, niter=niter, method=method, softmask=softmask,
                                    residual=residual)
         Ylist = self.table.views(Y, (J, B, 2), S)

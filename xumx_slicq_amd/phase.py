@@ -14,18 +14,11 @@ from torch import Tensor
 from . import _lib
 from .arena import BlockTable
 
-_WS = {}
+SCRATCH = _lib.Scratch()      # the workspaces of this module's calls and of loss.py, statistics.py and slicqfinder.py
 
 
 def _workspace(device, nbytes):
-    key = (device.index if device.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream(device).cuda_stream)          # per stream: see SliCQEngine.workspace
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _WS[key] = None
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-        _WS[key] = ws
-    return ws
+    return SCRATCH.get(device, nbytes)
 
 
 def _tables(table: BlockTable):
@@ -82,32 +75,18 @@ def _em(table: BlockTable, X: Tensor, masks, Y: Tensor, B: int, S: int, win_len:
     ``_options`` form."""
     F, T = _tables(table)
     geometry = (len(table), F.ctypes.data, T.ctypes.data)
-    if flags:
-        name = "xsq_wiener_em_options" if masks is None else "xsq_wiener_em_masked_options"
-        arenas = (X.data_ptr(), Y.data_ptr()) if masks is None else (X.data_ptr(), masks.data_ptr(), Y.data_ptr())
-        ext_max = () if masks is None else (None,)
-        with torch.cuda.device(X.device):
-            nbytes = _lib.lib.xsq_wiener_options_workspace(*geometry, B, S, win_len, niter, meth, flags)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_wiener_options_workspace: bad arguments")
-            ws = _workspace(X.device, nbytes)
-            _lib.check(getattr(_lib.lib, name)(*geometry, *arenas, B, S, win_len, int(batch_group), *ext_max, niter, meth, flags,
-                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
-        return
     name, arenas = "xsq_wiener_em", (X.data_ptr(), Y.data_ptr())
     if masks is not None:
         name, arenas = "xsq_wiener_em_masked", (X.data_ptr(), masks.data_ptr(), Y.data_ptr())
     query, count = "xsq_wiener_workspace", ()
-    if niter != 1:
+    if flags:
+        name, query, count = name + "_options", "xsq_wiener_options_workspace", (niter, meth, flags)
+    elif niter != 1:
         name, query, count = name + "_iter", "xsq_wiener_iter_workspace", (niter, meth)
-    ext_max = (None,) if count and masks is not None else ()          # xsq_wiener_em_masked_iter takes a table; none here
+    ext_max = (None,) if count and masks is not None else ()          # the masked _iter / _options forms take a table; none here
     with torch.cuda.device(X.device):
-        nbytes = getattr(_lib.lib, query)(*geometry, B, S, win_len, *count)
-        if nbytes == 0:
-            raise _lib.XsqError(f"{query}: bad arguments")
-        ws = _workspace(X.device, nbytes)
-        _lib.check(getattr(_lib.lib, name)(*geometry, *arenas, B, S, win_len, int(batch_group), *ext_max, *count,
-                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
+        ws = _workspace(X.device, _lib.workspace_bytes(query, *geometry, B, S, win_len, *count, why="bad arguments"))
+        _lib.call(name, *geometry, *arenas, B, S, win_len, int(batch_group), *ext_max, *count, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
 
 
 def wiener_em_arena(table: BlockTable, X: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
@@ -129,8 +108,8 @@ def wiener_start_arena(table: BlockTable, X: Tensor, mag: Tensor, Y: Tensor, B: 
     start without)."""
     F, T = _tables(table)
     with torch.cuda.device(X.device):
-        _lib.check(_lib.lib.xsq_wiener_start(len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), mag.data_ptr(), Y.data_ptr(), B, S,
-                                             option_flags(softmask, residual), _lib.stream_ptr()), "xsq_wiener_start")
+        _lib.call("xsq_wiener_start", len(table), F.ctypes.data, T.ctypes.data, X.data_ptr(), mag.data_ptr(), Y.data_ptr(), B, S,
+                  option_flags(softmask, residual), _lib.stream_ptr())
 
 
 def wiener_em_masked_arena(table: BlockTable, X: Tensor, masks: Tensor, Y: Tensor, B: int, S: int, win_len: int = 5000,
@@ -162,8 +141,7 @@ def blockwise_phasemix_sep(X_block: Tensor, Ymag_block: Tensor) -> Tensor:
     mag = Ymag_block.contiguous().float()
     with torch.cuda.device(X.device):
         Y = torch.empty(*Ymag_block.shape, 2, dtype=torch.float32, device=X.device)
-        _lib.check(_lib.lib.xsq_phasemix(1, F.ctypes.data, T.ctypes.data, X.data_ptr(), mag.data_ptr(),
-                                         Y.data_ptr(), B, S, _lib.stream_ptr()), "xsq_phasemix")
+        _lib.call("xsq_phasemix", 1, F.ctypes.data, T.ctypes.data, X.data_ptr(), mag.data_ptr(), Y.data_ptr(), B, S, _lib.stream_ptr())
     return Y
 
 

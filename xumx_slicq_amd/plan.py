@@ -134,8 +134,7 @@ class SliCQPlan:
         c = np.ascontiguousarray(self.c, dtype=np.int32)
         gd = np.ascontiguousarray(self.gd, dtype=np.float64)
         out = np.empty_like(gd)
-        _lib.check(_lib.lib.xsq_slicqt_adjoint_window(self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, gd.ctypes.data,
-                                                      out.ctypes.data), "xsq_slicqt_adjoint_window")
+        _lib.call("xsq_slicqt_adjoint_window", self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, gd.ctypes.data, out.ctypes.data)
         return out
 
     def forward_adjoint_window(self) -> np.ndarray:
@@ -147,8 +146,7 @@ class SliCQPlan:
         c = np.ascontiguousarray(self.c, dtype=np.int32)
         g = np.ascontiguousarray(self.g, dtype=np.float32)
         out = np.empty(g.shape, dtype=np.float64)
-        _lib.check(_lib.lib.xsq_slicqt_forward_adjoint_window(self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, g.ctypes.data,
-                                                              out.ctypes.data), "xsq_slicqt_forward_adjoint_window")
+        _lib.call("xsq_slicqt_forward_adjoint_window", self.L, len(Lg), Lg.ctypes.data, c.ctypes.data, g.ctypes.data, out.ctypes.data)
         return out
 
 

@@ -173,9 +173,8 @@ def resample(waveform: torch.Tensor, orig_freq, new_freq, lowpass_filter_width: 
         return y
     x, xs = _rows(waveform)
     with torch.cuda.device(waveform.device):
-        _lib.check(_lib.lib.xsq_resample(x.data_ptr(), xs, x.shape[0], L, y.data_ptr(), Lo, Lo, table.data_ptr(),
-                                         first.data_ptr(), o, n, tab.span, tab.width, _lib.stream_ptr()),
-                   "xsq_resample")
+        _lib.call("xsq_resample", x.data_ptr(), xs, x.shape[0], L, y.data_ptr(), Lo, Lo, table.data_ptr(), first.data_ptr(), o, n, tab.span,
+                  tab.width, _lib.stream_ptr())
     return y
 
 

@@ -125,7 +125,7 @@ class TrackScorer:
         self.perm = target_permutation(self.target_order, self.estimate_order)
         self._perm = (C.c_int * 4)(*self.perm)
         tb, wb = C.c_size_t(0), C.c_size_t(0)
-        _lib.check(_lib.lib.xsq_score_workspace(self.nb_samples, self.length, self.window, C.byref(tb), C.byref(wb)), "xsq_score_workspace")
+        _lib.call("xsq_score_workspace", self.nb_samples, self.length, self.window, C.byref(tb), C.byref(wb))
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.XsqError("scores are computed on a ROCm device only; there is no CPU fallback")
@@ -155,9 +155,8 @@ class TrackScorer:
         with torch.cuda.device(self._table.device):
             if self._scored == 0:
                 self._table.zero_()
-            _lib.check(_lib.lib.xsq_score_accumulate(est.data_ptr(), tgt.data_ptr(), C.cast(self._perm, C.c_void_p), B, n, es, ts, off,
-                                                     self.length, self.window, self._table.data_ptr(), self._ws.data_ptr(),
-                                                     self._ws.numel(), _lib.stream_ptr()), "xsq_score_accumulate")
+            _lib.call("xsq_score_accumulate", est.data_ptr(), tgt.data_ptr(), C.cast(self._perm, C.c_void_p), B, n, es, ts, off,
+                      self.length, self.window, self._table.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr())
         self.position = self._covered = off + n
         self._scored += n
         return self
@@ -169,8 +168,8 @@ class TrackScorer:
         with torch.cuda.device(self._table.device):
             frames = torch.empty(4, B, F, dtype=torch.float64, device=self._table.device)
             scores = torch.empty(4, B, 2, dtype=torch.float64, device=self._table.device)
-            _lib.check(_lib.lib.xsq_score_finalise(self._table.data_ptr(), B, F, SILENT_MODES[self.silent], frames.data_ptr(),
-                                                   scores.data_ptr(), _lib.stream_ptr()), "xsq_score_finalise")
+            _lib.call("xsq_score_finalise", self._table.data_ptr(), B, F, SILENT_MODES[self.silent], frames.data_ptr(), scores.data_ptr(),
+                      _lib.stream_ptr())
             frames, scores = frames.cpu().numpy(), scores.cpu().numpy()        # the only device-to-host traffic
         return {"metric": METRIC, "window": self.window, "silent": self.silent,
                 "targets": {name: {"sdr_median": [float(v) for v in scores[i, :, 0]], "sdr_global": [float(v) for v in scores[i, :, 1]],

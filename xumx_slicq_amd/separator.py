@@ -123,6 +123,7 @@ class Separator(nn.Module):
         self.nsgt, self.insgt, self.cnorm = encoder
         self.quiet = quiet
         self.sources = Separator.sources
+        self._nws = _lib.Scratch()     # the workspaces of the native calls (``_native_ws``)
 
     @property
     def dc_twins(self) -> bool:
@@ -232,11 +233,7 @@ class Separator(nn.Module):
                 static_out = call()
             # the captured kernels hold raw pointers into the grow-only workspaces: keep those tensors
             # alive with the graph even if a later, larger call replaces them in their owners
-            from . import phase
-            keep = (list(self.insgt.nsgt.nsgt._ws.values()) + list(self.nsgt.nsgt.nsgt._ws.values())
-                    + list(self.xumx_model._ws.values()) + list(phase._WS.values())
-                    + list(self.__dict__.get("_nws", {}).values()))
-            entry = cache[key] = [graph, static_in, static_out, keep, slot, audio_big.data_ptr()]
+            entry = cache[key] = [graph, static_in, static_out, self._scratch_tensors(), slot, audio_big.data_ptr()]
         graph, static_in, static_out, _keep, slot, last_ptr = entry
         if slot is None:
             static_in.copy_(audio_big)
@@ -245,6 +242,13 @@ class Separator(nn.Module):
             entry[5] = audio_big.data_ptr()
         graph.replay()
         return static_out
+
+    def _scratch_tensors(self) -> list:
+        """Every live workspace a forward of this separator can have written through: those of the two transforms' engines,
+        of the model, of the post-filter (``phase``) and of the native calls."""
+        from . import phase
+        pools = (self.insgt.nsgt.nsgt.scratch, self.nsgt.nsgt.nsgt.scratch, self.xumx_model.scratch, phase.SCRATCH, self._nws)
+        return [ws for pool in {id(p): p for p in pools}.values() for ws in pool.tensors()]       # (the transforms share an engine)
 
     def _packed_fft(self) -> bool:
         """Packed-fp32 butterflies in the slice FFTs: a DIAGNOSTIC build option (csrc/Makefile PACKED_FFT=1), not part of
@@ -369,14 +373,10 @@ class Separator(nn.Module):
                 key = ("pass", B, n_pad, wiener, self._handle_key(), c.dev.index)
                 nbytes = self.__dict__.setdefault("_nsizes", {}).get(key)
                 if nbytes is None:
-                    nbytes = _lib.lib.xsq_demix_pass_workspace(c.d, c.model, B, n_pad, wiener)
-                    if nbytes == 0:
-                        raise _lib.XsqError("xsq_demix_pass_workspace: " + _lib.last_error())
-                    self._nsizes[key] = nbytes
+                    nbytes = self._nsizes[key] = _lib.workspace_bytes("xsq_demix_pass_workspace", c.d, c.model, B, n_pad, wiener)
                 ws = self._native_ws(c.dev, stream, "pass", nbytes)
-                _lib.check(_lib.lib.xsq_demix_pass(c.d, c.model, audio.data_ptr(), x_rows.data_ptr() if x_rows is not None else None,
-                                                   B, n, n_pad, int(group), wiener, out.data_ptr(), offs.data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), stream), "xsq_demix_pass")
+                _lib.call("xsq_demix_pass", c.d, c.model, audio.data_ptr(), x_rows.data_ptr() if x_rows is not None else None, B, n, n_pad,
+                          int(group), wiener, out.data_ptr(), offs.data_ptr(), ws.data_ptr(), ws.numel(), stream)
             return
         if x_rows is not None:
             audio = torch.cat(keep, dim=0)
@@ -405,14 +405,8 @@ class Separator(nn.Module):
                     and switch(self.xumx_model, "wiener_masked") and switch(self.xumx_model, "niter_method") == "auto")
 
     def _native_ws(self, dev: torch.device, stream_ptr: int, which: str, nbytes: int) -> Tensor:
-        """Grow-only workspace of the native path per (device, stream, main | tail).  PyTorch owns the memory."""
-        key = (dev.index, stream_ptr, which)
-        pool = self.__dict__.setdefault("_nws", {})
-        ws = pool.get(key)
-        if ws is None or ws.numel() < nbytes:
-            pool[key] = None
-            ws = pool[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-        return ws
+        """Grow-only workspace of the native path per (device, stream, main | tail | ...)."""
+        return self._nws.get(dev, nbytes, stream_ptr, which)
 
     def _stream_pool(self, dev: torch.device, n: int = 1) -> list:
         """At least ``n`` side streams of ``dev``: pool[0] = the tail's, pool[1:] = extra pass streams."""
@@ -425,21 +419,21 @@ class Separator(nn.Module):
         """What a native entry point needs before its C calls: the device with an index, the model handle, the demixer, the
         caller's stream and the chunking numbers (``cs``, ``max_stack``, the ``max_item_slices`` cap)."""
         if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+            dev = torch.device("cuda", _lib.device_index(dev))
         return _Native(dev, self.xumx_model._model(dev), self.nsgt.nsgt.nsgt.demixer(dev), torch.cuda.current_stream(dev),
                        int(min(self.chunk_size, 1 << 62)), switch(self, "max_stack"), switch(self, "max_item_slices"))
 
-    def _plan_sizes(self, c: _Native, kind: str, args: tuple, fn, nout: int):
-        """The ``nout`` workspace byte counts of a whole-call shape under the current cap, ``fn(d, model, *args, &size...)``:
+    def _plan_sizes(self, c: _Native, kind: str, args: tuple, query: str, nout: int):
+        """The ``nout`` workspace byte counts of a whole-call shape under the current cap, ``query(d, model, *args, &size...)``:
         asked of the library once per (kind, args, model handle, device, cap) and kept in ``_nsizes``."""
         # the cap is sticky state of the native demixer and part of its plan key: set it on EVERY call, not only on a
         # miss of ``_nsizes`` -- after 0 -> 20 -> 0 a cached shape would otherwise run under the stale cap (ADVICE round 4)
-        _lib.check(_lib.lib.xsq_demixer_set_max_rows(c.d, c.cap), "xsq_demixer_set_max_rows")
+        _lib.call("xsq_demixer_set_max_rows", c.d, c.cap)
         key = (kind,) + args + (self._handle_key(), c.dev.index, c.cap)
         sizes = self.__dict__.setdefault("_nsizes", {})
         if key not in sizes:
             outs = [C.c_size_t() for _ in range(nout)]
-            _lib.check(fn(c.d, c.model, *args, *map(C.byref, outs)), fn.__name__)
+            _lib.call(query, c.d, c.model, *args, *map(C.byref, outs))
             sizes[key] = outs[0].value if nout == 1 else tuple(o.value for o in outs)
         return sizes[key]
 
@@ -456,7 +450,7 @@ class Separator(nn.Module):
             nb, N, dev, main = audio_big.shape[0], audio_big.shape[-1], c.dev, c.main
             overlap = switch(self, "overlap_tail")
             side = self._stream_pool(dev)[0] if overlap else main
-            sizes = self._plan_sizes(c, "forward", (nb, N, c.cs, c.max_stack, wiener), _lib.lib.xsq_separator_workspace, 2)
+            sizes = self._plan_sizes(c, "forward", (nb, N, c.cs, c.max_stack, wiener), "xsq_separator_workspace", 2)
             two = overlap and sizes[1] > 0
             ws = self._native_ws(dev, main.cuda_stream, "main", sizes[0] if two else max(sizes))
             wt = self._native_ws(dev, main.cuda_stream, "tail", sizes[1]) if two else None
@@ -465,12 +459,12 @@ class Separator(nn.Module):
             shared = (1 if two else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), wt.data_ptr() if two else None, wt.numel() if two else 0,
                       main.cuda_stream, side.cuda_stream if two else main.cuda_stream)
             if gains is not None:
-                _lib.check(_lib.lib.xsq_separator_remix(c.d, c.model, audio_big.data_ptr(), nb, N, c.cs, c.max_stack, wiener, *shared,
-                                                        gains.data_ptr(), int(gains.shape[0])), "xsq_separator_remix")
+                _lib.call("xsq_separator_remix", c.d, c.model, audio_big.data_ptr(), nb, N, c.cs, c.max_stack, wiener, *shared,
+                          gains.data_ptr(), int(gains.shape[0]))
                 return out
-            fn, src = ((_lib.lib.xsq_separator_forward, audio_big.data_ptr()) if slot is None
-                       else (_lib.lib.xsq_separator_forward_indirect, slot.data_ptr()))
-            _lib.check(fn(c.d, c.model, src, nb, N, c.cs, c.max_stack, wiener, *shared), "xsq_separator_forward")
+            name, src = (("xsq_separator_forward", audio_big.data_ptr()) if slot is None
+                         else ("xsq_separator_forward_indirect", slot.data_ptr()))
+            _lib.call(name, c.d, c.model, src, nb, N, c.cs, c.max_stack, wiener, *shared)
         return out
 
     def _stacked_chunks(self, nb: int, N: int, cs: int):
@@ -606,10 +600,10 @@ class Separator(nn.Module):
         with torch.cuda.device(c.dev):
             nb, N, stream = audio_big.shape[0], audio_big.shape[-1], c.main.cuda_stream
             args = (nb, N, c.cs, chunk_len, ov, c.max_stack, wiener)
-            ws = self._native_ws(c.dev, stream, "main", self._plan_sizes(c, "segments", args, _lib.lib.xsq_separator_segments_workspace, 1))
+            ws = self._native_ws(c.dev, stream, "main", self._plan_sizes(c, "segments", args, "xsq_separator_segments_workspace", 1))
             out = torch.empty(self._nb_sources(), nb, 2, N, dtype=torch.float32, device=c.dev)
-            _lib.check(_lib.lib.xsq_separator_forward_segments(c.d, c.model, audio_big.data_ptr(), *args, out.data_ptr(),
-                                                               ws.data_ptr(), ws.numel(), stream), "xsq_separator_forward_segments")
+            _lib.call("xsq_separator_forward_segments", c.d, c.model, audio_big.data_ptr(), *args, out.data_ptr(), ws.data_ptr(),
+                      ws.numel(), stream)
         return out
 
     def stream(self, nb_samples: int = 1, hop_slices: int = 1) -> "StreamSession":
@@ -826,8 +820,7 @@ class StreamSession:
                 raise _lib.XsqError(f"stream: a session lives on a ROCm device (the separator's is '{dev}')")
             c = separator._native_call(dev)
             handle = C.c_void_p()
-            _lib.check(_lib.lib.xsq_stream_create(C.byref(handle), c.d, c.model, self.nb_samples, self.hop_slices, self.back, self.ahead),
-                       "xsq_stream_create")
+            _lib.call("xsq_stream_create", C.byref(handle), c.d, c.model, self.nb_samples, self.hop_slices, self.back, self.ahead)
             self._handle = handle
             self._finalizer = weakref.finalize(self, _lib.lib.xsq_stream_destroy, handle)
             with torch.cuda.device(c.dev):
@@ -864,18 +857,15 @@ class StreamSession:
 
     def _step_native(self, c: _Native, ws: Tensor, total: int, out: Tensor, col: int, length: int, new=(None, 0, 0)):
         """``new`` = (address, row stride, count) of the samples that release the step: they ride on its first kernel."""
-        _lib.check(_lib.lib.xsq_stream_step(self._handle, c.model, self._state.data_ptr(), *new, total, out.data_ptr() + 4 * col,
-                                            out.shape[-1], length, ws.data_ptr(), ws.numel(), c.main.cuda_stream), "xsq_stream_step")
+        _lib.call("xsq_stream_step", self._handle, c.model, self._state.data_ptr(), *new, total, out.data_ptr() + 4 * col, out.shape[-1],
+                  length, ws.data_ptr(), ws.numel(), c.main.cuda_stream)
 
     def _native_setup(self):
         sep = self.separator
         c = sep._native_call(self._dev)
         key = sep._handle_key()
         if key not in self._ws_bytes:
-            nbytes = _lib.lib.xsq_stream_workspace(self._handle, c.model)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_stream_workspace: " + _lib.last_error())
-            self._ws_bytes = {key: nbytes}
+            self._ws_bytes = {key: _lib.workspace_bytes("xsq_stream_workspace", self._handle, c.model)}
         return c, sep._native_ws(c.dev, c.main.cuda_stream, "stream", self._ws_bytes[key])
 
     def _step_py(self, total: Optional[int], b0: int, blocks: int, w1: int, out: Tensor, col: int, length: int):
@@ -914,8 +904,8 @@ class StreamSession:
                     self._step_native(c, ws, -1, out, col, per, new=(block.data_ptr() + 4 * pos, block.stride(1), count))
                     col += per
                 else:
-                    _lib.check(_lib.lib.xsq_stream_push(self._handle, self._state.data_ptr(), block.data_ptr() + 4 * pos, block.stride(1), count,
-                                                        c.main.cuda_stream), "xsq_stream_push")
+                    _lib.call("xsq_stream_push", self._handle, self._state.data_ptr(), block.data_ptr() + 4 * pos, block.stride(1), count,
+                              c.main.cuda_stream)
                 pos += count
         self.samples_out += col
         return out

@@ -277,9 +277,9 @@ class RowExchange:
             if use_rccl:
                 from . import _lib
                 path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
-                _lib.check(_lib.lib.xsq_comm_load(path.encode() if os.path.exists(path) else None), "xsq_comm_load")
+                _lib.call("xsq_comm_load", path.encode() if os.path.exists(path) else None)
                 if self.rank == 0:
-                    _lib.check(_lib.lib.xsq_comm_unique_id(uid), "xsq_comm_unique_id")
+                    _lib.call("xsq_comm_unique_id", uid)
         except Exception as e:                                 # noqa: BLE001 -- reported through the collective decision
             err = e
         if several:
@@ -299,7 +299,7 @@ class RowExchange:
             if use_rccl:
                 from . import _lib
                 with torch.cuda.device(self.dev):
-                    _lib.check(_lib.lib.xsq_comm_create(C.byref(out), uid, self.world, self.rank), "xsq_comm_create")
+                    _lib.call("xsq_comm_create", C.byref(out), uid, self.world, self.rank)
         except Exception as e:                                 # noqa: BLE001
             err = e
         if not all_ranks_ok(err is None, group, self.dev, self.world):
@@ -323,9 +323,8 @@ class RowExchange:
             raise RuntimeError("injected fault at the exchange's enqueue")
         if self.comm is not None:
             from . import _lib
-            _lib.check(_lib.lib.xsq_exchange_rows(self.comm, flat.data_ptr(), flat.numel(), dst.data_ptr(), dst.numel(),
-                                                  table.ctypes.data, int(table.shape[0]), 1 if self_loop else 0,
-                                                  _lib.stream_ptr()), "xsq_exchange_rows")
+            _lib.call("xsq_exchange_rows", self.comm, flat.data_ptr(), flat.numel(), dst.data_ptr(), dst.numel(), table.ctypes.data,
+                      int(table.shape[0]), 1 if self_loop else 0, _lib.stream_ptr())
             return
         if self.world == 1 and not self_loop:
             return
@@ -653,8 +652,8 @@ class ShardedDemixer:
             return
         if self.dev.type == "cuda":
             from . import _lib
-            _lib.check(_lib.lib.xsq_place_rows(self.recv[key].data_ptr(), self.flat.data_ptr(), table.data_ptr(),
-                                               nrows, longest, _lib.stream_ptr()), "xsq_place_rows")
+            _lib.call("xsq_place_rows", self.recv[key].data_ptr(), self.flat.data_ptr(), table.data_ptr(), nrows, longest,
+                      _lib.stream_ptr())
             return
         src = self.recv[key]                      # host tensors: the gloo tests' stand-in separator
         for so, do, n in table.tolist():

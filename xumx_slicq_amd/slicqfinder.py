@@ -63,13 +63,10 @@ def ideal_slicqt(sources: Tensor, base, strategy: str = "wiener", wiener_win_len
     eng = base.nsgt
     d = eng.demixer(src.device)
     with torch.cuda.device(src.device):
-        nbytes = _lib.lib.xsq_ideal_workspace(d, B, n, STRATEGIES[strategy], win)
-        if nbytes == 0:
-            raise _lib.XsqError("xsq_ideal_workspace: " + _lib.last_error())
-        ws = eng.workspace(src.device, nbytes)
+        ws = eng.workspace(src.device, _lib.workspace_bytes("xsq_ideal_workspace", d, B, n, STRATEGIES[strategy], win))
         out = torch.empty_like(src)
-        _lib.check(_lib.lib.xsq_ideal_separate(d, src.data_ptr(), B, n, STRATEGIES[strategy], win, out.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _lib.stream_ptr()), "xsq_ideal_separate")
+        _lib.call("xsq_ideal_separate", d, src.data_ptr(), B, n, STRATEGIES[strategy], win, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                  _lib.stream_ptr())
     return out
 
 
@@ -88,16 +85,13 @@ def filter_sources_arena(table, Sc: Tensor, Y: Tensor, B: int, S: int, strategy:
     geometry = (len(table), F.ctypes.data, T.ctypes.data)
     with torch.cuda.device(Sc.device):
         if strategy == "phasemix":
-            _lib.check(_lib.lib.xsq_phasemix_sources(*geometry, Sc.data_ptr(), Y.data_ptr(), B, S, _lib.stream_ptr()), "xsq_phasemix_sources")
+            _lib.call("xsq_phasemix_sources", *geometry, Sc.data_ptr(), Y.data_ptr(), B, S, _lib.stream_ptr())
             return Y
         if strategy != "wiener":
             raise ValueError(f"strategy {strategy!r} not in {sorted(STRATEGIES)}")
-        nbytes = _lib.lib.xsq_wiener_sources_workspace(*geometry, B, S, int(win_len))
-        if nbytes == 0:
-            raise _lib.XsqError("xsq_wiener_sources_workspace: bad arguments")
-        ws = _workspace(Sc.device, nbytes)
-        _lib.check(_lib.lib.xsq_wiener_em_sources(*geometry, Sc.data_ptr(), Y.data_ptr(), B, S, int(win_len), int(batch_group), ws.data_ptr(),
-                                                  ws.numel(), _lib.stream_ptr()), "xsq_wiener_em_sources")
+        ws = _workspace(Sc.device, _lib.workspace_bytes("xsq_wiener_sources_workspace", *geometry, B, S, int(win_len), why="bad arguments"))
+        _lib.call("xsq_wiener_em_sources", *geometry, Sc.data_ptr(), Y.data_ptr(), B, S, int(win_len), int(batch_group), ws.data_ptr(),
+                  ws.numel(), _lib.stream_ptr())
     return Y
 
 

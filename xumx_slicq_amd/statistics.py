@@ -35,9 +35,8 @@ def get_statistics(encoder, tracks: Iterable[Tensor]) -> Tuple[List[np.ndarray],
         with torch.cuda.device(arena.device):
             out = torch.empty(sumF, 2, dtype=torch.float64, device=arena.device)
             ws = _workspace(arena.device, 32 * sumF)
-            _lib.check(_lib.lib.xsq_magnitude_stats(len(table), F.ctypes.data, T.ctypes.data, arena.data_ptr(), C, S,
-                                                    out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                       "xsq_magnitude_stats")
+            _lib.call("xsq_magnitude_stats", len(table), F.ctypes.data, T.ctypes.data, arena.data_ptr(), C, S, out.data_ptr(),
+                      ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         acc += out.cpu().numpy()
         n += S * T.astype(np.float64)
     means, stds, o = [], [], 0

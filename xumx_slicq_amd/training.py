@@ -42,12 +42,12 @@ class PendingLoss:
     def result(self) -> Tuple[float, ...]:
         if self._value is None and self._sdr_mcoef > 0:
             out = (C.c_double * 3)()
-            _lib.check(_lib.lib.xsq_train_loss_sdr(self._trainer._h, self._ticket, out), "xsq_train_loss_sdr")
+            _lib.call("xsq_train_loss_sdr", self._trainer._h, self._ticket, out)
             mse, mask, sdr = float(out[0]), float(out[1]), float(out[2])
             self._value = (mse + mask + self._sdr_mcoef * sdr, mse, mask, sdr)
         if self._value is None:
             out = (C.c_double * 2)()
-            _lib.check(_lib.lib.xsq_train_loss(self._trainer._h, self._ticket, out), "xsq_train_loss")
+            _lib.call("xsq_train_loss", self._trainer._h, self._ticket, out)
             mse, mask = float(out[0]), float(out[1])
             self._value = (mse + mask, mse, mask)
         return self._value
@@ -101,16 +101,15 @@ class Trainer:
         self.nparams = int(params.size)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.xsq_train_create(C.byref(self._h), len(self.table), self._F.ctypes.data,
-                                                 self._T.ctypes.data, 1 if self.causal else 0,
-                                                 params.ctypes.data, params.size), "xsq_train_create")
+            _lib.call("xsq_train_create", C.byref(self._h), len(self.table), self._F.ctypes.data, self._T.ctypes.data,
+                      1 if self.causal else 0, params.ctypes.data, params.size)
         if precision not in ("fp32", "bf16x6", "bf16"):
             raise ValueError(f"precision {precision!r}: the training step offers 'fp32', 'bf16x6' and 'bf16'")
         self.precision = precision
         from .model import note_precision
         note_precision(self, precision)          # bf16x6: no packed-fp32 slice FFT in this process meanwhile
         # "bf16": the reference's autocast arithmetic for the convolutions (training.py:473-476): operands rounded to bf16, fp32 accumulate
-        _lib.check(_lib.lib.xsq_train_set_precision(self._h, {"fp32": 0, "bf16": 1, "bf16x6": 2}[precision]), "xsq_train_set_precision")
+        _lib.call("xsq_train_set_precision", self._h, {"fp32": 0, "bf16": 1, "bf16x6": 2}[precision])
         self._ws = None
         self._need = {}          # workspace bytes per step shape
         self._side = None        # stream of the targets' transform, made by the first step()
@@ -210,7 +209,7 @@ class Trainer:
     def _read(self, what: int) -> "OrderedDict[str, Tensor]":
         buf = np.empty(self.nparams, dtype=np.float32)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.xsq_train_read(self._h, what, buf.ctypes.data), "xsq_train_read")
+            _lib.call("xsq_train_read", self._h, what, buf.ctypes.data)
         out, o = OrderedDict(), 0
         for k, shp in self._spec:
             n = int(np.prod(shp)) if shp else 1
@@ -238,7 +237,7 @@ class Trainer:
             buf[o:o + n] = v.detach().to("cpu", torch.float32).reshape(-1).numpy()
             o += n
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.xsq_train_write(self._h, what, buf.ctypes.data), "xsq_train_write")
+            _lib.call("xsq_train_write", self._h, what, buf.ctypes.data)
 
     def _trainable(self):
         """Keys of ``unmix.parameters()`` in the order torch.optim.AdamW numbers them (training.py:391-393): the

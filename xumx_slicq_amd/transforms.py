@@ -30,6 +30,18 @@ def make_filterbanks(nsgt_base, sample_rate=44100.0):
     return NSGT_SL(nsgt_base), INSGT_SL(nsgt_base)
 
 
+# The A/B switches of a plan handle: switch -> (its setter in the library, default).  ``SliCQEngine`` keeps each as ``_<switch>``.
+_PLAN_SWITCHES = {
+    "fft_backend": ("xsq_plan_set_fft_backend", 0),
+    "band_radix4": ("xsq_plan_set_band_radix4", True),
+    # measured (r02c-e): synthesising the short bands inside the inverse slice FFT kernel is 0.03-0.05 ms SLOWER per
+    # 240 s track than the dense GEMM + workspace round trip it replaces (the kernel is bound by its serial chain of
+    # memory / LDS round trips, and the in-kernel stage adds three) -> off by default; XSQ_SHORT_INLINE=1 / set_short_inline
+    "short_inline": ("xsq_plan_set_short_inline", False),
+    "packed_fft": ("xsq_plan_set_packed_fft", False),        # see set_packed_fft
+}
+
+
 class SliCQEngine:
     """Device-side plan handle (the role NSGT_sliced plays in the reference,
     nsgt/slicq.py:70-230).  One handle per device, created on first use."""
@@ -43,98 +55,88 @@ class SliCQEngine:
         self.fbins_actual = plan.nbands
         self.table = BlockTable(plan.block_shapes())
         self._handles = {}
-        self._ws = {}
-        self._fft_backend = 0
+        self._ws = _lib.Scratch()
+        for switch, (_, default) in _PLAN_SWITCHES.items():
+            setattr(self, "_" + switch, default)
         import os
-        # measured (r02c-e): synthesising the short bands inside the inverse slice FFT kernel is 0.03-0.05 ms SLOWER per
-        # 240 s track than the dense GEMM + workspace round trip it replaces (the kernel is bound by its serial chain of
-        # memory / LDS round trips, and the in-kernel stage adds three) -> off by default; XSQ_SHORT_INLINE=1 / set_short_inline
         self._short_inline = os.environ.get("XSQ_SHORT_INLINE", "0") != "0"
-        self._packed_fft = False        # see set_packed_fft
+
+    scratch = property(lambda self: self._ws, doc="the pool of this engine's workspaces (``_lib.Scratch``)")
+
+    def _apply(self, h):
+        """Sets the four switches of plan handle ``h`` to this engine's values."""
+        for switch, (setter, _) in _PLAN_SWITCHES.items():
+            _lib.call(setter, h, int(getattr(self, "_" + switch)))
+
+    def _set(self, switch: str, value):
+        """Every live handle first, the engine's own value after: one the library refuses (``XsqError``) is not kept."""
+        for h in self._handles.values():
+            _lib.call(_PLAN_SWITCHES[switch][0], h, int(value))
+        setattr(self, "_" + switch, value)
 
     def set_fft_backend(self, backend: int):
         """0 = hand-written LDS slice FFT when the plan allows it (default), 1 = rocFFT."""
-        self._fft_backend = int(backend)
-        for h in self._handles.values():
-            _lib.check(_lib.lib.xsq_plan_set_fft_backend(h, self._fft_backend), "xsq_plan_set_fft_backend")
+        self._set("fft_backend", int(backend))
 
     def set_band_radix4(self, on: bool):
         """True (default): long bands on the radix-4 DFT kernel; False: every band on the dense GEMM."""
-        self._band_radix4 = bool(on)
-        for h in self._handles.values():
-            _lib.check(_lib.lib.xsq_plan_set_band_radix4(h, int(self._band_radix4)), "xsq_plan_set_band_radix4")
+        self._set("band_radix4", bool(on))
 
     def set_packed_fft(self, on: bool):
         """True: the hand-written slice FFT runs its butterflies on packed-fp32 vector instructions (half the vector
         instructions, bitwise the same results).  Diagnostic builds only (csrc/Makefile PACKED_FFT=1): the product library
         refuses (``XsqError``) -- a packed-fp32 transform next to split-bf16 MFMA waves of another stream returned wrong
         values on MI355X and it measured no faster."""
-        on = bool(on)
-        if on == getattr(self, "_packed_fft", False):
-            return
-        for h in self._handles.values():
-            _lib.check(_lib.lib.xsq_plan_set_packed_fft(h, int(on)), "xsq_plan_set_packed_fft")
-        self._packed_fft = on
+        if bool(on) != self._packed_fft:
+            self._set("packed_fft", bool(on))
 
     def set_short_inline(self, on: bool):
         """False (default): bands with Lg < 24 on the dense GEMM with a round trip through the workspace; True: the inverse
         transform synthesises them inside the slice-FFT kernel (A/B switch, same results to fp32 rounding; measured slower)."""
-        self._short_inline = bool(on)
-        for h in self._handles.values():
-            _lib.check(_lib.lib.xsq_plan_set_short_inline(h, int(self._short_inline)), "xsq_plan_set_short_inline")
+        self._set("short_inline", bool(on))
 
     # -- handle management ---------------------------------------------------
     def handle(self, device: torch.device):
         if device.type != "cuda":
             raise _lib.XsqError(
                 f"the sliCQT runs on a ROCm device only (got a tensor on '{device}'); there is no CPU fallback")
-        idx = device.index if device.index is not None else torch.cuda.current_device()
+        idx = _lib.device_index(device)
         h = self._handles.get(idx)
         if h is None:
             p = self.plan
-            out = C.c_void_p()
+            h = C.c_void_p()
             with torch.cuda.device(idx):
                 # a plan built with dc_twins=True: the library derives the table of the mirrored synthesis from Lg, c and gd
-                create = "xsq_plan_create_twins" if p.dc_twins else "xsq_plan_create"
-                _lib.check(getattr(_lib.lib, create)(
-                    C.byref(out), p.L, p.tr, p.nbands,
-                    p.Lg.ctypes.data, p.c.ctypes.data, p.g.ctypes.data, p.gd.ctypes.data, p.tw.ctypes.data),
-                    create)
-            h = out
-            _lib.check(_lib.lib.xsq_plan_set_fft_backend(h, self._fft_backend), "xsq_plan_set_fft_backend")
-            _lib.check(_lib.lib.xsq_plan_set_band_radix4(h, int(getattr(self, "_band_radix4", True))),
-                       "xsq_plan_set_band_radix4")
-            _lib.check(_lib.lib.xsq_plan_set_short_inline(h, int(getattr(self, "_short_inline", False))),
-                       "xsq_plan_set_short_inline")
-            _lib.check(_lib.lib.xsq_plan_set_packed_fft(h, int(getattr(self, "_packed_fft", False))), "xsq_plan_set_packed_fft")
+                _lib.call("xsq_plan_create_twins" if p.dc_twins else "xsq_plan_create", C.byref(h), p.L, p.tr, p.nbands, p.Lg.ctypes.data,
+                          p.c.ctypes.data, p.g.ctypes.data, p.gd.ctypes.data, p.tw.ctypes.data)
+            self._apply(h)
             self._handles[idx] = h
         return h
 
     def demixer(self, device: torch.device):
         """The native whole-call handle of this plan on ``device`` (xsq_demixer: cached row-offset tables of the call
         shapes + the fork / join events of the tail stream); what ``Separator.forward`` issues a track through."""
-        idx = device.index if device.index is not None else torch.cuda.current_device()
+        idx = _lib.device_index(device)
         d = self.__dict__.setdefault("_demixers", {}).get(idx)
         if d is None:
             h = self.handle(device)
             out = C.c_void_p()
             with torch.cuda.device(idx):
-                _lib.check(_lib.lib.xsq_demixer_create(C.byref(out), h), "xsq_demixer_create")
+                _lib.call("xsq_demixer_create", C.byref(out), h)
             d = self._demixers[idx] = out
         return d
 
     def workspace(self, device: torch.device, nbytes: int) -> Tensor:
-        """Grow-only scratch buffer per (device, stream): calls issued on different streams may overlap
-        (Separator.forward runs the tail chunk beside the stacked pass). PyTorch owns the memory."""
-        key = (device.index if device.index is not None else torch.cuda.current_device(),
-               torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = None
-            self._ws[key] = None
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+        """This engine's grow-only scratch buffer of the current stream on ``device`` (``_lib.Scratch``: calls issued on
+        different streams may overlap -- Separator.forward runs the tail chunk beside the stacked pass)."""
+        return self._ws.get(device, nbytes)
+
+    def _scratch(self, query: str, device, h, BC: int, extent: int, *more, least: int = 1) -> Tensor:
+        """The workspace ``query(h, BC, extent, *more)`` asks for, ``extent`` the samples or slices per channel.  The
+        transforms' queries refuse a shape without a message (they set one only where rocFFT refuses a plan), so the shape
+        is named here."""
+        why = None if BC > 0 and extent >= least else f"{BC} channels of {extent}: needs at least 1 of {least}"
+        return self.workspace(device, _lib.workspace_bytes(query, h, BC, extent, *more, why=why))
 
     def close(self):
         """Frees the device side now -- demixers, plan handles, workspaces -- after the work queued on their devices has ended.
@@ -155,18 +157,18 @@ class SliCQEngine:
             pass
 
     def __deepcopy__(self, memo):
-        """The device plan handles and workspaces stay with the original (a copied raw handle would be
-        destroyed twice); the copy creates its own on first use."""
+        """The device plan handles stay with the original (a copied raw handle would be destroyed twice) and the copy of a
+        workspace pool is empty; the copy creates its own on first use."""
         import copy
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            new.__dict__[k] = {} if k in ("_handles", "_ws", "_demixers") else copy.deepcopy(v, memo)
+            new.__dict__[k] = {} if k in ("_handles", "_demixers") else copy.deepcopy(v, memo)
         return new
 
     def __getstate__(self):
         st = dict(self.__dict__)
-        st["_handles"], st["_ws"] = {}, {}
+        st["_handles"] = {}
         st.pop("_demixers", None)
         return st
 
@@ -185,18 +187,13 @@ class SliCQEngine:
         with torch.cuda.device(x.device):
             S = self.plan.num_slices(n)
             arena = torch.empty(self.table.numel(BC, S), dtype=torch.float32, device=x.device)
-            nbytes = _lib.lib.xsq_slicqt_forward_workspace(h, BC, n)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_slicqt_forward_workspace: " + _lib.last_error())
-            ws = self.workspace(x.device, nbytes)
+            ws = self._scratch("xsq_slicqt_forward_workspace", x.device, h, BC, n)
             if whiten is None:
-                _lib.check(_lib.lib.xsq_slicqt_forward(h, xb.data_ptr(), BC, n, arena.data_ptr(), ws.data_ptr(),
-                                                       ws.numel(), _lib.stream_ptr()), "xsq_slicqt_forward")
+                _lib.call("xsq_slicqt_forward", h, xb.data_ptr(), BC, n, arena.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
             else:
                 xin, mean, scale, split = whiten
-                _lib.check(_lib.lib.xsq_slicqt_forward_xin(h, xb.data_ptr(), BC, n, arena.data_ptr(), xin, mean, scale,
-                                                           int(split), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                           "xsq_slicqt_forward_xin")
+                _lib.call("xsq_slicqt_forward_xin", h, xb.data_ptr(), BC, n, arena.data_ptr(), xin, mean, scale, int(split), ws.data_ptr(),
+                          ws.numel(), _lib.stream_ptr())
         return arena, lead, S
 
     def backward(self, arena: Tensor, BC: int, S: int, length: int, out: Tensor = None,
@@ -207,17 +204,12 @@ class SliCQEngine:
         h = self.handle(arena.device)
         with torch.cuda.device(arena.device):
             y = out if out is not None else torch.empty(BC, length, dtype=torch.float32, device=arena.device)
-            nbytes = _lib.lib.xsq_slicqt_inverse_workspace(h, BC, S)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_slicqt_inverse_workspace: " + _lib.last_error())
-            ws = self.workspace(arena.device, nbytes)
+            ws = self._scratch("xsq_slicqt_inverse_workspace", arena.device, h, BC, S)
             if out is not None:
                 assert row_offsets is not None and row_offsets.dtype == torch.int64 and row_offsets.numel() == BC
                 assert out.is_contiguous() and out.dtype == torch.float32
-            _lib.check(_lib.lib.xsq_slicqt_inverse_rows(
-                h, arena.data_ptr(), BC, S, length, y.data_ptr(),
-                row_offsets.data_ptr() if row_offsets is not None else None,
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_rows")
+            _lib.call("xsq_slicqt_inverse_rows", h, arena.data_ptr(), BC, S, length, y.data_ptr(),
+                      row_offsets.data_ptr() if row_offsets is not None else None, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         return y
 
     def backward_adjoint(self, gy: Tensor, S: int, out: Tensor = None) -> Tensor:
@@ -230,12 +222,9 @@ class SliCQEngine:
             if out is not None:
                 assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == self.table.numel(BC, S)
             arena = out if out is not None else torch.empty(self.table.numel(BC, S), dtype=torch.float32, device=gy.device)
-            nbytes = _lib.lib.xsq_slicqt_inverse_adjoint_workspace(h, BC, S, int(out is not None))
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_slicqt_inverse_adjoint_workspace: " + _lib.last_error())
-            ws = self.workspace(gy.device, nbytes)
-            _lib.check(_lib.lib.xsq_slicqt_inverse_adjoint(h, gy.data_ptr(), BC, S, length, arena.data_ptr(), int(out is not None),
-                                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_adjoint")
+            ws = self._scratch("xsq_slicqt_inverse_adjoint_workspace", gy.device, h, BC, S, int(out is not None), least=2)
+            _lib.call("xsq_slicqt_inverse_adjoint", h, gy.data_ptr(), BC, S, length, arena.data_ptr(), int(out is not None), ws.data_ptr(),
+                      ws.numel(), _lib.stream_ptr())
         return arena
 
     def forward_adjoint(self, garena: Tensor, lead, n: int) -> Tensor:
@@ -251,12 +240,8 @@ class SliCQEngine:
                              f"({BC} channels, {S} slices), got {garena.dtype} x {garena.numel()}")
         with torch.cuda.device(garena.device):
             gx = torch.empty(BC, n, dtype=torch.float32, device=garena.device)
-            nbytes = _lib.lib.xsq_slicqt_forward_adjoint_workspace(h, BC, n)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_slicqt_forward_adjoint_workspace: " + _lib.last_error())
-            ws = self.workspace(garena.device, nbytes)
-            _lib.check(_lib.lib.xsq_slicqt_forward_adjoint(h, garena.data_ptr(), BC, n, gx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                           _lib.stream_ptr()), "xsq_slicqt_forward_adjoint")
+            ws = self._scratch("xsq_slicqt_forward_adjoint_workspace", garena.device, h, BC, n)
+            _lib.call("xsq_slicqt_forward_adjoint", h, garena.data_ptr(), BC, n, gx.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         return gx.view(*lead, n)
 
     def backward_masked(self, masks: Tensor, mix: Tensor, BC: int, BCx: int, S: int, length: int, out: Tensor,
@@ -266,15 +251,11 @@ class SliCQEngine:
         for BCx channels.  Output placement as in ``backward``."""
         h = self.handle(masks.device)
         with torch.cuda.device(masks.device):
-            nbytes = _lib.lib.xsq_slicqt_inverse_workspace(h, BC, S)
-            if nbytes == 0:
-                raise _lib.XsqError("xsq_slicqt_inverse_workspace: " + _lib.last_error())
-            ws = self.workspace(masks.device, nbytes)
+            ws = self._scratch("xsq_slicqt_inverse_workspace", masks.device, h, BC, S)
             assert row_offsets.dtype == torch.int64 and row_offsets.numel() == BC
             assert out.is_contiguous() and out.dtype == torch.float32
-            _lib.check(_lib.lib.xsq_slicqt_inverse_masked(
-                h, masks.data_ptr(), mix.data_ptr(), BC, BCx, S, length, out.data_ptr(), row_offsets.data_ptr(),
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_slicqt_inverse_masked")
+            _lib.call("xsq_slicqt_inverse_masked", h, masks.data_ptr(), mix.data_ptr(), BC, BCx, S, length, out.data_ptr(),
+                      row_offsets.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         return out
 
 

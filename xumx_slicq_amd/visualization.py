@@ -167,8 +167,8 @@ def overlap_add_slicq(slicq: Tensor, flatten: bool = False) -> Tensor:
     with torch.cuda.device(x.device):
         size = int(_lib.lib.xsq_spectrogram_overlap_add_size(1, Fa.ctypes.data, Ta.ctypes.data, BC, S, int(flatten)))
         out = torch.empty(size, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib.xsq_spectrogram_overlap_add(1, Fa.ctypes.data, Ta.ctypes.data, x.data_ptr(), BC, S, int(flatten),
-                                                        out.data_ptr(), _lib.stream_ptr()), "xsq_spectrogram_overlap_add")
+        _lib.call("xsq_spectrogram_overlap_add", 1, Fa.ctypes.data, Ta.ctypes.data, x.data_ptr(), BC, S, int(flatten), out.data_ptr(),
+                  _lib.stream_ptr())
     out = out.view(*lead, F, -1, 2)
     return torch.view_as_complex(out) if as_complex else out
 
@@ -187,8 +187,8 @@ def overlap_add_blocks(X_list: Sequence[Tensor], base, flatten: bool = False) ->
     with torch.cuda.device(arena.device):
         size = int(_lib.lib.xsq_spectrogram_overlap_add_size(len(Fa), Fa.ctypes.data, Ta.ctypes.data, BC, S, int(flatten)))
         out = torch.empty(size, dtype=torch.float32, device=arena.device)
-        _lib.check(_lib.lib.xsq_spectrogram_overlap_add(len(Fa), Fa.ctypes.data, Ta.ctypes.data, arena.data_ptr(), BC, S, int(flatten),
-                                                        out.data_ptr(), _lib.stream_ptr()), "xsq_spectrogram_overlap_add")
+        _lib.call("xsq_spectrogram_overlap_add", len(Fa), Fa.ctypes.data, Ta.ctypes.data, arena.data_ptr(), BC, S, int(flatten),
+                  out.data_ptr(), _lib.stream_ptr())
     views, off = [], 0
     for F, T in table.shapes:
         Lout = S * T if flatten else (S + 1) * (T // 2)
@@ -221,8 +221,8 @@ def _db(geo: _Geometry, arena: Tensor) -> Tensor:
     arena = _aligned(arena)
     with torch.cuda.device(arena.device):
         db = torch.empty(geo.B * geo.per_item, dtype=torch.float32, device=arena.device)
-        _lib.check(_lib.lib.xsq_spectrogram_db(len(geo.F), geo.F.ctypes.data, geo.T.ctypes.data, geo.N.ctypes.data, arena.data_ptr(), geo.B,
-                                               geo.S, int(geo.flatten), db.data_ptr(), _lib.stream_ptr()), "xsq_spectrogram_db")
+        _lib.call("xsq_spectrogram_db", len(geo.F), geo.F.ctypes.data, geo.T.ctypes.data, geo.N.ctypes.data, arena.data_ptr(), geo.B, geo.S,
+                  int(geo.flatten), db.data_ptr(), _lib.stream_ptr())
     return db
 
 
@@ -242,8 +242,8 @@ def _order_stats(F: np.ndarray, N: np.ndarray, db: Tensor, B: int, q: float) -> 
     with torch.cuda.device(db.device):
         ws = torch.empty(int(_lib.lib.xsq_spectrogram_order_workspace(B)), dtype=torch.uint8, device=db.device)
         out = torch.empty(B, 2, dtype=torch.float32, device=db.device)
-        _lib.check(_lib.lib.xsq_spectrogram_order_stats(len(F), F.ctypes.data, N.ctypes.data, db.data_ptr(), B, k_lo, k_hi, out.data_ptr(),
-                                                        ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "xsq_spectrogram_order_stats")
+        _lib.call("xsq_spectrogram_order_stats", len(F), F.ctypes.data, N.ctypes.data, db.data_ptr(), B, k_lo, k_hi, out.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         return out.cpu().numpy(), t
 
 
@@ -256,8 +256,8 @@ def quantile(values: Tensor, q: float) -> np.ndarray:
 def _raster(geo: _Geometry, db: Tensor, width: int) -> Tensor:
     with torch.cuda.device(db.device):
         image = torch.empty(geo.B, geo.plan.nbands, int(width), dtype=torch.float32, device=db.device)
-        _lib.check(_lib.lib.xsq_spectrogram_raster(len(geo.F), geo.F.ctypes.data, geo.N.ctypes.data, db.data_ptr(), geo.B, int(width),
-                                                   image.data_ptr(), _lib.stream_ptr()), "xsq_spectrogram_raster")
+        _lib.call("xsq_spectrogram_raster", len(geo.F), geo.F.ctypes.data, geo.N.ctypes.data, db.data_ptr(), geo.B, int(width),
+                  image.data_ptr(), _lib.stream_ptr())
     return image
 
 
