@@ -84,6 +84,22 @@ int xsq_slicqt_dropped_twin_share(int L, int nbands, const int32_t* Lg, const in
 int xsq_plan_create_twins(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg,
                           const int32_t* c, const float* g, const double* gd, const float* tw);
 int xsq_plan_num_twins(const xsq_plan* plan);
+/* xsq_plan_create with options (XSQ_ABI_VERSION stays 2: more exports).  flags = 0 is xsq_plan_create, XSQ_PLAN_TWINS is
+ * xsq_plan_create_twins.  XSQ_PLAN_LONG_BANDS (build_plan(long_bands=True)): every band with Lg above xsq_plan_long_band_min()
+ * (320) runs on the FFT band engine (csrc/band_fft.h: one radix-4 split and a chirp-z transform of length Lg / 4 through a
+ * power-of-two FFT in LDS; O(Lg log Lg) work, tables linear in Lg) instead of the dense engine, whose matrices are quadratic in
+ * Lg -- the upper bands of the logarithmic scales (`cqlog, 12, 20.0`: Lg up to 6416).  Both transforms, both adjoints and the
+ * masked and remix inverses use it; xsq_slicqt_forward_xin refuses such a plan when it has a long band (the network does not
+ * run on one), and such a plan takes the rocFFT path.  A band longer than xsq_plan_long_band_max() (16384) is refused by
+ * name (XSQ_ERR_ARG).  A plan without a band above 320 behaves exactly like that of the other flags alone.
+ * xsq_plan_num_long_bands: the bands on the engine, 0 for a plan without the flag.                                    */
+#define XSQ_PLAN_TWINS 1u
+#define XSQ_PLAN_LONG_BANDS 2u
+int xsq_plan_create_flags(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg,
+                          const int32_t* c, const float* g, const double* gd, const float* tw, unsigned flags);
+int xsq_plan_long_band_max(void);
+int xsq_plan_long_band_min(void);
+int xsq_plan_num_long_bands(const xsq_plan* plan);
 int xsq_plan_destroy(xsq_plan* plan);
 int xsq_plan_num_blocks(const xsq_plan* plan);
 /* slice-FFT backend: 0 (default) = the hand-written LDS-resident transform when L == 18060

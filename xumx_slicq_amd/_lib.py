@@ -46,6 +46,10 @@ _SIGS = {
     "xsq_plan_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "xsq_plan_create_twins": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "xsq_plan_num_twins": (C.c_int, [_vp]),
+    "xsq_plan_create_flags": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_uint]),
+    "xsq_plan_long_band_max": (C.c_int, []),
+    "xsq_plan_long_band_min": (C.c_int, []),
+    "xsq_plan_num_long_bands": (C.c_int, [_vp]),
     "xsq_plan_destroy": (C.c_int, [_vp]),
     "xsq_plan_num_blocks": (C.c_int, [_vp]),
     "xsq_plan_set_fft_backend": (C.c_int, [_vp, C.c_int]),
@@ -190,6 +194,7 @@ for _name, (_res, _args) in _SIGS.items():
     _fn.argtypes = _args
 
 EXPORTED = tuple(_SIGS)
+PLAN_TWINS, PLAN_LONG_BANDS = 1, 2       # the flags of xsq_plan_create_flags: XSQ_PLAN_TWINS, XSQ_PLAN_LONG_BANDS (include/xumx_slicq_hip.h)
 
 
 def build_info() -> dict:

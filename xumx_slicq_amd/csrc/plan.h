@@ -142,6 +142,17 @@ struct xsq_plan {
     void *d_twin_bands = nullptr, *d_twin_asrc = nullptr;   // its transpose: TwinDst per band / TwinSrc per entry
     float2* d_twin_tw = nullptr;                            // e^{2 pi i r / Lg}, r = 0 .. Lg - 1, per distinct Lg of those bands
     int ntwin_bins = 0, ntwin_bands = 0, ntwins = 0;        // ntwins: landing entries (xsq_plan_num_twins)
+    // The FFT band engine (band_fft.h): on a plan of xsq_plan_create_flags with XSQ_PLAN_LONG_BANDS every band above LONG_LG runs there
+    // and has no dense matrix; any other plan has nlong == 0 and launches nothing for it.  Such a plan with a long band takes the
+    // rocFFT path (lds_fft).
+    bool long_bands = false;
+    std::vector<char> on_fft;                       // (nbands) 1: the band runs on the FFT band engine
+    void* d_long = nullptr;                         // LongBandDev table, classes of equal N back to back, largest N first
+    int nlong = 0;
+    std::vector<std::tuple<int, int, int>> long_classes;   // (first entry, entries, N)
+    float *d_poolLf = nullptr, *d_poolLi = nullptr; // chirps, transformed chirps, twiddles, windows: analysis / synthesis direction
+    size_t poolL_floats = 0;
+    float *d_adj_poolLf = nullptr, *d_fadj_poolLi = nullptr;   // the same pools over the adjoints' windows
     // caches keyed by the call shape
     std::mutex mu;
     std::map<std::pair<int, int>, xsq::FftPlan> fft;              // (direction, batch)

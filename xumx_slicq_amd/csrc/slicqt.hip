@@ -27,6 +27,7 @@
 #include "band_dft4.h"
 #include "band_dft4s.h"
 #include "dc_twins.h"
+#include "band_fft.h"
 
 namespace xsq {
 
@@ -458,7 +459,7 @@ __global__ __launch_bounds__(256) void k_remix_combine(RemixArgs a) {
 // plan keeps its one table), 1 the analysis' bands up to LONG_LG, 2 the tiles of k_band_fwd_long over the bands above it
 static int get_band_tiles(xsq_plan* P, int rows, TileTable* out, int part = 0) {
     const bool r4 = P->band_radix4 && P->nbands4 > 0;
-    const auto is_long = [&](int j) { return P->bands[j].Lg > LONG_LG; };
+    const auto is_long = [&](int j) { return P->bands[j].Lg > LONG_LG && !P->on_fft[j]; };
     bool any_long = false;
     for (int j = 0; j < P->nbands; ++j) any_long = any_long || is_long(j);
     if (!any_long) {
@@ -468,6 +469,7 @@ static int get_band_tiles(xsq_plan* P, int rows, TileTable* out, int part = 0) {
     return cached_tiles<TileDev>(P->mu, P->tiles, TileKey{TileKind::BandGemm, rows, 0, part, r4 ? 1 : 0}, out, [&](std::vector<TileDev>& t) {
         // longest tiles first (K = 2*Lg grows along the band table): the launch ends on short tiles
         const auto push = [&](int j) {
+            if (P->on_fft[j]) return;               // (band_fft.h: no dense matrix)
             if (part == 2) { if (is_long(j)) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg, LONG_BM); }
             else if (part == 0 || !is_long(j)) push_group_tiles(t, j, rows, 2 * P->bands[j].Lg);
         };
@@ -598,8 +600,11 @@ static int run_fft(const FftPlan& f, void* in, void* out, void* work, hipStream_
     return XSQ_OK;
 }
 
-// (a plan with the mirrored synthesis adds it to the slice spectra in memory, dc_twins.h: rocFFT whatever L is)
-static inline bool lds_fft(const xsq_plan* P) { return P->fft_backend == 0 && P->L == FFT_L && P->d_tgt != nullptr && P->ntwins == 0; }
+// (a plan with the mirrored synthesis adds it to the slice spectra in memory, dc_twins.h: rocFFT whatever L is; so does a plan
+// with a band on the FFT band engine, which writes Z in the arena's layout, band_fft.h)
+static inline bool lds_fft(const xsq_plan* P) {
+    return P->fft_backend == 0 && P->L == FFT_L && P->d_tgt != nullptr && P->ntwins == 0 && P->nlong == 0;
+}
 static inline FftTables fft_tables(const xsq_plan* P) {
     return FftTables{P->d_T, P->d_T + FFT_R1 * FFT_M1, P->d_T + FFT_R1 * FFT_M1 + FFT_R2 * FFT_R3};
 }
@@ -653,6 +658,7 @@ static int build_band_tables(xsq_plan* P, const PlanArgs& A) {
     P->nblocks = (int)P->blocks.size();
     P->sumFT = cum;
     int64_t woff = 0;
+    P->on_fft.assign(nbands, 0);
     for (const BlockHost& b : P->blocks) {
         for (int f = 0; f < b.F; ++f) {
             const int j = b.first_band + f;
@@ -660,13 +666,18 @@ static int build_band_tables(xsq_plan* P, const PlanArgs& A) {
                 set_error("xsq_plan_create: band %d has Lg=%d c=%d (need Lg%%4==0, c even, Lg<=L/2)", j, Lg[j], c[j]);
                 return XSQ_ERR_ARG;
             }
+            // a long_bands plan: every band above LONG_LG on the FFT band engine (band_fft.h), which has no dense matrix
+            P->on_fft[j] = P->long_bands && Lg[j] > LONG_LG;
+            XSQ_REQUIRE(!P->on_fft[j] || Lg[j] <= LF_MAX_LG, "xsq_plan_create_flags: band %d has Lg=%d, longer than the FFT band engine's "
+                        "maximum %d (XSQ_PLAN_LONG_BANDS, xsq_plan_long_band_max): plan refused", j, Lg[j], LF_MAX_LG);
             BandDev d;
             d.Lg = Lg[j]; d.bin0 = c[j] - Lg[j] / 2; d.f = f; d.F = b.F; d.cum = b.cum;
             d.ldw = (int)round_up(2 * Lg[j], 16); d.w_off = woff; d.ent = 0;
-            woff += round_up(2 * Lg[j], 64) * d.ldw;
+            if (!P->on_fft[j]) woff += round_up(2 * Lg[j], 64) * d.ldw;
             P->bands.push_back(d);
         }
     }
+    P->wf_floats = (size_t)woff;
     return XSQ_OK;
 }
 
@@ -676,11 +687,11 @@ static int build_band_tables(xsq_plan* P, const PlanArgs& A) {
 // index q = (p + Lg/2) mod Lg since windows are stored peak-at-0), n = 2t+ro over coefficients;
 // synthesis: k = 2t+ri over coefficients, n = 2p+ro over spectrum positions.
 static void build_dense_matrices(const xsq_plan* P, const PlanArgs& A, std::vector<float>& Wf, std::vector<float>& Wi) {
-    const BandDev& last = P->bands.back();
-    const size_t floats = (size_t)(last.w_off + round_up(2 * last.Lg, 64) * last.ldw);
+    const size_t floats = P->wf_floats;           // (build_band_tables: the matrices of every band but those of the FFT band engine)
     Wf.assign(floats, 0.f);
     Wi.assign(floats, 0.f);
     for (int j = 0; j < A.nbands; ++j) {
+        if (P->on_fft[j]) continue;
         const BandDev& d = P->bands[j];
         const int n = d.Lg, ld = d.ldw;
         std::vector<double> cs(n), sn(n);
@@ -777,6 +788,7 @@ static void build_radix4_tables(xsq_plan* P, const PlanArgs& A, std::vector<Band
     auto alloc2 = [&](size_t n) { size_t o = pf.size(); pf.resize(o + n, 0.f); pi.resize(o + n, 0.f); return (int64_t)o; };    // analysis / synthesis pools
     for (int j = 0; j < A.nbands; ++j) {
         const BandDev& b = P->bands[j];
+        if (P->on_fft[j]) continue;                 // (band_fft.h: neither engine's)
         if (b.Lg < d4_min_lg || b.Lg > 4 * D4_MPAD) { if (commit) P->bands4_small.push_back(j); is_short[j] = 1; continue; }
         const int n = b.Lg, m = n / 4;
         Band4Dev d;
@@ -920,6 +932,90 @@ static bool build_short_schedule(xsq_plan* P, const PlanArgs& A, const std::vect
     return true;
 }
 
+// Tables of the FFT band engine (band_fft.h) over the bands of on_fft: one pool per direction (pf analysis, pi synthesis), both
+// laid out alike, so one LongBandDev table serves both and the adjoints' pools (`commit` false: only the pools are wanted, the
+// plan stays as it is).  Everything is formed in double and rounded once.
+static void build_long_tables(xsq_plan* P, const PlanArgs& A, std::vector<LongBandDev>& lb, std::vector<float>& pf, std::vector<float>& pi,
+                              bool commit = true) {
+    auto alloc2 = [&](size_t n) { size_t o = pf.size(); n = (size_t)round_up((int64_t)n, 4); pf.resize(o + n, 0.f); pi.resize(o + n, 0.f); return (int64_t)o; };
+    const auto put = [](std::vector<float>& pool, int64_t o, size_t i, double re, double im) { pool[o + 2 * i] = (float)re; pool[o + 2 * i + 1] = (float)im; };
+    std::map<int, int64_t> twoff, choff;
+    std::vector<int> order;
+    for (int j = 0; j < A.nbands; ++j) if (P->on_fft[j]) order.push_back(j);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return A.Lg[x] > A.Lg[y]; });     // classes of N: largest first
+    for (int j : order) {
+        const BandDev& b = P->bands[j];
+        const int n = b.Lg, m = n / 4;
+        int N = 8;
+        while (N < 2 * m - 1) N *= 2;
+        LongBandDev d;
+        memset(&d, 0, sizeof(d));
+        d.Lg = n; d.m = m; d.N = N; d.bin0 = b.bin0; d.f = b.f; d.F = b.F; d.cum = b.cum;
+        if (!twoff.count(N)) {          // e^{-2 pi i k / N}, k < N / 2: both directions' FFT pair
+            const int64_t o = twoff[N] = alloc2((size_t)N);
+            for (int k = 0; k < N / 2; ++k) { put(pf, o, k, std::cos(PI2 * k / N), -std::sin(PI2 * k / N)); put(pi, o, k, std::cos(PI2 * k / N), -std::sin(PI2 * k / N)); }
+        }
+        d.tw_off = twoff[N];
+        // the chirp c[j] = e^{+ pi i j^2 / m} of the analysis (the synthesis': its conjugate), j^2 reduced mod 2 m
+        std::vector<double> cr(m), ci(m);
+        for (int i = 0; i < m; ++i) { const int64_t e = ((int64_t)i * i) % (2 * m); cr[i] = std::cos(PI2 * e / (2.0 * m)); ci[i] = std::sin(PI2 * e / (2.0 * m)); }
+        if (!choff.count(m)) {          // FFT_N of conj(c) on -(m - 1) .. m - 1 (cyclic), over N, in bit-reversed order
+            const int64_t o = choff[m] = alloc2((size_t)2 * N);
+            std::vector<double> xr(N, 0.0), xi(N, 0.0);
+            for (int i = 0; i < m; ++i) { xr[i] = cr[i]; xi[i] = -ci[i]; if (i) { xr[N - i] = cr[i]; xi[N - i] = -ci[i]; } }
+            // decimation in frequency in double, as the kernel's: natural order in, bit-reversed out
+            for (int s = N; s >= 2; s >>= 1) {
+                const int h = s / 2;
+                for (int blk = 0; blk < N; blk += s)
+                    for (int i = 0; i < h; ++i) {
+                        const double wr = std::cos(PI2 * i / s), wi = -std::sin(PI2 * i / s);
+                        const int i0 = blk + i, i1 = i0 + h;
+                        const double ur = xr[i0], ui = xi[i0], vr = xr[i1], vi = xi[i1];
+                        xr[i0] = ur + vr; xi[i0] = ui + vi;
+                        const double dr = ur - vr, di = ui - vi;
+                        xr[i1] = dr * wr - di * wi; xi[i1] = dr * wi + di * wr;
+                    }
+            }
+            // the kernel is symmetric (c[-j] = c[j]), so the synthesis' transform is the conjugate of the analysis'
+            for (int i = 0; i < N; ++i) { put(pf, o, i, xr[i] / N, xi[i] / N); put(pi, o, i, xr[i] / N, -xi[i] / N); }
+        }
+        d.chirp_off = choff[m];
+        d.pre_off = alloc2((size_t)2 * n);
+        d.post_off = alloc2((size_t)2 * n);
+        d.win_off = alloc2((size_t)n);
+        for (int q = 0; q < n; ++q) {
+            const double ga = A.analysis_window(j, q);
+            put(pf, d.pre_off, q, ga * cr[q / 4], ga * ci[q / 4]);
+            put(pi, d.pre_off, q, cr[q / 4], -ci[q / 4]);
+            pi[d.win_off + q] = (float)A.synthesis_window(j, q);
+        }
+        for (int r = 0; r < 4; ++r)
+            for (int k1 = 0; k1 < m; ++k1) {        // c[k1] w^{r k1}: the phase 2 pi (2 (k1^2 mod 2 m) + r k1) / Lg
+                const int64_t e = (2 * (((int64_t)k1 * k1) % (2 * m)) + (int64_t)r * k1) % n;
+                const double re = std::cos(PI2 * e / n), im = std::sin(PI2 * e / n);
+                put(pf, d.post_off, (size_t)r * m + k1, re, im);
+                put(pi, d.post_off, (size_t)r * m + k1, re, -im);
+            }
+        lb.push_back(d);
+    }
+    if (!commit) return;
+    P->nlong = (int)lb.size();
+    for (int i = 0; i < P->nlong;) {
+        int k = i;
+        while (k + 1 < P->nlong && lb[k + 1].N == lb[i].N) ++k;
+        P->long_classes.emplace_back(i, k - i + 1, lb[i].N);
+        i = k + 1;
+    }
+}
+
+// one launch per class of N (band_fft.h)
+template <bool FWD>
+static void launch_band_fft(const xsq_plan* P, const LongArgs& a, int rows, hipStream_t stream) {
+    for (const auto& cl : P->long_classes)
+        hipLaunchKernelGGL(k_band_fft<FWD>, dim3(rows, std::get<1>(cl)), dim3(LF_NT), (size_t)std::get<2>(cl) * sizeof(float2), stream, a,
+                           std::get<0>(cl));
+}
+
 // Tables of the mirrored synthesis (dc_twins.h) from Lg, c and gd alone: band j = 1 .. nbands - 2 with 0 < c_j < Lg_j / 2 lands
 // on bin q - c_j for c_j <= q < Lg_j / 2 with the weight (-1)^(c_j/2) (-1)^q Lg_j gd_j[Lg_j - q] / L (the inverse slice FFT is
 // unnormalised: the 1/L sits in the weights, as in Wi).  Synthesis entries by bin, then band; the transpose's by band, then q,
@@ -962,7 +1058,8 @@ static int build_twin_tables(xsq_plan* P, const PlanArgs& A) {
 }
 
 static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
-                      const float* g, const double* gd, const float* tw, bool twins) {
+                      const float* g, const double* gd, const float* tw, bool twins, bool long_bands) {
+    P->long_bands = long_bands;
     PlanArgs A{L, tr, nbands, Lg, c, g, gd, tw, std::vector<int64_t>(nbands, 0)};
     for (int j = 1; j < nbands; ++j) A.g_off[j] = A.g_off[j - 1] + Lg[j - 1];
     int rc;
@@ -1011,6 +1108,17 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
             if ((rc = upload(P->d_pool4i, pi))) return rc;
         }
     }
+    {
+        std::vector<LongBandDev> lb;
+        std::vector<float> pf, pi;
+        build_long_tables(P, A, lb, pf, pi);
+        if (P->nlong) {
+            if ((rc = upload(P->d_long, lb))) return rc;
+            if ((rc = upload(P->d_poolLf, pf))) return rc;
+            P->poolL_floats = pf.size();
+            if ((rc = upload(P->d_poolLi, pi))) return rc;
+        }
+    }
     if ((rc = upload(P->d_tw, tw, (size_t)L))) return rc;
     // what the adjoint tables are made from on first use (adjoint_tables)
     P->h_Lg.assign(Lg, Lg + nbands); P->h_c.assign(c, c + nbands);
@@ -1032,8 +1140,9 @@ static int plan_build(xsq_plan* P, int L, int tr, int nbands, const int32_t* Lg,
     return XSQ_OK;
 }
 
-// xsq_plan_create (twins false: a plan whose dropped mirrored synthesis is not negligible is refused) and xsq_plan_create_twins
-static int plan_create(const char* who, bool twins, xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
+// xsq_plan_create (twins false: a plan whose dropped mirrored synthesis is not negligible is refused), xsq_plan_create_twins and
+// xsq_plan_create_flags (long_bands: the bands above LONG_LG on the FFT band engine, band_fft.h)
+static int plan_create(const char* who, bool twins, bool long_bands, xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
                        const float* g, const double* gd, const float* tw) {
     XSQ_REQUIRE(out && Lg && c && g && gd && tw, "%s: null argument", who);
     XSQ_REQUIRE(L > 0 && L % 4 == 0 && tr % 2 == 0 && nbands >= 2, "%s: bad L/tr/nbands", who);
@@ -1047,7 +1156,7 @@ static int plan_create(const char* who, bool twins, xsq_plan** out, int L, int t
                     worst, (int)c[worst], (int)Lg[worst], share[worst], (double)XSQ_TWIN_SHARE_MAX);
     }
     xsq_plan* P = new xsq_plan();
-    const int rc = plan_build(P, L, tr, nbands, Lg, c, g, gd, tw, twins);
+    const int rc = plan_build(P, L, tr, nbands, Lg, c, g, gd, tw, twins, long_bands);
     if (rc != XSQ_OK) {          // frees whatever was allocated before the failure
         xsq_plan_destroy(P);
         return rc;
@@ -1075,13 +1184,23 @@ const char* xsq_last_error(void) { return g_err; }
 
 int xsq_plan_create(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
                     const float* g, const double* gd, const float* tw) {
-    return plan_create("xsq_plan_create", false, out, L, tr, nbands, Lg, c, g, gd, tw);
+    return plan_create("xsq_plan_create", false, false, out, L, tr, nbands, Lg, c, g, gd, tw);
 }
 
 int xsq_plan_create_twins(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
                           const float* g, const double* gd, const float* tw) {
-    return plan_create("xsq_plan_create_twins", true, out, L, tr, nbands, Lg, c, g, gd, tw);
+    return plan_create("xsq_plan_create_twins", true, false, out, L, tr, nbands, Lg, c, g, gd, tw);
 }
+
+int xsq_plan_create_flags(xsq_plan** out, int L, int tr, int nbands, const int32_t* Lg, const int32_t* c,
+                          const float* g, const double* gd, const float* tw, unsigned flags) {
+    XSQ_REQUIRE(!(flags & ~(unsigned)(XSQ_PLAN_TWINS | XSQ_PLAN_LONG_BANDS)), "xsq_plan_create_flags: unknown flags 0x%x", flags);
+    return plan_create("xsq_plan_create_flags", (flags & XSQ_PLAN_TWINS) != 0, (flags & XSQ_PLAN_LONG_BANDS) != 0, out, L, tr, nbands, Lg, c, g, gd, tw);
+}
+
+int xsq_plan_long_band_max(void) { return LF_MAX_LG; }
+int xsq_plan_long_band_min(void) { return LONG_LG; }
+int xsq_plan_num_long_bands(const xsq_plan* P) { return P ? P->nlong : XSQ_ERR_ARG; }
 
 int xsq_plan_num_twins(const xsq_plan* P) { return P ? P->ntwins : XSQ_ERR_ARG; }
 
@@ -1099,6 +1218,7 @@ int xsq_plan_destroy(xsq_plan* P) {
     (void)hipFree(P->d_fadj_Wi); (void)hipFree(P->d_fadj_pool4i); (void)hipFree(P->d_fold_dst); (void)hipFree(P->d_fold_src);
     (void)hipFree(P->d_fold_inl_dst); (void)hipFree(P->d_fold_inl_src);
     (void)hipFree(P->d_twin_bins); (void)hipFree(P->d_twin_src); (void)hipFree(P->d_twin_bands); (void)hipFree(P->d_twin_asrc); (void)hipFree(P->d_twin_tw);
+    (void)hipFree(P->d_long); (void)hipFree(P->d_poolLf); (void)hipFree(P->d_poolLi); (void)hipFree(P->d_adj_poolLf); (void)hipFree(P->d_fadj_poolLi);
     (void)hipFree(P->d_s_item1); (void)hipFree(P->d_s_tw1); (void)hipFree(P->d_s_item2); (void)hipFree(P->d_s_tgt); (void)hipFree(P->d_s_wd);
     delete P;
     return XSQ_OK;
@@ -1201,7 +1321,7 @@ int xsq_slicqt_forward_rows(xsq_plan* P, const float* x, const int64_t* x_rows, 
 // S slices per channel from absolute slice s0 on; ring > 0: x is the ring of a streaming session (k_slice_rfft, RING)
 struct RingNew { const float* x; int64_t first, stride; };       // the samples from `first` on, not yet in the ring (row bc at x + bc * stride)
 // the window-dependent tables of the analysis: the plan's own (null) or the adjoint's (adjoint_tables)
-struct AnalysisTables { const float *tw, *Wf, *pool4f; };
+struct AnalysisTables { const float *tw, *Wf, *pool4f, *poolLf; };
 static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot, const int64_t* x_rows, int BC, int64_t n, int S, int64_t s0,
                         int ring, float* coef, float* xin, const float* mean, const float* scale, int split, void* ws, size_t ws_bytes,
                         void* stream_, RingNew fresh = RingNew{nullptr, 0, 0}, const AnalysisTables* adj = nullptr);
@@ -1242,6 +1362,9 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
     const float* d_tw = adj ? adj->tw : P->d_tw;
     const float* d_Wf = adj ? adj->Wf : P->d_Wf;
     const float* d_pool4f = adj ? adj->pool4f : P->d_pool4f;
+    const float* d_poolLf = adj ? adj->poolLf : P->d_poolLf;
+    XSQ_REQUIRE(!xin || !P->nlong, "xsq_slicqt_forward_xin: the whitened magnitude is not written for a plan with bands on the FFT band "
+                "engine (XSQ_PLAN_LONG_BANDS): the network does not run on such a plan");
     hipStream_t stream = (hipStream_t)stream_;
     const int rows = BC * S;
     XSQ_REQUIRE(S >= 2, "xsq_slicqt_forward: signal too short");
@@ -1293,6 +1416,8 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
                        tt.d_tiles, tt.ntiles); }
     if (tl.ntiles) { XSQ_PROF(adj ? "adjoint_band_long" : "band_analysis_long", stream);
     hipLaunchKernelGGL(k_band_fwd_long, dim3(tl.ntiles), dim3(256), 0, stream, op, (const TileDev*)tl.d_tiles); }
+    if (P->nlong) { XSQ_PROF(adj ? "adjoint_band_fft" : "band_analysis_fft", stream);
+    launch_band_fft<true>(P, LongArgs{(const LongBandDev*)P->d_long, d_poolLf, U, coef, BC, S, P->nbins, P->L, nullptr, 0}, rows, stream); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
 }
@@ -1370,6 +1495,12 @@ static int adjoint_tables(xsq_plan* P, AnalysisTables* out) {
         std::vector<Band4Dev> b4;
         std::vector<char> is_short;
         build_radix4_tables(P, A, b4, pf, pi, is_short, false);
+        std::vector<LongBandDev> lb;
+        std::vector<float> lf, li;
+        build_long_tables(P, A, lb, lf, li, false);
+        XSQ_REQUIRE((int)lb.size() == P->nlong && (!P->nlong || lf.size() == P->poolL_floats),
+                    "xsq_slicqt_inverse_adjoint: the adjoint's FFT band tables (%zu floats, %zu bands) do not match the plan's (%zu, %d)", lf.size(),
+                    lb.size(), P->poolL_floats, P->nlong);
         // The kernels reach both pools through the offsets of the plan's ONE band table (d_bands: w_off; d_bands4: d_off, c_off,
         // tw_off, win_off), so the adjoint's pools must be laid out exactly like the plan's: same builders, same band split (the
         // process switches are read once, switches()), only the window entries differ.  The synthesis halves (Wi, pi) the
@@ -1378,15 +1509,16 @@ static int adjoint_tables(xsq_plan* P, AnalysisTables* out) {
                     "xsq_slicqt_inverse_adjoint: the adjoint tables (%zu / %zu floats, %zu radix-4 bands) do not match the plan's (%zu / %zu, %d)",
                     Wf.size(), pf.size(), b4.size(), P->wf_floats, P->pool4_floats, P->nbands4);
         const std::vector<float> ones((size_t)P->L, 1.f);
-        float *tw = nullptr, *dWf = nullptr, *dpf = nullptr;
+        float *tw = nullptr, *dWf = nullptr, *dpf = nullptr, *dlf = nullptr;
         int rc = upload(tw, ones);
         if (!rc) rc = upload(dWf, Wf);
         if (!rc && P->nbands4) rc = upload(dpf, pf);
-        if (rc) { (void)hipFree(tw); (void)hipFree(dWf); (void)hipFree(dpf); return rc; }
-        P->d_adj_tw = tw; P->d_adj_Wf = dWf; P->d_adj_pool4f = dpf;
+        if (!rc && P->nlong) rc = upload(dlf, lf);
+        if (rc) { (void)hipFree(tw); (void)hipFree(dWf); (void)hipFree(dpf); (void)hipFree(dlf); return rc; }
+        P->d_adj_tw = tw; P->d_adj_Wf = dWf; P->d_adj_pool4f = dpf; P->d_adj_poolLf = dlf;
         P->adj_built = true;
     }
-    *out = AnalysisTables{P->d_adj_tw, P->d_adj_Wf, P->d_adj_pool4f};
+    *out = AnalysisTables{P->d_adj_tw, P->d_adj_Wf, P->d_adj_pool4f, P->d_adj_poolLf};
     return XSQ_OK;
 }
 
@@ -1461,7 +1593,7 @@ int xsq_slicqt_inverse(xsq_plan* P, const float* coef, int BC, int S, int64_t le
 // carry != nullptr: the S slices are the new ones of a streaming step and `y` takes its blocks (CarryArgs, slice_fft.h)
 // adj != nullptr: the adjoint of the forward transform (xsq_slicqt_forward_adjoint) -- the synthesis over the tables of its
 // window, the fold of the mirrored entries, and slices multiplied by the slice window before the overlap-add
-struct AdjointSynthesis { const float *Wi, *pool4i, *tw; const FoldDst* dst; const FoldSrc* src; int ndst; FoldSched inl; };
+struct AdjointSynthesis { const float *Wi, *pool4i, *poolLi, *tw; const FoldDst* dst; const FoldSrc* src; int ndst; FoldSched inl; };
 static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int BCx, int BC, int S, int64_t length, float* y,
                         const int64_t* row_offsets, void* ws, size_t ws_bytes, void* stream_, const CarryArgs* carry = nullptr,
                         const AdjointSynthesis* adj = nullptr);
@@ -1521,6 +1653,8 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
     if (tt.ntiles && !inl) { XSQ_PROF(adj ? "fwd_adjoint_band_gemm" : "band_synthesis_gemm", stream);
     hipLaunchKernelGGL((grouped_gemm_kernel<BandInvOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
+    if (P->nlong) { XSQ_PROF(adj ? "fwd_adjoint_band_fft" : "band_synthesis_fft", stream);
+    launch_band_fft<false>(P, LongArgs{(const LongBandDev*)P->d_long, adj ? adj->poolLi : P->d_poolLi, coef, Z, BC, S, P->nbins, P->L, mask, BCx}, rows, stream); }
     // the fold: inside the hand-written slice FFT (FOLD, slice_fft.h), or a pass over Z in front of the rocFFT path's gather
     if (adj && adj->ndst && !lds_fft(P)) { XSQ_PROF("fwd_adjoint_fold", stream);
     hipLaunchKernelGGL(k_fold_mirrored, dim3(rows), dim3(256), 0, stream, Z, P->d_bands, adj->dst, adj->src, adj->ndst, BC, S); }
@@ -1630,6 +1764,12 @@ static int forward_adjoint_tables(xsq_plan* P, AdjointSynthesis* out) {
         std::vector<Band4Dev> b4;
         std::vector<char> is_short;
         build_radix4_tables(P, A, b4, pf, pi, is_short, false);
+        std::vector<LongBandDev> lb;
+        std::vector<float> lf, li;
+        build_long_tables(P, A, lb, lf, li, false);
+        XSQ_REQUIRE((int)lb.size() == P->nlong && (!P->nlong || li.size() == P->poolL_floats),
+                    "xsq_slicqt_forward_adjoint: the adjoint's FFT band tables (%zu floats, %zu bands) do not match the plan's (%zu, %d)", li.size(),
+                    lb.size(), P->poolL_floats, P->nlong);
         // same layout as the plan's own pools: the kernels reach them through the plan's ONE band table (see adjoint_tables)
         XSQ_REQUIRE(Wi.size() == P->wf_floats && (int)b4.size() == P->nbands4 && (!P->nbands4 || pi.size() == P->pool4_floats),
                     "xsq_slicqt_forward_adjoint: the adjoint tables (%zu / %zu floats, %zu radix-4 bands) do not match the plan's (%zu / %zu, %d)",
@@ -1665,20 +1805,21 @@ static int forward_adjoint_tables(xsq_plan* P, AdjointSynthesis* out) {
         std::vector<int4> id;
         std::vector<int> is;
         for (auto& kv : by_bin) { id.push_back(make_int4(kv.first, (int)is.size(), (int)kv.second.size(), 0)); is.insert(is.end(), kv.second.begin(), kv.second.end()); }
-        float *dWi = nullptr, *dpi = nullptr;
+        float *dWi = nullptr, *dpi = nullptr, *dli = nullptr;
         void *dd = nullptr, *ds = nullptr, *did = nullptr, *dis = nullptr;
         int rc = upload(dWi, Wi);
         if (!rc && P->nbands4) rc = upload(dpi, pi);
+        if (!rc && P->nlong) rc = upload(dli, li);
         if (!rc) rc = upload(dd, fd);
         if (!rc) rc = upload(ds, fs);
         if (!rc) rc = upload(did, id);
         if (!rc) rc = upload(dis, is);
-        if (rc) { (void)hipFree(dWi); (void)hipFree(dpi); (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(did); (void)hipFree(dis); return rc; }
-        P->d_fadj_Wi = dWi; P->d_fadj_pool4i = dpi; P->d_fold_dst = dd; P->d_fold_src = ds; P->nfold_dst = (int)fd.size();
+        if (rc) { (void)hipFree(dWi); (void)hipFree(dpi); (void)hipFree(dli); (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(did); (void)hipFree(dis); return rc; }
+        P->d_fadj_Wi = dWi; P->d_fadj_pool4i = dpi; P->d_fadj_poolLi = dli; P->d_fold_dst = dd; P->d_fold_src = ds; P->nfold_dst = (int)fd.size();
         P->d_fold_inl_dst = did; P->d_fold_inl_src = dis; P->nfold_inl = (int)id.size();
         P->fadj_built = true;
     }
-    *out = AdjointSynthesis{P->d_fadj_Wi, P->d_fadj_pool4i, P->d_tw, (const FoldDst*)P->d_fold_dst, (const FoldSrc*)P->d_fold_src, P->nfold_dst,
+    *out = AdjointSynthesis{P->d_fadj_Wi, P->d_fadj_pool4i, P->d_fadj_poolLi, P->d_tw, (const FoldDst*)P->d_fold_dst, (const FoldSrc*)P->d_fold_src, P->nfold_dst,
                             FoldSched{(const int4*)P->d_fold_inl_dst, (const int*)P->d_fold_inl_src, P->nfold_inl}};
     return XSQ_OK;
 }

@@ -43,7 +43,35 @@ def _mel_frequencies(fmin: float, fmax: float, bins: int) -> Tuple[torch.Tensor,
     return torch.tensor(f, dtype=torch.float32), torch.tensor(q, dtype=torch.float32)
 
 
+def _log_frequencies(fmin: float, fmax: float, bins: int, gamma: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nsgt/fscale.py:92-128 (LogScale): geometric centres, plus ``gamma`` Hz for the variable-Q scale, and one constant Q
+    for every band.  The first centre is 2**log2(fmin), as there, not fmin."""
+    lo, hi = math.log2(fmin), math.log2(fmax)
+    step = 2 ** ((hi - lo) / (bins - 1))
+    first = 2 ** lo
+    q = math.sqrt(step) / (step - 1.0) / 2.0
+    f = [first * step ** b + gamma for b in range(bins)]
+    return torch.tensor(f, dtype=torch.float32), torch.tensor([q] * bins, dtype=torch.float32)
+
+
 _SCALES = {"bark": _bark_frequencies, "mel": _mel_frequencies}
+# the logarithmic scales: their upper bands run to thousands of samples, which only the FFT band engine of a ``long_bands`` plan takes
+_LOG_SCALES = {"cqlog": lambda fmin, fmax, bins, fgamma: _log_frequencies(fmin, fmax, bins),
+               "vqlog": lambda fmin, fmax, bins, fgamma: _log_frequencies(fmin, fmax, bins, fgamma)}
+LONG_BAND_MIN = 320          # 4 * D4_MPAD of csrc/band_dft4.h: on a ``long_bands`` plan the bands above it run on the FFT band engine
+
+
+def scale_frequencies(scale: str, fmin: float, fmax: float, bins: int, fgamma: float = 15.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(centres, Q factors) of any scale ``build_plan`` knows, the logarithmic ones included."""
+    if scale in _LOG_SCALES:
+        return _LOG_SCALES[scale](fmin, fmax, bins, fgamma)
+    return _SCALES[scale](fmin, fmax, bins)
+
+
+def long_band_max() -> int:
+    """The longest band the FFT band engine takes (xsq_plan_long_band_max; host arithmetic, no device needed)."""
+    from . import _lib
+    return int(_lib.lib.xsq_plan_long_band_max())
 
 
 def _cosine_sum_window(n: int) -> torch.Tensor:
@@ -101,6 +129,8 @@ class SliCQPlan:
     blocks: List[Tuple[int, int, int]]   # (first_band, F_b, T_b)
     dc_twins: bool = False     # build_plan(dc_twins=True): the device plan computes the mirrored synthesis (xsq_plan_create_twins)
     twins: list = field(default_factory=list)   # [(band, q, landing bins, fp64 dual window of the mirrored band at q)] as oracle.slicqt.Plan.twins
+    long_bands: bool = False   # build_plan(long_bands=True): the device plan runs bands above LONG_BAND_MIN on the FFT band engine (xsq_plan_create_flags)
+    fgamma: float = 15.0       # the offset of the ``vqlog`` centres in Hz; no other scale reads it
 
     @property
     def nbands(self) -> int:
@@ -151,14 +181,25 @@ class SliCQPlan:
 
 
 def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: float = 22050.0,
-               fs: float = 44100.0, min_win: int = 16, dc_twins: bool = False) -> SliCQPlan:
+               fs: float = 44100.0, min_win: int = 16, dc_twins: bool = False, fgamma: float = 15.0,
+               long_bands: bool = False) -> SliCQPlan:
     """``dc_twins`` False: a plan in which a band reaches across DC (0 < c_j < Lg_j / 2) with a mirrored synthesis of
     TWIN_SHARE_MAX or more of the band's own is refused, and a smaller one is dropped by contract.  True: never refused for
     that; the plan carries ``twins`` and the device computes the term.  A plan without such a band
-    is the default plan field for field, with ``twins == []``."""
-    if scale not in _SCALES:
-        raise ValueError(f"scale '{scale}' is not on the accelerated path (have: {sorted(_SCALES)})")
-    f, q = _SCALES[scale](fmin, fmax, fbins)
+    is the default plan field for field, with ``twins == []``.
+
+    ``long_bands`` False: the scales ``cqlog`` and ``vqlog`` are refused.  True: they build (``fgamma`` is the ``vqlog`` offset), the
+    device plan runs every band above LONG_BAND_MIN on the FFT band engine, and a band above
+    ``long_band_max()`` is refused.  A ``bark`` or ``mel`` plan is the default plan field for field but for the flag."""
+    if scale in _LOG_SCALES and long_bands:
+        f, q = _LOG_SCALES[scale](fmin, fmax, fbins, fgamma)
+    elif scale in _LOG_SCALES:
+        raise ValueError(f"scale '{scale}' is not on the accelerated path (have: {sorted(_SCALES)}) unless the plan is built with "
+                         f"long_bands=True: its longest bands need the FFT band engine")
+    elif scale not in _SCALES:
+        raise ValueError(f"scale '{scale}' is not on the accelerated path (have: {sorted(_SCALES)}; with long_bands=True also {sorted(_LOG_SCALES)})")
+    else:
+        f, q = _SCALES[scale](fmin, fmax, fbins)
 
     # slice / transition length, nsgt/fscale.py:40-53
     L = int(torch.ceil(torch.max(q * 8.0 * fs / f)))
@@ -229,6 +270,14 @@ def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: 
     c = np.asarray(centre[:used], dtype=np.int32)
     if np.any(Lg % 4) or np.any(c % 2):
         raise ValueError("plan violates Lg % 4 == 0 / even centre bins; the closed forms need both")
+    if long_bands and int(Lg.max()) > long_band_max():     # xsq_plan_create_flags refuses the same plans
+        worst = int(np.argmax(Lg))
+        raise ValueError(f"plan ({scale}, {fbins}, {fmin}): band {worst} has Lg {int(Lg[worst])}, longer than the FFT band engine's maximum "
+                         f"{long_band_max()} (long_bands, xsq_plan_long_band_max)")
+    if long_bands and int(Lg.max()) > L // 2:              # xsq_plan_create* refuses the same plans (a few-bins log scale's Nyquist band)
+        worst = int(np.argmax(Lg))
+        raise ValueError(f"plan ({scale}, {fbins}, {fmin}): band {worst} has Lg {int(Lg[worst])}, longer than half the slice ({L // 2}): "
+                         f"the library takes bands up to L / 2")
     blocks, j = [], 0
     while j < used:                                 # runs of equal length (nsgt/nsgtf.py:66-78)
         k = j
@@ -257,4 +306,4 @@ def build_plan(scale: str = "bark", fbins: int = 262, fmin: float = 32.9, fmax: 
         scale=scale, fbins=fbins, fmin=fmin, fmax=fmax, fs=fs, L=L, tr=tr, Lg=Lg, c=c,
         g=torch.cat(g[:used]).numpy().astype(np.float32),
         gd=gd_used,
-        tw=tw.numpy(), blocks=blocks, dc_twins=bool(dc_twins), twins=twins)
+        tw=tw.numpy(), blocks=blocks, dc_twins=bool(dc_twins), twins=twins, long_bands=bool(long_bands), fgamma=float(fgamma))

@@ -13,7 +13,9 @@ Departures from the reference, all deliberate:
     of the track's own length is the reference's behaviour where the arena fits one launch;
   * the draws are ONE table made up front from ``numpy.random.default_rng(seed)`` (``draw_params``): a search is reproducible
     anywhere (the reference seeds ``random`` but draws the bins from the unseeded ``numpy.random``);
-  * ``cqlog`` is not a scale ``plan.build_plan`` builds and is refused by name;
+  * the logarithmic scales ``cqlog`` and ``vqlog`` are drawn only with ``long_bands`` (``--long-bands``), which runs their upper
+    bands on the FFT band engine; without it they are refused by name, and with it a draw whose longest band exceeds
+    ``plan.long_band_max()`` is refused and counted like any other;
   * a plan with a band across DC is refused by ``build_plan`` (the library leaves out that band's mirrored synthesis term);
     the oracle then returns four ``-inf`` like a too-long slice, and every refusal is counted and named in the result.
 
@@ -35,6 +37,8 @@ from . import _lib
 STRATEGIES = {"wiener": 0, "phasemix": 1}              # XSQ_IDEAL_WIENER, XSQ_IDEAL_PHASEMIX (include/xumx_slicq_hip.h)
 ORACLE_TARGETS = ("bass", "drums", "vocals", "other")  # the order of TrackEvaluator.oracle's tuple (slicqfinder.py:179-201)
 SCALES = ("bark", "mel")                               # what plan.build_plan builds
+LONG_SCALES = ("bark", "mel", "cqlog", "vqlog")        # ... with long_bands=True
+LONG_DEFAULT_SCALES = ("bark", "mel", "cqlog")         # the reference's default draw (slicqfinder.py: --fscale)
 DEFAULT_PIECE = 2621440                                # Separator.chunk_size
 NEG_INF4 = (float("-inf"),) * 4
 NO_REASON = "the oracle returned four -inf without a reason"
@@ -99,10 +103,11 @@ class TrackEvaluator:
     """slicqfinder.py:120-201 over a ``data.DeviceDataset``.  ``oracle(scale, fmin, bins)`` -> the SDRs of bass, drums,
     vocals, other: per target the mean over ``tracks`` (indices or names; default all) of the whole-track ``sdr_global``.
     ``dc_twins``: score the plans with bands across DC too, decoded with the reference's mirrored synthesis
-    (``plan.build_plan``); by default such a draw is refused."""
+    (``plan.build_plan``); by default such a draw is refused.  ``long_bands``: score ``cqlog`` and ``vqlog`` too, their bands above
+    320 on the FFT band engine; by default those scales are refused."""
 
     def __init__(self, dataset, max_sllen: int = 44100, piece: Optional[int] = None, tracks: Optional[Sequence] = None,
-                 strategy: str = "wiener", wiener_win_len: int = 5000, dc_twins: bool = False):
+                 strategy: str = "wiener", wiener_win_len: int = 5000, dc_twins: bool = False, long_bands: bool = False):
         from .evaluation import _track_indices
         if strategy not in STRATEGIES:
             raise ValueError(f"strategy {strategy!r} not in {sorted(STRATEGIES)}")
@@ -113,6 +118,7 @@ class TrackEvaluator:
         self.tracks = _track_indices(dataset, tracks)
         self.strategy, self.wiener_win_len = strategy, int(wiener_win_len)
         self.dc_twins = bool(dc_twins)
+        self.long_bands = bool(long_bands)
         self.refusals: List[Dict] = []                 # every draw that was not scored, with the reason
 
     def _refuse(self, scale, fmin, bins, reason) -> Tuple[float, float, float, float]:
@@ -124,8 +130,8 @@ class TrackEvaluator:
         from .transforms import NSGTBase
         bins = int(bins)
         try:
-            base = NSGTBase(scale, bins, float(fmin), device=self.dataset.device, dc_twins=self.dc_twins)
-        except ValueError as e:                        # an unknown scale, a band across DC: plan.build_plan says which
+            base = NSGTBase(scale, bins, float(fmin), device=self.dataset.device, dc_twins=self.dc_twins, long_bands=self.long_bands)
+        except ValueError as e:                        # an unknown scale, a band across DC, a band too long: plan.build_plan says which
             return self._refuse(scale, fmin, bins, f"plan refused: {e}")
         if base.sllen > self.max_sllen:                # slicqfinder.py:137: "skip too big transforms"
             return self._refuse(scale, fmin, bins, f"sllen {base.sllen} > max_sllen {self.max_sllen}")
@@ -170,15 +176,15 @@ def _reason(refusals: Optional[List], before: int) -> str:
 
 
 def optimize_many(f: Callable, params: Dict, n_iter: int, per_target: bool = False, seed: int = 42, out: Optional[str] = None,
-                  refusals: Optional[List] = None, dc_twins: Optional[bool] = None) -> Dict:
+                  refusals: Optional[List] = None, dc_twins: Optional[bool] = None, long_bands: Optional[bool] = None) -> Dict:
     """slicqfinder.py:225-354: ``n_iter`` scored rounds; a draw whose oracle value is four ``-inf`` is rerolled (the next
     row of the table is taken in its place) and counted.  ``params``: {"scales", "bins": (lo, hi), "fmin": (lo, hi, step)}.
     The table holds ``8 * n_iter + 8`` draws; a search that exhausts it stops short and says so (``"exhausted"``).
     ``refusals``: the list ``f`` appends its reasons to (``TrackEvaluator.refusals`` for ``TrackEvaluator.oracle``); whatever it
     gained during a refused call becomes that draw's reason, and a draw refused without one says so (``NO_REASON``).
     Returns -- and, with ``out``, writes as JSON -- the best score and parameters (per target with ``per_target``), every
-    scored round, and under ``"refusals"`` every rerolled draw with its reason (``"rerolled"`` counts them).  ``dc_twins`` (when
-    given): the evaluator's flag, recorded in the result under that name."""
+    scored round, and under ``"refusals"`` every rerolled draw with its reason (``"rerolled"`` counts them).  ``dc_twins``, ``long_bands``
+    (when given): the evaluator's flags, recorded in the result under those names."""
     table = draw_params(seed, 8 * int(n_iter) + 8, params["scales"], params["bins"], params["fmin"])
     names = ORACLE_TARGETS if per_target else ("total",)
     best = {t: {"sdr": float("-inf"), "params": None} for t in names}
@@ -205,12 +211,14 @@ def optimize_many(f: Callable, params: Dict, n_iter: int, per_target: bool = Fal
               "exhausted": len(rounds) < n_iter}
     if dc_twins is not None:
         result["dc_twins"] = bool(dc_twins)
+    if long_bands is not None:
+        result["long_bands"] = bool(long_bands)
     _write(result, out)
     return result
 
 
 def evaluate_single(f: Callable, params: Dict, out: Optional[str] = None, refusals: Optional[List] = None,
-                    dc_twins: Optional[bool] = None) -> Dict:
+                    dc_twins: Optional[bool] = None, long_bands: Optional[bool] = None) -> Dict:
     """slicqfinder.py:204-222: one (scale, bins, fmin).  ``refusals``, ``dc_twins``: as in ``optimize_many``; a refused parameter set
     is named with its reason under ``"refusals"``."""
     before = len(refusals) if refusals is not None else 0
@@ -220,6 +228,8 @@ def evaluate_single(f: Callable, params: Dict, out: Optional[str] = None, refusa
               "refusals": [dict(params, reason=_reason(refusals, before))] if _is_reroll(scores) else []}
     if dc_twins is not None:
         result["dc_twins"] = bool(dc_twins)
+    if long_bands is not None:
+        result["long_bands"] = bool(long_bands)
     _write(result, out)
     return result
 
@@ -238,13 +248,15 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--fbins", type=str, default="10,300", metavar="LO,HI", help="bins are drawn from [LO, HI); with --single: the one bin count")
     p.add_argument("--fmins", type=str, default="10,130,0.1", metavar="LO,HI,STEP", help="fmin is drawn from the grid LO, LO + STEP, ... below HI (Hz); with --single: the one fmin")
     p.add_argument("--n-iter", type=int, default=60, help="scored rounds of the search")
-    p.add_argument("--fscale", type=str, default=",".join(SCALES), metavar="NAME,...", help="frequency scales to draw from: bark, mel")
+    p.add_argument("--fscale", type=str, default=None, metavar="NAME,...",
+                   help="frequency scales to draw from: bark, mel (the default), and with --long-bands cqlog, vqlog (default then: bark,mel,cqlog)")
     p.add_argument("--oracle-strategy", type=str, default="wiener", choices=sorted(STRATEGIES), help="one Wiener-EM iteration (default) or the mix phase on the true magnitudes")
     p.add_argument("--random-seed", type=int, default=42, help="seed of the draw table")
     p.add_argument("--max-sllen", type=int, default=44100, help="a plan with a longer slice is not scored and the round is drawn again")
     p.add_argument("--single", action="store_true", help="score the one parameter set --fscale / --fbins / --fmins name; no search")
     p.add_argument("--per-target", action="store_true", help="keep the best parameter set of each target, not of their mean")
     p.add_argument("--dc-twins", action="store_true", help="score plans with bands across DC too (the reference's mirrored synthesis on the device); by default they are drawn again")
+    p.add_argument("--long-bands", action="store_true", help="open the logarithmic scales cqlog and vqlog: their bands above 320 run on the FFT band engine")
     p.add_argument("--root", type=str, required=True, help="<root>/<track>/{vocals,drums,bass,other}.wav, the MUSDB18-HQ layout")
     p.add_argument("--valid", type=str, default=None, metavar="NAME,...", help="the validation track directories (default: all, sorted)")
     p.add_argument("--storage", choices=("fp32", "pcm16"), default="fp32", help="how the stems are kept on the device (pcm16: 16-bit files only)")
@@ -257,12 +269,15 @@ def cli_parser() -> argparse.ArgumentParser:
 def parse_args(p: argparse.ArgumentParser, argv=None):
     """``p.parse_args`` plus the checks between options.  Host only."""
     args = p.parse_args(argv)
+    if args.fscale is None:
+        args.fscale = ",".join(LONG_DEFAULT_SCALES if args.long_bands else SCALES)
     args.scales = [s for s in args.fscale.split(",") if s]
+    allowed = LONG_SCALES if args.long_bands else SCALES
     for s in args.scales:
-        if s == "cqlog":
-            p.error("--fscale cqlog: the constant-Q log scale is not one plan.build_plan builds (bark, mel)")
-        if s not in SCALES:
-            p.error(f"--fscale {s}: not in {SCALES}")
+        if s in LONG_SCALES and s not in allowed:
+            p.error(f"--fscale {s}: the logarithmic scales need --long-bands (their upper bands run on the FFT band engine); without it: {SCALES}")
+        if s not in allowed:
+            p.error(f"--fscale {s}: not in {allowed}")
     if not args.scales:
         p.error("--fscale: at least one scale")
     try:
@@ -289,12 +304,12 @@ def slicqfinder_main(argv=None) -> Dict:
     p = cli_parser()
     args = parse_args(p, argv)
     ds = DeviceDataset.from_directory(args.root, names=args.valid, storage=args.storage, device=args.device)
-    ev = TrackEvaluator(ds, args.max_sllen, piece=args.piece, strategy=args.oracle_strategy, dc_twins=args.dc_twins)
+    ev = TrackEvaluator(ds, args.max_sllen, piece=args.piece, strategy=args.oracle_strategy, dc_twins=args.dc_twins, long_bands=args.long_bands)
     if args.single:
-        return evaluate_single(ev.oracle, args.params, out=args.out, refusals=ev.refusals, dc_twins=ev.dc_twins)
+        return evaluate_single(ev.oracle, args.params, out=args.out, refusals=ev.refusals, dc_twins=ev.dc_twins, long_bands=ev.long_bands)
     print(f"searching scales {args.params['scales']}, bins {args.params['bins']}, fmin {args.params['fmin']}; sllen at most {args.max_sllen}")
     return optimize_many(ev.oracle, args.params, args.n_iter, args.per_target, seed=args.random_seed, out=args.out, refusals=ev.refusals,
-                         dc_twins=ev.dc_twins)
+                         dc_twins=ev.dc_twins, long_bands=ev.long_bands)
 
 
 if __name__ == "__main__":

@@ -107,8 +107,11 @@ class SliCQEngine:
             h = C.c_void_p()
             with torch.cuda.device(idx):
                 # a plan built with dc_twins=True: the library derives the table of the mirrored synthesis from Lg, c and gd
-                _lib.call("xsq_plan_create_twins" if p.dc_twins else "xsq_plan_create", C.byref(h), p.L, p.tr, p.nbands, p.Lg.ctypes.data,
-                          p.c.ctypes.data, p.g.ctypes.data, p.gd.ctypes.data, p.tw.ctypes.data)
+                args = (C.byref(h), p.L, p.tr, p.nbands, p.Lg.ctypes.data, p.c.ctypes.data, p.g.ctypes.data, p.gd.ctypes.data, p.tw.ctypes.data)
+                if p.long_bands:                         # the bands above 320 on the FFT band engine
+                    _lib.call("xsq_plan_create_flags", *args, _lib.PLAN_LONG_BANDS | (_lib.PLAN_TWINS if p.dc_twins else 0))
+                else:
+                    _lib.call("xsq_plan_create_twins" if p.dc_twins else "xsq_plan_create", *args)
             self._apply(h)
             self._handles[idx] = h
         return h
@@ -261,14 +264,16 @@ class SliCQEngine:
 
 class NSGTBase(nn.Module):
     """transforms.py:21-94.  Holds the plan; `.nsgt` is the device engine.  ``dc_twins=True`` accepts a plan with bands across
-    DC and computes the reference's mirrored synthesis of them (``plan.build_plan``); the default refuses such a plan."""
+    DC and computes the reference's mirrored synthesis of them (``plan.build_plan``); the default refuses such a plan.
+    ``long_bands=True`` opens the scales ``cqlog`` and ``vqlog`` (``fgamma``: the offset of the latter's centres) and runs the
+    bands above 320 on the FFT band engine."""
 
-    def __init__(self, scale, fbins, fmin, fmax=22050.0, fgamma=15.0, fs=44100.0, device="cuda", dc_twins=False):
+    def __init__(self, scale, fbins, fmin, fmax=22050.0, fgamma=15.0, fs=44100.0, device="cuda", dc_twins=False, long_bands=False):
         super().__init__()
         self.fbins = fbins
         self.fmin = fmin
         self.fmax = fmax
-        self.plan = build_plan(scale, fbins, fmin, fmax, fs, dc_twins=dc_twins)
+        self.plan = build_plan(scale, fbins, fmin, fmax, fs, dc_twins=dc_twins, fgamma=fgamma, long_bands=long_bands)
         self.sllen, self.trlen = self.plan.L, self.plan.tr
         print(f"scale={scale}, fbins={fbins}, fmin={fmin:.2f}, fmax={fmax:.2f}, "
               f"sllen={self.sllen}, trlen={self.trlen}")

@@ -35,7 +35,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .plan import _SCALES, SliCQPlan
+from .plan import SliCQPlan, scale_frequencies
 
 CMAPS = ("hot", "gray")
 
@@ -88,7 +88,7 @@ def quantile_lerp(v_lo: float, v_hi: float, t: float) -> float:
 
 def band_frequencies(plan: SliCQPlan) -> np.ndarray:
     """(nbands,) float64, Hz: 0 for the DC band, the scale's centre frequencies kept by the plan (0 < f < fs / 2), fs / 2."""
-    f, _q = _SCALES[plan.scale](plan.fmin, plan.fmax, plan.fbins)
+    f, _q = scale_frequencies(plan.scale, plan.fmin, plan.fmax, plan.fbins, plan.fgamma)
     f = f.double().numpy()
     nyq = plan.fs / 2.0
     f = f[(f > 0) & (f < nyq)]
