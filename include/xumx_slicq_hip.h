@@ -89,8 +89,9 @@ int xsq_plan_num_twins(const xsq_plan* plan);
  * (320) runs on the FFT band engine (csrc/band_fft.h: one radix-4 split and a chirp-z transform of length Lg / 4 through a
  * power-of-two FFT in LDS; O(Lg log Lg) work, tables linear in Lg) instead of the dense engine, whose matrices are quadratic in
  * Lg -- the upper bands of the logarithmic scales (`cqlog, 12, 20.0`: Lg up to 6416).  Both transforms, both adjoints and the
- * masked and remix inverses use it; xsq_slicqt_forward_xin refuses such a plan when it has a long band (the network does not
- * run on one), and such a plan takes the rocFFT path.  A band longer than xsq_plan_long_band_max() (16384) is refused by
+ * masked and remix inverses use it; xsq_slicqt_forward_xin and its _rows / _rows_indirect / _ring forms serve such a plan (the
+ * engine's analysis writes the whitened magnitude of its bands beside the coefficients, in the layout and the split-bf16 format
+ * of the other engines: the network runs on one), and such a plan takes the rocFFT path.  A band longer than xsq_plan_long_band_max() (16384) is refused by
  * name (XSQ_ERR_ARG).  A plan without a band above 320 behaves exactly like that of the other flags alone.
  * xsq_plan_num_long_bands: the bands on the engine, 0 for a plan without the flag.                                    */
 #define XSQ_PLAN_TWINS 1u

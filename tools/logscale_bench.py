@@ -21,6 +21,15 @@ dc_twins=True)`` accepts at the engine's maximum with sllen <= 44100, and why th
 One JSON line per (plan, shape, arm), appended to --out as well.
 
     python tools/logscale_bench.py [--rounds 7] [--iters 2] [--out profiles/logscale_bench.jsonl]
+
+``--net``: instead of the above, ``Separator.forward`` of the seeded offline model (Wiener-EM) with ``long_bands=True`` on the same two
+plans and shapes, two arms alternated round by round:
+    separator/fused   the default: the analysis kernels (the FFT band engine among them) write the CDAE's whitened magnitude
+    separator/two_pass  ``fuse_whiten = False``: the Python chunk loop, the model's own magnitude pass
+each with the per-kernel table of one call from the library's event profiler (``kernels_ms``) and the device memory the model's weight
+pools take (``weight_pools_bytes``: what ``xsq_model_create`` allocates, read from the driver's free-memory count).
+
+    python tools/logscale_bench.py --net [--out profiles/logscale_net_bench.jsonl]
 """
 import argparse
 import json
@@ -117,6 +126,67 @@ def draw_census(count):
     return {"tool": "logscale_bench", "arm": "draw-census", "scale": "cqlog", "draws": len(table), "seed": 42, "engine_max": long_band_max(), **res}
 
 
+def net_bench(args):
+    from xumx_slicq_amd import _lib
+    from xumx_slicq_amd.separator import seeded_separator
+    from xumx_slicq_amd.synth import synth_audio_device
+    dev = torch.device("cuda", 0)
+    lines = []
+    for pk in args.plans:
+        scale, fbins, fmin = PLANS[pk]
+        sep = seeded_separator(realtime=False, device=dev, fscale=scale, fbins=fbins, fmin=fmin, long_bands=True)
+        plan = sep.nsgt.nsgt.plan
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info(dev)[0]
+        sep.xumx_model._model(dev)                       # xsq_model_create: the folded and the transformed weight pools
+        torch.cuda.synchronize()
+        pools = int(free0 - torch.cuda.mem_get_info(dev)[0])
+        for shape in args.shapes:
+            B, n = SHAPES[shape]
+            x = synth_audio_device(n, 20260300, dev, nb_samples=B)
+
+            def arm(fused):
+                sep.fuse_whiten = fused
+                return sep(x)
+
+            arms = {"separator/fused": lambda: arm(True), "separator/two_pass": lambda: arm(False)}
+            with torch.no_grad():
+                a, b = arms["separator/fused"]().clone(), arms["separator/two_pass"]().clone()
+                same = bool(torch.equal(a, b))
+                del a, b
+                for fn in arms.values():
+                    for _ in range(args.warmup):
+                        fn()
+                torch.cuda.synchronize()
+                times = {name: [] for name in arms}
+                for _ in range(args.rounds):
+                    for name, fn in arms.items():
+                        times[name].append(event_timed(fn, args.iters))
+                kernels = {}
+                for name, fn in arms.items():
+                    _lib.profile_reset()
+                    _lib.profile_enable(True)
+                    fn()
+                    torch.cuda.synchronize()
+                    kernels[name] = {k: [round(float(v[0]), 4), int(v[1])] for k, v in sorted(_lib.profile_read().items())}
+                    _lib.profile_enable(False)
+            sep.fuse_whiten = True
+            for name, t in times.items():
+                t = np.array(t)
+                line = {"tool": "logscale_bench", "mode": "net", "plan": list(PLANS[pk]), "L": plan.L, "longest_band": int(plan.Lg.max()),
+                        "long_bands": int((plan.Lg > 320).sum()), "blocks": len(plan.blocks), "shape": shape, "B": B, "samples": n,
+                        "slices": plan.num_slices(n), "arm": name, "rounds": args.rounds, "clock": "hip-events",
+                        "ms_median": round(float(np.median(t)), 4), "ms_min": round(float(t.min()), 4), "ms_max": round(float(t.max()), 4),
+                        "two_arms_bitwise_equal": same, "weight_pools_bytes": pools, "kernels_ms": kernels[name]}
+                lines.append(line)
+                print(json.dumps(line), flush=True)
+            del x
+            torch.cuda.empty_cache()
+        sep.drop_graphs()
+        del sep
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rounds", type=int, default=7)
@@ -126,7 +196,16 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--draws", type=int, default=100)
     ap.add_argument("--out", type=str, default=os.path.join("profiles", "logscale_bench.jsonl"))
+    ap.add_argument("--net", action="store_true", help="time Separator.forward on the two plans instead of the transforms")
     args = ap.parse_args()
+    if args.net:
+        lines = net_bench(args)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                for line in lines:
+                    f.write(json.dumps(line) + "\n")
+        return
 
     from xumx_slicq_amd import _lib, phase
     from xumx_slicq_amd.slicqfinder import ideal_slicqt

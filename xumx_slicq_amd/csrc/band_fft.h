@@ -26,6 +26,7 @@
 // needs no workspace.  Fixed order throughout: the same bits every run.
 #pragma once
 #include "common.h"
+#include "gemm_tile_bf3.h"
 
 namespace xsq {
 
@@ -36,6 +37,7 @@ constexpr int LF_MAX_LG = 4 * (LF_MAX_N / 2);   // N >= 2 m - 1 with m = Lg / 4:
 struct LongBandDev {
     int Lg, m, N;          // N: power of two >= 2 m - 1, 8 <= N <= LF_MAX_N
     int bin0, f, F;        // as BandDev
+    int jband;             // band index inside the plan (= row of the model's input_mean / input_scale tables), as Band4Dev's
     int64_t cum;
     int64_t pre_off, post_off, win_off, chirp_off, tw_off;     // float offsets into the direction's pool
 };
@@ -46,10 +48,17 @@ struct LongArgs {
     const float* in;       // analysis: slice spectra U (rows of nbins complex); synthesis: the coefficient (or mix) arena
     float* out;            // analysis: the coefficient arena; synthesis: Z (arena layout).  CONTRACT: `out` never overlaps `in` (nor `mask`):
                            // the kernel parks its four sub-transforms on the band's output row while it still reads the input
-                           // row (forward_impl: U -> coef; inverse_impl: coef -> Z in the workspace)
+                           // row (forward_impl: U -> coef; inverse_impl: coef -> Z in the workspace).  `xin` lies in the CDAE's
+                           // workspace and overlaps neither: it is only written, once per entry, after the last read of the parked row
     int BC, S, nbins, L;
     const float* mask;     // synthesis, optional: coefficients = mask * mix, `in` the mix arena of BCx channels
     int BCx;
+    // analysis, optional: the CDAE's whitened magnitude (|coef| + mean[band]) * scale[band] written beside the coefficients, same
+    // arena layout, real; split = 1: in the split-bf16 operand format -- Band4Args' fields of the same names (band_dft4.h)
+    float* xin;
+    const float* mean;
+    const float* scale;
+    int split;
 };
 
 __device__ __forceinline__ float2 lf_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -167,6 +176,9 @@ __global__ __launch_bounds__(LF_NT) void k_band_fft(const LongArgs a, int first)
         for (int k1 = threadIdx.x; k1 < m; k1 += LF_NT) orow[r * m + k1] = lf_mul(lf_buf[k1], post[r * m + k1]);
         __syncthreads();
     }
+    float* xrow = nullptr;                       // analysis: the band's row of the whitened magnitude (uniform)
+    float w_mu = 0.f, w_sc = 1.f;
+    if (FWD && a.xin) { xrow = a.xin + arena_row(a.BC, bc); w_mu = a.mean[b.jband]; w_sc = a.scale[b.jband]; }
     // the radix-4 step over what this lane parked: Y[k1 + m k2] = sum_r (sigma i)^{r k2} A_r[k1]
     for (int k1 = threadIdx.x; k1 < m; k1 += LF_NT) {
         const float2 a0 = orow[k1], a1 = orow[m + k1], a2 = orow[2 * m + k1], a3 = orow[3 * m + k1];
@@ -176,6 +188,13 @@ __global__ __launch_bounds__(LF_NT) void k_band_fft(const LongArgs a, int first)
         if (FWD) {
 #pragma unroll
             for (int k2 = 0; k2 < 4; ++k2) orow[k1 + m * k2] = y[k2];
+            if (xrow) {         // the epilogue of band_dft4.h (FWD && a.xin): a split word depends on its own value alone
+#pragma unroll
+                for (int k2 = 0; k2 < 4; ++k2) {
+                    const float wm = whiten_mag(y[k2].x, y[k2].y, w_mu, w_sc);
+                    xrow[k1 + m * k2] = a.split ? bf3_word(wm) : wm;
+                }
+            }
         } else {        // window index q = k1 + m k2 lands on spectrum position (q + Lg / 2) mod Lg = k1 + m ((k2 + 2) mod 4)
 #pragma unroll
             for (int k2 = 0; k2 < 4; ++k2) {

@@ -950,7 +950,7 @@ static void build_long_tables(xsq_plan* P, const PlanArgs& A, std::vector<LongBa
         while (N < 2 * m - 1) N *= 2;
         LongBandDev d;
         memset(&d, 0, sizeof(d));
-        d.Lg = n; d.m = m; d.N = N; d.bin0 = b.bin0; d.f = b.f; d.F = b.F; d.cum = b.cum;
+        d.Lg = n; d.m = m; d.N = N; d.bin0 = b.bin0; d.f = b.f; d.F = b.F; d.jband = j; d.cum = b.cum;
         if (!twoff.count(N)) {          // e^{-2 pi i k / N}, k < N / 2: both directions' FFT pair
             const int64_t o = twoff[N] = alloc2((size_t)N);
             for (int k = 0; k < N / 2; ++k) { put(pf, o, k, std::cos(PI2 * k / N), -std::sin(PI2 * k / N)); put(pi, o, k, std::cos(PI2 * k / N), -std::sin(PI2 * k / N)); }
@@ -1363,8 +1363,6 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
     const float* d_Wf = adj ? adj->Wf : P->d_Wf;
     const float* d_pool4f = adj ? adj->pool4f : P->d_pool4f;
     const float* d_poolLf = adj ? adj->poolLf : P->d_poolLf;
-    XSQ_REQUIRE(!xin || !P->nlong, "xsq_slicqt_forward_xin: the whitened magnitude is not written for a plan with bands on the FFT band "
-                "engine (XSQ_PLAN_LONG_BANDS): the network does not run on such a plan");
     hipStream_t stream = (hipStream_t)stream_;
     const int rows = BC * S;
     XSQ_REQUIRE(S >= 2, "xsq_slicqt_forward: signal too short");
@@ -1417,7 +1415,7 @@ static int forward_impl(xsq_plan* P, const float* x, const float* const* x_slot,
     if (tl.ntiles) { XSQ_PROF(adj ? "adjoint_band_long" : "band_analysis_long", stream);
     hipLaunchKernelGGL(k_band_fwd_long, dim3(tl.ntiles), dim3(256), 0, stream, op, (const TileDev*)tl.d_tiles); }
     if (P->nlong) { XSQ_PROF(adj ? "adjoint_band_fft" : "band_analysis_fft", stream);
-    launch_band_fft<true>(P, LongArgs{(const LongBandDev*)P->d_long, d_poolLf, U, coef, BC, S, P->nbins, P->L, nullptr, 0}, rows, stream); }
+    launch_band_fft<true>(P, LongArgs{(const LongBandDev*)P->d_long, d_poolLf, U, coef, BC, S, P->nbins, P->L, nullptr, 0, xin, mean, scale, split}, rows, stream); }
     XSQ_HIP(hipGetLastError());
     return XSQ_OK;
 }
@@ -1654,7 +1652,7 @@ static int inverse_impl(xsq_plan* P, const float* coef, const float* mask, int B
     hipLaunchKernelGGL((grouped_gemm_kernel<BandInvOp>), dim3(tt.ntiles), dim3(256), 0, stream, op,
                        tt.d_tiles, tt.ntiles); }
     if (P->nlong) { XSQ_PROF(adj ? "fwd_adjoint_band_fft" : "band_synthesis_fft", stream);
-    launch_band_fft<false>(P, LongArgs{(const LongBandDev*)P->d_long, adj ? adj->poolLi : P->d_poolLi, coef, Z, BC, S, P->nbins, P->L, mask, BCx}, rows, stream); }
+    launch_band_fft<false>(P, LongArgs{(const LongBandDev*)P->d_long, adj ? adj->poolLi : P->d_poolLi, coef, Z, BC, S, P->nbins, P->L, mask, BCx, nullptr, nullptr, nullptr, 0}, rows, stream); }
     // the fold: inside the hand-written slice FFT (FOLD, slice_fft.h), or a pass over Z in front of the rocFFT path's gather
     if (adj && adj->ndst && !lds_fft(P)) { XSQ_PROF("fwd_adjoint_fold", stream);
     hipLaunchKernelGGL(k_fold_mirrored, dim3(rows), dim3(256), 0, stream, Z, P->d_bands, adj->dst, adj->src, adj->ndst, BC, S); }

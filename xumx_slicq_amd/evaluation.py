@@ -127,6 +127,10 @@ def cli_parser() -> argparse.ArgumentParser:
     p.add_argument("--storage", choices=("fp32", "pcm16"), default="fp32", help="how the stems are kept on the device (pcm16: 16-bit files only)")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--out", type=str, required=True, help="directory for <track>.json and aggregate.json")
+    p.add_argument("--long-bands", action="store_true",
+                   help="accept a model trained on the cqlog or vqlog scale: its bands above 320 samples run on the FFT band engine")
+    p.add_argument("--fgamma", type=float, default=15.0, metavar="HZ",
+                   help="offset of the vqlog band centres where the model's JSON names none (default 15.0)")
     return p
 
 
@@ -156,9 +160,10 @@ def evaluation_main(argv=None) -> Dict:
     args = parse_args(p, argv)
     if args.model_path:
         separator = Separator.load(model_path=args.model_path, runtime_backend="hip-rocm", realtime=args.realtime, device=args.device,
-                                   niter=args.niter, softmask=args.softmask or None)
+                                   niter=args.niter, softmask=args.softmask or None, long_bands=args.long_bands, fgamma=args.fgamma)
     else:
-        separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter, softmask=args.softmask or None)
+        separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter, softmask=args.softmask or None,
+                                     long_bands=args.long_bands, fgamma=args.fgamma)
     names = args.tracks
     if names is None:
         names = sorted(d for d in os.listdir(args.root)

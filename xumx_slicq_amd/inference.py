@@ -301,6 +301,8 @@ def parse_args(p: argparse.ArgumentParser, argv=None):
         for opt in ("softmask", "residual"):
             if getattr(args, opt):
                 p.error(f"--{opt} is an option of the Wiener filter, which cannot stream; --stream is mix-phase")
+        if args.long_bands:
+            p.error("--stream cannot run on a --long-bands plan: Separator.stream refuses it")
         if not args.realtime and (args.niter is None or args.niter >= 1):
             p.error("--stream is mix-phase: the Wiener-EM of the offline model (--niter >= 1, its default) spans 5000-frame windows and "
                     "cannot stream; use --realtime or --niter 0")
@@ -342,6 +344,11 @@ def cli_parser() -> argparse.ArgumentParser:
                         "--overlap, --softmask, --residual")
     p.add_argument("--hop-slices", type=int, default=None, metavar="M",
                    help="blocks of sllen / 2 samples per step of the --stream session (default 1)")
+    p.add_argument("--long-bands", action="store_true",
+                   help="accept a model trained on the cqlog or vqlog scale: its bands above 320 samples run on the FFT band engine; "
+                        "one track at a time, not with --stream")
+    p.add_argument("--fgamma", type=float, default=15.0, metavar="HZ",
+                   help="offset of the vqlog band centres where the model's JSON names none (default 15.0)")
     return p
 
 
@@ -355,10 +362,13 @@ def inference_main(argv=None):
     if args.model_path:
         separator = Separator.load(model_path=args.model_path, runtime_backend="hip-rocm",
                                    warmup=args.warmup, realtime=args.realtime, device=args.device, niter=args.niter,
-                                   softmask=args.softmask or None, residual=args.residual or None)
+                                   softmask=args.softmask or None, residual=args.residual or None, long_bands=args.long_bands,
+                                   fgamma=args.fgamma)
     else:
         separator = seeded_separator(realtime=args.realtime, device=args.device, niter=args.niter, softmask=args.softmask or None,
-                                     residual=args.residual or None)
+                                     residual=args.residual or None, long_bands=args.long_bands, fgamma=args.fgamma)
+    if separator.long_bands:
+        args.serial = True       # demix_directory batches tracks through demix_into, which such a plan does not serve
     overlapped = overlapped_option(args)
     if overlapped is not None:
         try:

@@ -90,14 +90,17 @@ class Separator(nn.Module):
     def load(cls, chunk_size: int = 2621440, model_path: Optional[str] = None,
              runtime_backend: Optional[str] = _ACCELERATED, warmup: int = 0, realtime: bool = False,
              device: Union[str, torch.device] = "cuda", niter: Optional[int] = None, softmask: Optional[bool] = None,
-             residual: Optional[bool] = None, dc_twins: bool = False):
+             residual: Optional[bool] = None, dc_twins: bool = False, long_bands: bool = False, fgamma: float = 15.0):
         """separator.py:50-93.  ``niter``, ``softmask``, ``residual`` (extensions): the options of the Wiener post-filter, see the
         properties of the same names.  ``dc_twins``: accept a checkpoint whose plan has bands across DC and decode it with the
-        reference's mirrored synthesis (``plan.build_plan``); the default refuses such a plan."""
+        reference's mirrored synthesis (``plan.build_plan``); the default refuses such a plan.  ``long_bands``: accept a checkpoint
+        trained on ``cqlog`` or ``vqlog`` (``fgamma``: the offset of the latter's centres, unless the JSON names one) and run its
+        bands above 320 samples on the FFT band engine."""
         if runtime_backend not in _SUPPORTED_RUNTIMES:
             raise ValueError(f"requested runtime backend {runtime_backend} not in {_SUPPORTED_RUNTIMES}")
         xumx_model, encoder, sample_rate = load_target_models(
-            model_path, runtime_backend=runtime_backend, realtime=realtime, device=device, dc_twins=dc_twins)
+            model_path, runtime_backend=runtime_backend, realtime=realtime, device=device, dc_twins=dc_twins,
+            long_bands=long_bands, fgamma=fgamma)
         separator = cls(xumx_model=xumx_model, encoder=encoder, sample_rate=sample_rate,
                         runtime_backend=runtime_backend, chunk_size=chunk_size, device=device).to(device)
         separator.freeze()
@@ -130,6 +133,12 @@ class Separator(nn.Module):
         """The plan was built with ``dc_twins=True``: the inverse transforms add the mirrored synthesis of the bands across DC.
         ``stream``, ``demix_into`` (sharding) and ``Trainer`` refuse such a separator."""
         return bool(getattr(self.nsgt.nsgt.plan, "dc_twins", False))
+
+    @property
+    def long_bands(self) -> bool:
+        """The plan was built with ``long_bands=True``: the bands above 320 samples run on the FFT band engine, which opens the
+        scales ``cqlog`` and ``vqlog``.  ``stream``, ``demix_into`` (sharding) and ``Trainer`` refuse such a separator."""
+        return bool(getattr(self.nsgt.nsgt.plan, "long_bands", False))
 
     def freeze(self):
         for p in self.parameters():
@@ -342,6 +351,9 @@ class Separator(nn.Module):
         if self.dc_twins:
             raise _lib.XsqError("demix_into / sharding: a plan with bands across DC (dc_twins = True) is served by forward, forward_graphed, "
                                 "forward_overlapped and remix only")
+        if self.long_bands:
+            raise _lib.XsqError("demix_into / sharding: a plan with bands on the FFT band engine (long_bands = True) is served by forward, "
+                                "forward_graphed, forward_overlapped and remix only")
         x_rows, keep = None, None
         if isinstance(audio, (list, tuple)):
             keep = list(audio)
@@ -802,6 +814,9 @@ class StreamSession:
         if getattr(separator, "dc_twins", False):
             raise _lib.XsqError("stream: a plan with bands across DC (dc_twins = True) cannot stream: the mirrored synthesis turns with the "
                                 "parity of a slice's index in the whole stream, which the carried step does not keep")
+        if getattr(separator, "long_bands", False):
+            raise _lib.XsqError("stream: a plan with bands on the FFT band engine (long_bands = True) cannot stream: the carried step has "
+                                "not been taken through blocks of thousands of frames")
         self.separator = separator
         self.nb_samples, self.hop_slices = int(nb_samples), int(hop_slices)
         self.back, self.ahead = STREAM_BACK[causal.pop()], STREAM_AHEAD
@@ -991,10 +1006,10 @@ def aggregate_gains(aggregate_dict: dict):
 
 def build_models(fscale: str = "bark", fbins: int = 262, fmin: float = 32.9, sample_rate: float = 44100.0,
                  seq_dur: float = 2.0, realtime: bool = False, device="cuda", state=None,
-                 strict: bool = True, dc_twins: bool = False):
+                 strict: bool = True, dc_twins: bool = False, long_bands: bool = False, fgamma: float = 15.0):
     """Plan + filterbanks + Unmix from explicit config (what load_target_models does after
-    reading the JSON, separator.py:321-356).  ``dc_twins``: see ``plan.build_plan``."""
-    nsgt_base = NSGTBase(fscale, fbins, fmin, fs=sample_rate, device=device, dc_twins=dc_twins)
+    reading the JSON, separator.py:321-356).  ``dc_twins``, ``long_bands``, ``fgamma``: see ``plan.build_plan``."""
+    nsgt_base = NSGTBase(fscale, fbins, fmin, fgamma=fgamma, fs=sample_rate, device=device, dc_twins=dc_twins, long_bands=long_bands)
     jagged_slicq, _ = nsgt_base.predict_input_size(1, 2, seq_dur)
     cnorm = ComplexNorm()
     nsgt, insgt = make_filterbanks(nsgt_base, sample_rate)
@@ -1007,9 +1022,9 @@ def build_models(fscale: str = "bark", fbins: int = 262, fmin: float = 32.9, sam
 
 
 def load_target_models(model_path: str, runtime_backend: str = _ACCELERATED, realtime: bool = False,
-                       device="cuda", dc_twins: bool = False):
+                       device="cuda", dc_twins: bool = False, long_bands: bool = False, fgamma: float = 15.0):
     """separator.py:262-387 for the accelerated backend: <model_path>/xumx_slicq_v2.json
-    (args.sample_rate, fscale, fbins, fmin, seq_dur, realtime) + xumx_slicq_v2.pth."""
+    (args.sample_rate, fscale, fbins, fmin, seq_dur, realtime; fgamma where the key is there, else the keyword) + xumx_slicq_v2.pth."""
     if runtime_backend != _ACCELERATED:
         raise ValueError(f"unsupported runtime backend: {runtime_backend}")
     if model_path is None:
@@ -1026,16 +1041,19 @@ def load_target_models(model_path: str, runtime_backend: str = _ACCELERATED, rea
     state = torch.load(pth, map_location="cpu")
     args = results["args"]
     return build_models(args["fscale"], args["fbins"], args["fmin"], args["sample_rate"], args["seq_dur"],
-                        realtime=args["realtime"], device=device, state=state, dc_twins=dc_twins)
+                        realtime=args["realtime"], device=device, state=state, dc_twins=dc_twins, long_bands=long_bands,
+                        fgamma=float(args.get("fgamma", fgamma)))
 
 
 def seeded_separator(realtime: bool = False, wiener: Optional[bool] = None, seed: int = 1234,
                      device="cuda", chunk_size: int = 2621440, niter: Optional[int] = None, softmask: Optional[bool] = None,
-                     residual: Optional[bool] = None, dc_twins: bool = False, **cfg) -> Separator:
-    """Separator with the seeded synthetic weights (no checkpoint exists offline).  ``dc_twins``: see ``plan.build_plan``.
+                     residual: Optional[bool] = None, dc_twins: bool = False, long_bands: bool = False, fgamma: float = 15.0,
+                     **cfg) -> Separator:
+    """Separator with the seeded synthetic weights (no checkpoint exists offline).  ``dc_twins``, ``long_bands``, ``fgamma``: see
+    ``plan.build_plan``.
     ``wiener`` overrides the post-filter: None follows the reference (offline -> Wiener-EM,
     realtime -> mix-phase); False on the offline stack is BASELINE config 2."""
-    xumx_model, encoder, sr = build_models(realtime=realtime, device=device, dc_twins=dc_twins, **cfg)
+    xumx_model, encoder, sr = build_models(realtime=realtime, device=device, dc_twins=dc_twins, long_bands=long_bands, fgamma=fgamma, **cfg)
     xumx_model.load_state_dict(seeded_state_dict(xumx_model.table.shapes, seed=seed), strict=True)
     if wiener is not None:
         for blk in xumx_model.sliced_umx:      # the flag the reference reads at model.py:264

@@ -459,6 +459,9 @@ class ShardedDemixer:
         if getattr(separator, "dc_twins", False):
             from ._lib import XsqError
             raise XsqError("sharding: a plan with bands across DC (dc_twins = True) is served by Separator.forward only")
+        if getattr(separator, "long_bands", False):
+            from ._lib import XsqError
+            raise XsqError("sharding: a plan with bands on the FFT band engine (long_bands = True) is served by Separator.forward only")
         self.sep, self.get_chunk, self.dev, self.group, self.gather = separator, get_chunk, torch.device(device), group, gather
         self.exchange, self.fallback, self.exchange_note = exchange, bool(fallback), None
         live = dist.is_initialized() and not solo

@@ -96,6 +96,9 @@ class Trainer:
         if getattr(getattr(getattr(self.nsgt, "nsgt", None), "plan", None), "dc_twins", False):
             raise _lib.XsqError("training on a plan with bands across DC (dc_twins = True) is not supported: the training step has not "
                                 "been held to the reference on such a plan; build the plan without the flag (it is then refused by name)")
+        if getattr(getattr(getattr(self.nsgt, "nsgt", None), "plan", None), "long_bands", False):
+            raise _lib.XsqError("training on a plan with bands on the FFT band engine (long_bands = True) is not supported: the training "
+                                "step's kernels have not been taken through blocks of thousands of frames")
         self._spec = [(k, tuple(v.shape)) for k, v in unmix.state_dict().items() if not k.endswith("num_batches_tracked")]
         params = unmix.packed_parameters()
         self.nparams = int(params.size)
